@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Genima hot-path benchmark on MI355X (driver contract: one JSON line from rank 0).
 
-    python bench.py --gpus N --steps K --warmup W [--workload tiled_b8|single_b1] [--graph]
+    python bench.py --gpus N --steps K --warmup W [--workload tiled_b8|single_b1] [--graph] [--dump-outputs DIR]
 
 A "step" is ONE pipeline call of the hot path (metric 1): CLIP text encode -> ControlNet cond-embedding ->
 5 x (ControlNet + UNet + Euler step) -> VAE decode -> uint8 post-process, on a batch of synthetic tiled observations with
@@ -17,6 +17,9 @@ N > 1: one process per GPU under torch.distributed.run; inference shards episode
 Extra objects on the JSON line (rank 0, N = 1 only): `roofline` (dominant kernel family: the MFMA implicit-GEMM conv /
 linear kernel; per-op HIP-event timing of one replay of the recorded program), `roofline_extra` (attention: MFMA; GroupNorm
 +SiLU: HBM) and `cpu_baseline` (the fp32 torch-CPU oracle timed on this box's host cores on a bounded sample).
+
+--dump-outputs DIR (rank 0): what the last timed call returned -- the uint8 tiled images and, with the ACT controller, its actions --
+as DIR/<name>.npy in float32, so two builds run with the same arguments (same seeded inputs) can be compared output for output.
 """
 from __future__ import annotations
 
@@ -112,6 +115,26 @@ def synthetic_inputs(pipe, B, H, W, device, rank):
     g = torch.Generator().manual_seed(2 + rank)  # diffusion_seed = 2 (controller/cfgs/eval_genima.yaml:32)
     lat = torch.randn(B, 4, H // 8, W // 8, generator=g).to(torch.float16)
     return ids.to(device), img.to(device), lat.to(device)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as ``out_dir/<name>.npy`` in float32, at most DUMP_MAX_BYTES in all.  When the arrays are larger than that, each
+    one over its share keeps a fixed, seeded sample of its flattened elements, with their flat indices in ``<name>_index.npy``."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    keep = DUMP_MAX_BYTES // (8 * max(1, len(arrays)))  # elements per array: a float32 value + an int32 index each
+    sample = sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES
+    for name, a in arrays.items():
+        if sample and a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False)).astype(np.int32)
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def per_op_profile(pipe, io, dump=None):
@@ -301,7 +324,10 @@ def main():
     ap.add_argument("--train-steps", type=int, default=10)
     ap.add_argument("--no-act", action="store_true", help="skip the ACT controller forward after each pipeline call")
     ap.add_argument("--dump-ops", default=None, help="write the per-(kernel, shape) HIP-event timing table of one call to this CSV")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed call's outputs to DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from genima_amd.dist import maybe_self_launch
 
@@ -383,7 +409,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         tc = time.perf_counter()
-        call("np")
+        last = call("np")
         per_call.append(time.perf_counter() - tc)
     barrier()
     dt = time.perf_counter() - t0
@@ -395,6 +421,9 @@ def main():
     value = units * B * world * calls / dt
     per_call.sort()
     median_call = per_call[len(per_call) // 2] if len(per_call) % 2 else 0.5 * (per_call[len(per_call) // 2 - 1] + per_call[len(per_call) // 2])
+    if rank == 0 and args.dump_outputs:
+        # images: [B, H, W, 3] uint8 tiled observations; actions: [B, chunk, action_dim] from the ACT controller
+        dump_outputs(args.dump_outputs, dict(zip(("images", "actions"), last)) if isinstance(last, tuple) else {"images": last.images})
 
     # back-to-back bracket: the same K calls queued without waiting for their outputs (no D->H), rank-local, informational
     barrier()

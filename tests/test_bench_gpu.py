@@ -56,3 +56,16 @@ def test_bench_two_ranks_share_the_device_over_gloo():
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 2 and out["value"] > 0
     assert "roofline" not in out  # rank-0-at-N=1-only extras stay out of multi-rank lines
     assert out["train"]["n_gpus"] == 2 and out["train"]["config"]["parallelism"] == "dp2" and out["train"]["ms_per_step"] > 0
+
+
+def test_bench_dumps_the_last_timed_calls_outputs(tmp_path):
+    """--dump-outputs: the uint8 tiled images and the ACT actions of the last timed call, as float32 .npy files; --steps sets the timed calls."""
+    import numpy as np
+
+    out = _run(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0", "--workload", "tiled_b1", "--no-train", "--no-cpu-baseline",
+                "--no-single-view", "--no-roofline", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2
+    images, actions = np.load(tmp_path / "images.npy"), np.load(tmp_path / "actions.npy")
+    assert images.dtype == np.float32 and images.shape == (1, 512, 512, 3)
+    assert images.min() >= 0 and images.max() <= 255 and (images == np.round(images)).all() and images.std() > 0
+    assert actions.dtype == np.float32 and actions.shape[0] == 1 and np.isfinite(actions).all()
