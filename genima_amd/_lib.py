@@ -17,6 +17,7 @@ if os.environ.get("GN_LIB_PATH"):  # same-box A/B of library builds (tools/probe
 # enums of genima_hip.h
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU, ACT_RELU, ACT_GEGLU, ACT_TANH3 = 0, 1, 2, 3, 4, 5, 6
 OUT_ROWMAJOR, OUT_BATCH_TRANSPOSED, OUT_F32 = 0, 1, 2
+GEMM_REG, GEMM_DMA, GEMM_PP, GEMM_RING, GEMM_PPP = 0, 1, 2, 3, 4  # kernel families of the gn_gemm tiles
 
 
 class GenimaHipError(RuntimeError):
@@ -61,6 +62,11 @@ class GemmDesc(C.Structure):
         ("k_append", C.c_int32), ("a3", C.c_void_p), ("C3", C.c_int32), ("lda2", C.c_int64),
         ("sink", StatsSink), ("norm_in", NormIn), ("norm_out", NormOut),
     ]
+
+
+class GemmTile(C.Structure):
+    """gn_gemm_tile: one block-tile configuration of gn_gemm (gn_gemm_tile_info)."""
+    _fields_ = [("bm", C.c_int32), ("bn", C.c_int32), ("family", C.c_int32), ("geglu", C.c_int32), ("fp8", C.c_int32)]
 
 
 class AttnDesc(C.Structure):
@@ -136,6 +142,8 @@ SIGNATURES = {
     "gn_ctx_set_stream": (_I32, [_P, _P]),
     "gn_gemm_workspace_bytes": (_I64, [C.POINTER(GemmDesc)]),
     "gn_gemm_plan_valid": (_I32, [C.POINTER(GemmDesc)]),
+    "gn_gemm_tile_info": (_I32, [_I32, C.POINTER(GemmTile)]),
+    "gn_gemm_norm_in_tile_fits": (_I32, [_I32, _I64, _I64]),
     "gn_ppp_timeouts": (_I64, []),
     "gn_ppp_profile_read": (_I32, [C.POINTER(C.c_uint32), _I32]),
     "gn_gemm": (_I32, [_P, C.POINTER(GemmDesc)]),
@@ -307,6 +315,23 @@ def load() -> C.CDLL:
                                  "binding (stale build? run `python -m genima_amd.build`)")
     _lib = lib
     return lib
+
+
+_tiles = None
+
+
+def gemm_tiles() -> dict:
+    """-> {tile: GemmTile} of every block-tile configuration of the library, in tile order (gn_gemm_desc::tile 1 .. GN_NUM_GEMM_TILES)."""
+    global _tiles
+    if _tiles is None:
+        lib, tiles = load(), {}
+        while True:
+            t = GemmTile()
+            if lib.gn_gemm_tile_info(len(tiles) + 1, C.byref(t)) != 0:
+                break
+            tiles[len(tiles) + 1] = t
+        _tiles = tiles
+    return _tiles
 
 
 def check(rc: int, what: str = ""):

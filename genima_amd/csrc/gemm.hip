@@ -800,36 +800,12 @@ struct Plan {
   int bm, bn, splitk, kper;
 };
 
-// tile configurations: {BM, BN, relative MFMA rate on large problems (tools/bench_gemm.py), GEGLU-capable (wave tile >= 64
-// columns)}.  Index + 1 is the public gn_gemm_desc::tile value.
-struct Cfg { int bm, bn; double eff; bool geglu; bool dma; };
-constexpr Cfg kCfg[] = {{256, 128, 1.00, true, false}, {128, 128, 1.00, true, false}, {128, 64, 0.85, false, false},
-                        {64, 64, 0.65, false, false},  {256, 64, 0.90, true, false},  {128, 256, 1.00, true, false},
-                        // LDS-DMA variants (never picked by the fallback heuristic: eff 0; the host autotuner times them)
-                        {256, 256, 0.0, true, true},   {256, 128, 0.0, true, true},   {128, 128, 0.0, true, true},
-                        {128, 64, 0.0, false, true},   {64, 64, 0.0, false, true},    {256, 64, 0.0, true, true},
-                        // 320-wide N tiles: the 64x64-latent UNet level (N = 320) without padded-tile waste
-                        {128, 320, 0.0, false, true},  {256, 320, 0.0, false, true},
-                        // ping-pong 256x256 (gemm_pp.hip): counted-vmcnt 8-phase K loop
-                        {256, 256, 0.0, false, true},
-                        // 3-stage LDS-DMA ring (gemm_s3.hip): two K tiles in flight, counted vmcnt -- the latency-bound mid-size launches
-                        {128, 128, 0.0, true, true},   {128, 64, 0.0, false, true},   {64, 64, 0.0, false, true},    {256, 64, 0.0, true, true},
-                        // exact-fit ring tiles: N = 640 / 1280 / 320 problems whose 128x64 / 128x128 grids leave the 256 CUs 1.25 .. 2.5
-                        // workgroups each (the K loop of those launches is bound by L2 -> LDS bytes per CU: bigger tile, fewer bytes)
-                        {128, 160, 0.0, false, true},  {64, 160, 0.0, false, true},   {64, 320, 0.0, false, true},
-                        // 2-stage 128x160 (two workgroups per CU)
-                        {128, 160, 0.0, false, true},
-                        // 2-stage 128x320 on EIGHT waves of 32x160 (round 5): the wave tile of the 128x160 tile with all of N = 320 in one workgroup --
-                        // the A tile is staged once for both column halves (10.9 instead of 14 LDS-DMA bytes per kFLOP), one workgroup per CU
-                        {128, 320, 0.0, false, true},
-                        // persistent skewed ping-pong 256x256 (gemm_ppp.hip, round 6): one workgroup per CU walks the tile list; the next tile's ring is
-                        // requested before the finished tile's epilogue, tile boundaries are skewed over the chip, the last partial round is split along K
-                        {256, 256, 0.0, true, true}};
-constexpr int kNumCfg = 25;
-constexpr int kCfgPPP = 24;
-constexpr int kCfgS3End = 22;  // one past the last 3-stage configuration
-constexpr int kCfgPP = 14;
-constexpr int kCfgS3 = 15;  // first of the four 3-stage configurations
+// named rows of kCfg (gemm_common.h)
+constexpr int kReg128x128 = cfg_row(GN_GEMM_REG, 128, 128);  // the heuristic's start, and GEGLU's tile when the requested one lacks it
+constexpr int kDma256x256 = cfg_row(GN_GEMM_DMA, 256, 256);
+constexpr int kPingPong = cfg_row(GN_GEMM_PP, 256, 256);
+constexpr int kRing64x64 = cfg_row(GN_GEMM_RING, 64, 64);
+constexpr int kRing64x160 = cfg_row(GN_GEMM_RING, 64, 160);
 
 // the ping-pong kernel's extra restrictions on top of dma_eligible (gemm_pp.hip header)
 bool pp_eligible(const gn_gemm_desc* d) {
@@ -901,6 +877,12 @@ bool dma_eligible(const gn_gemm_desc* d) {
   return true;
 }
 
+// norm_in on ring row c: LDS of the ring + the scale / shift table of the samples a row tile touches (launch_s3_gna), ct normalised channels
+constexpr int64_t kCuLdsBytes = 160 * 1024;
+int64_t ring_lds_bytes(int c, int64_t rps, int64_t ct) {
+  return (int64_t)3 * (kCfg[c].bm + kCfg[c].bn) * 128 + (rps >= kCfg[c].bm ? 1 : kCfg[c].bm / (rps > 0 ? rps : 1)) * ct * 8;
+}
+
 int g_tile_override = -2;
 int tile_override() {
   if (g_tile_override == -2) {
@@ -916,7 +898,7 @@ Plan plan_gemm(const gn_gemm_desc* d) {
   const int64_t M = d->M, N = d->N, K = d->K;
   Plan pl;
   const bool geglu = d->act == GN_ACT_GEGLU;
-  int best = 1;
+  int best = kReg128x128;
   {
     // fallback heuristic when the caller did not autotune (genima_amd/engine.py times every configuration per shape):
     // score = tile efficiency x useful fraction of the padded grid x how evenly the grid fills the 256 CUs
@@ -936,32 +918,22 @@ Plan plan_gemm(const gn_gemm_desc* d) {
   const int ov = tile_override();
   if (ov >= 0 && ov < kNumCfg) best = ov;
   if (d->tile >= 1 && d->tile <= kNumCfg) best = d->tile - 1;
-  if (geglu && !kCfg[best].geglu) best = 1;
-  if (d->ln_c1) {  // LayerNorm fold: the LDS-DMA kernels (two-stage and ring) carry it
-    static const int to_dma[kNumCfg] = {7, 8, 9, 10, 11, 8, 6, 7, 8, 9, 10, 11, 12, 13, 6, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24};
-    best = to_dma[best];
-  }
-  if (d->k_append && !kCfg[best].dma) {  // the appended segment lives in the LDS-DMA loaders
-    static const int to_dma[kNumCfg] = {7, 8, 9, 10, 11, 8, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24};
-    best = to_dma[best];
-  }
-  if (d->norm_in.stats) {  // the normalising A path lives in the ring kernels (gemm_s3.hip): 15 .. 21 = {128x128, 128x64, 64x64, 256x64, 128x160, 64x160, 64x320}
-    static const int to_s3[kNumCfg] = {18, 15, 16, 17, 18, 15, 15, 18, 15, 16, 17, 18, 19, 19, 15, 15, 16, 17, 18, 19, 20, 21, 19, 19, 15};
-    best = to_s3[best];
+  if (geglu && !kCfg[best].geglu) best = kReg128x128;
+  // LayerNorm fold: the LDS-DMA kernels (two-stage, ring, persistent ping-pong) carry it
+  if (d->ln_c1 && (kCfg[best].family == GN_GEMM_REG || kCfg[best].family == GN_GEMM_PP)) best = kCfg[best].dma;
+  if (d->k_append && kCfg[best].family == GN_GEMM_REG) best = kCfg[best].dma;  // the appended segment lives in the LDS-DMA loaders
+  if (d->norm_in.stats) {  // the normalising A path lives in the ring kernels (gemm_s3.hip)
+    best = kCfg[best].ring;
     // a row tile spans whole samples or lies inside one (the kernel's scale / shift table covers <= 4 of them)
     const int64_t rps = d->conv ? (int64_t)d->Ho * d->Wo : d->norm_in.rows_per_sample;
-    if (rps > 0 && kCfg[best].bm > 4 * rps) best = kCfg[best].bn >= 160 ? 20 : 17;  // -> a 64-row tile
-    // the ring + the scale / shift table of the samples a row tile touches must fit the CU's 160 KB (launch_s3_gna): else the 64 x 64 ring
+    if (rps > 0 && kCfg[best].bm > 4 * rps) best = kCfg[best].bn >= 160 ? kRing64x160 : kRing64x64;  // -> a 64-row tile
+    // the ring + the scale / shift table of the samples a row tile touches must fit the CU's LDS: else the 64 x 64 ring
     const int64_t ct = d->conv ? (d->k_append ? d->C1 : d->C1 + d->C2) : (d->k_append ? d->K - d->C2 : d->K);
-    auto lds_bytes = [&](int c) { return (int64_t)3 * (kCfg[c].bm + kCfg[c].bn) * 128 + (rps >= kCfg[c].bm ? 1 : kCfg[c].bm / (rps > 0 ? rps : 1)) * ct * 8; };
-    if (lds_bytes(best) > 160 * 1024) best = 17;
+    if (ring_lds_bytes(best, rps, ct) > kCuLdsBytes) best = kRing64x64;
   }
-  if (best == kCfgPPP && !ppp_eligible(d)) best = (geglu || d->ln_c1) ? 6 : kCfgPP;
-  if (best == kCfgPP && !pp_eligible(d)) best = 6;
-  if (kCfg[best].dma && !dma_eligible(d)) {
-    static const int fallback[kNumCfg] = {0, 1, 2, 3, 4, 5, 0, 0, 1, 2, 3, 4, 1, 0, 0, 1, 2, 3, 4, 1, 2, 2, 1, 1, 0};
-    best = fallback[best];
-  }
+  if (kCfg[best].family == GN_GEMM_PPP && !ppp_eligible(d)) best = (geglu || d->ln_c1) ? kDma256x256 : kPingPong;
+  if (kCfg[best].family == GN_GEMM_PP && !pp_eligible(d)) best = kDma256x256;
+  if (kCfg[best].family != GN_GEMM_REG && !dma_eligible(d)) best = kCfg[best].reg;
   {  // audit aid: GN_GEMM_LOG_FALLBACK=1 reports every launch whose requested tile (the tune table's) is not the tile that runs
     static const bool log_fb = getenv("GN_GEMM_LOG_FALLBACK") && atoi(getenv("GN_GEMM_LOG_FALLBACK")) != 0;
     if (log_fb && d->tile >= 1 && d->tile <= kNumCfg && best != d->tile - 1)
@@ -987,7 +959,7 @@ Plan plan_gemm(const gn_gemm_desc* d) {
       if (sk < 1) sk = 1;
     }
   }
-  if (d->act == GN_ACT_GEGLU || d->out_mode == GN_OUT_BATCH_TRANSPOSED || d->batch > 1 || d->fp8 || d->out2 || d->ln_c1 || best == kCfgPPP) sk = 1;
+  if (d->act == GN_ACT_GEGLU || d->out_mode == GN_OUT_BATCH_TRANSPOSED || d->batch > 1 || d->fp8 || d->out2 || d->ln_c1 || kCfg[best].family == GN_GEMM_PPP) sk = 1;
   int kper = (int)(cdiv64(cdiv64(K, sk), BK) * BK);
   sk = (int)cdiv64(K, kper);
   pl.splitk = sk;
@@ -1000,6 +972,18 @@ Plan plan_gemm(const gn_gemm_desc* d) {
 extern "C" int32_t gn_set_gemm_tile_override(int32_t cfg) {
   g_tile_override = cfg < 0 ? -1 : cfg;
   return GN_OK;
+}
+
+extern "C" int32_t gn_gemm_tile_info(int32_t tile, gn_gemm_tile* out) {
+  if (tile < 1 || tile > kNumCfg || !out) { gn_set_error("gn_gemm_tile_info: tile %d outside 1 .. %d, or null out", tile, kNumCfg); return GN_ERR_INVALID; }
+  const GemmCfg& c = kCfg[tile - 1];
+  *out = {c.bm, c.bn, c.family, c.geglu, c.fp8};
+  return GN_OK;
+}
+
+extern "C" int32_t gn_gemm_norm_in_tile_fits(int32_t tile, int64_t rows_per_sample, int64_t ct) {
+  if (tile < 1 || tile > kNumCfg || kCfg[tile - 1].family != GN_GEMM_RING || rows_per_sample <= 0) return 0;
+  return kCfg[tile - 1].bm <= 4 * rows_per_sample && ring_lds_bytes(tile - 1, rows_per_sample, ct) <= kCuLdsBytes;
 }
 
 extern "C" int32_t gn_gemm_norm_in_supported(const gn_gemm_desc* d) {
@@ -1049,7 +1033,7 @@ extern "C" int32_t gn_gemm_plan_valid(const gn_gemm_desc* d) {
   }
   if (d->norm_in.stats) {
     if (!gn_gemm_norm_in_supported(d) || !d->norm_in.gamma || !d->norm_in.beta) { gn_set_error("norm_in: unsupported problem (gn_gemm_norm_in_supported) or missing gamma / beta"); return 0; }
-    if (!(pl.cfg >= kCfgS3 && pl.cfg < kCfgS3End)) { gn_set_error("norm_in: the plan must be a ring tile (16 .. 22), tile %d runs", pl.cfg + 1); return 0; }
+    if (kCfg[pl.cfg].family != GN_GEMM_RING) { gn_set_error("norm_in: the plan must be a ring tile (16 .. 22), tile %d runs", pl.cfg + 1); return 0; }
     const int64_t rps = d->conv ? (int64_t)d->Ho * d->Wo : d->norm_in.rows_per_sample;
     if (pl.bm > 4 * rps) { gn_set_error("norm_in: a %d-row tile would span more than 4 samples of %ld rows", pl.bm, (long)rps); return 0; }
   }
@@ -1059,7 +1043,7 @@ extern "C" int32_t gn_gemm_plan_valid(const gn_gemm_desc* d) {
 extern "C" int64_t gn_gemm_workspace_bytes(const gn_gemm_desc* d) {
   if (!d) return 0;
   Plan pl = plan_gemm(d);
-  if (pl.cfg == kCfgPPP) {  // hand-off slabs of the tiles whose K range several workgroups share (gemm_ppp.hip)
+  if (kCfg[pl.cfg].family == GN_GEMM_PPP) {  // hand-off slabs of the tiles whose K range several workgroups share (gemm_ppp.hip)
     GemmParams p = {};
     p.K = (int)d->K;
     return (int64_t)gn_ppp_plan(&p, (int)ppp_tiles(d), ppp_workgroups()) * 256 * 256 * (int64_t)sizeof(float);
@@ -1200,7 +1184,7 @@ int32_t gn_launch_gemm(gn_ctx* ctx, const gn_gemm_desc* d) {
   if (d->norm_in.stats) {
     GN_REQUIRE(gn_gemm_norm_in_supported(d) && d->norm_in.gamma && d->norm_in.beta && ((uintptr_t)d->norm_in.stats & 7) == 0,
                "gn_gemm(norm_in): unsupported problem (gn_gemm_norm_in_supported) or missing gamma / beta");
-    GN_REQUIRE(pl.cfg >= kCfgS3 && pl.cfg < kCfgS3End, "gn_gemm(norm_in): the plan must be a ring tile (16 .. 22)");
+    GN_REQUIRE(kCfg[pl.cfg].family == GN_GEMM_RING, "gn_gemm(norm_in): the plan must be a ring tile (16 .. 22)");
     const int64_t rps = d->conv ? (int64_t)d->Ho * d->Wo : d->norm_in.rows_per_sample;
     GN_REQUIRE(pl.bm <= 4 * rps, "gn_gemm(norm_in): a %d-row tile would span more than 4 samples of %ld rows", pl.bm, (long)rps);
   }
@@ -1214,48 +1198,32 @@ int32_t gn_launch_gemm(gn_ctx* ctx, const gn_gemm_desc* d) {
     p.sa = (const float*)d->scale_a; p.sw = (const float*)d->scale_w;
     p.a_bytes = (unsigned)((uint64_t)d->M * d->lda); p.w_bytes = (unsigned)((uint64_t)d->N * d->ldw);
     p.splitk = 1; p.kper = (int)d->K;
-    static const int to_dma[kNumCfg] = {7, 8, 9, 10, 11, 8, 6, 7, 8, 9, 10, 11, 8, 7, 6, 8, 9, 10, 11, 8, 9, 9, 8, 8, 6};
-    const int cfg = to_dma[pl.cfg];
-    const int bm = kCfg[cfg].bm, bn = kCfg[cfg].bn;
-    p.tiles_m = (int)cdiv64(d->M, bm); p.tiles_n = (int)cdiv64(d->N, bn);
-    switch (cfg) {
-      case 6: launch_fp8<256, 256, 2, 4>(p, ctx->stream); break;
-      case 7: launch_fp8<256, 128, 4, 2>(p, ctx->stream); break;
-      case 8: launch_fp8<128, 128, 2, 2>(p, ctx->stream); break;
-      case 9: launch_fp8<128, 64, 2, 2>(p, ctx->stream); break;
-      case 10: launch_fp8<64, 64, 2, 2>(p, ctx->stream); break;
-      default: launch_fp8<256, 64, 4, 1>(p, ctx->stream); break;
-    }
+    const int cfg = kCfg[pl.cfg].dma;
+    p.tiles_m = (int)cdiv64(d->M, kCfg[cfg].bm); p.tiles_n = (int)cdiv64(d->N, kCfg[cfg].bn);
+    with_cfg(cfg, [&](auto row) {
+      constexpr GemmCfg c = kCfg[row];
+      if constexpr (c.fp8) launch_fp8<c.bm, c.bn, c.wm, c.wn>(p, ctx->stream);
+    });
     GN_LAUNCH_CHECK();
     return GN_OK;
   }
   const bool conv = d->conv != 0;
-  switch (pl.cfg) {
-    case 0: launch_cfg<256, 128, 4, 2>(p, conv, ctx->stream); break;
-    case 1: launch_cfg<128, 128, 2, 2>(p, conv, ctx->stream); break;
-    case 2: launch_cfg<128, 64, 2, 2>(p, conv, ctx->stream); break;
-    case 3: launch_cfg<64, 64, 2, 2>(p, conv, ctx->stream); break;
-    case 4: launch_cfg<256, 64, 4, 1>(p, conv, ctx->stream); break;
-    case 5: launch_cfg<128, 256, 2, 4>(p, conv, ctx->stream); break;
-    case 6: launch_dma<256, 256, 2, 4>(p, conv, ctx->stream); break;
-    case 7: launch_dma<256, 128, 4, 2>(p, conv, ctx->stream); break;
-    case 8: launch_dma<128, 128, 2, 2>(p, conv, ctx->stream); break;
-    case 9: launch_dma<128, 64, 2, 2>(p, conv, ctx->stream); break;
-    case 10: launch_dma<64, 64, 2, 2>(p, conv, ctx->stream); break;
-    case 11: launch_dma<256, 64, 4, 1>(p, conv, ctx->stream); break;
-    case 12: launch_dma<128, 320, 2, 2>(p, conv, ctx->stream); break;
-    case 13: launch_dma<256, 320, 4, 2>(p, conv, ctx->stream); break;
-    case 14: gn_launch_gemm_pp(&p, conv, p.tiles_m * p.tiles_n, p.splitk, p.nbatch > 0 ? p.nbatch : 1, ctx->stream); break;
-    case kCfgPPP: {
+  switch (kCfg[pl.cfg].family) {
+    case GN_GEMM_PP: gn_launch_gemm_pp(&p, conv, p.tiles_m * p.tiles_n, p.splitk, p.nbatch > 0 ? p.nbatch : 1, ctx->stream); break;
+    case GN_GEMM_PPP: {
       GN_REQUIRE(d->workspace, "gn_gemm: tile 25 (persistent ping-pong) needs a workspace of gn_gemm_workspace_bytes()");
       (void)gn_ppp_plan(&p, (int)ppp_tiles(d), ppp_workgroups());
       GN_REQUIRE(gn_ppp_pool_init(ctx->device) == GN_OK, "gn_gemm: tile 25 could not allocate its flag pool (first use inside a stream capture?): %s", gn_last_error());
       gn_launch_gemm_ppp(&p, conv, ctx->stream);
       break;
     }
-    case 22: launch_dma<128, 160, 4, 1>(p, conv, ctx->stream); break;
-    case 23: launch_dma<128, 320, 4, 2>(p, conv, ctx->stream); break;
-    default: gn_launch_gemm_s3(&p, pl.cfg - kCfgS3, conv, p.tiles_m * p.tiles_n, p.splitk, p.nbatch > 0 ? p.nbatch : 1, ctx->stream); break;
+    case GN_GEMM_RING: gn_launch_gemm_s3(&p, pl.cfg, conv, p.tiles_m * p.tiles_n, p.splitk, p.nbatch > 0 ? p.nbatch : 1, ctx->stream); break;
+    default:
+      with_cfg(pl.cfg, [&](auto row) {
+        constexpr GemmCfg c = kCfg[row];
+        if constexpr (c.family == GN_GEMM_REG) launch_cfg<c.bm, c.bn, c.wm, c.wn>(p, conv, ctx->stream);
+        else if constexpr (c.family == GN_GEMM_DMA) launch_dma<c.bm, c.bn, c.wm, c.wn>(p, conv, ctx->stream);
+      });
   }
   GN_LAUNCH_CHECK();
   if (pl.splitk > 1) {

@@ -707,6 +707,91 @@ constexpr int gemm_waves_per_simd(int lds_bytes, int waves_per_block) {
 #define GN_PIN(x) asm volatile("" : "+v"(x))
 constexpr unsigned kOOB = 0xFFFFFFF0u;  // out-of-range buffer offset: the hardware writes zeros to LDS for such lanes
 
+// The block-tile configurations of gn_gemm: row index + 1 is the public gn_gemm_desc::tile value.  A row is its block and wave tile, its
+// relative MFMA rate on large problems (tools/bench_gemm.py; the fallback heuristic only considers eff > 0, the host autotuner times every
+// row), whether it carries GEGLU (wave tile >= 64 columns), its kernel family (GN_GEMM_*, include/genima_hip.h), whether the fp8 kernel
+// exists for it, and the rows that stand in for it where a problem needs what its family lacks:
+//   dma   the two-stage LDS-DMA tile with an fp8 kernel: fp8 always, ln_c1 (REG, PP) and k_append (REG)
+//   ring  the three-stage ring tile: norm_in
+//   reg   the register-staged tile: problems whose operands exceed the LDS-DMA loaders' 32-bit buffer offsets
+struct GemmCfg {
+  int bm, bn, wm, wn;  // wm x wn waves; 0 x 0 = the ping-pong kernels' own layout of 8 waves
+  double eff;
+  bool geglu;
+  int family;
+  bool fp8;
+  int dma, ring, reg;
+};
+constexpr GemmCfg kCfg[] = {
+    // register-staged
+    /*  0 */ {256, 128, 4, 2, 1.00, true, GN_GEMM_REG, false, 7, 18, 0},
+    /*  1 */ {128, 128, 2, 2, 1.00, true, GN_GEMM_REG, false, 8, 15, 1},
+    /*  2 */ {128, 64, 2, 2, 0.85, false, GN_GEMM_REG, false, 9, 16, 2},
+    /*  3 */ {64, 64, 2, 2, 0.65, false, GN_GEMM_REG, false, 10, 17, 3},
+    /*  4 */ {256, 64, 4, 1, 0.90, true, GN_GEMM_REG, false, 11, 18, 4},
+    /*  5 */ {128, 256, 2, 4, 1.00, true, GN_GEMM_REG, false, 8, 15, 5},
+    // two-stage LDS-DMA
+    /*  6 */ {256, 256, 2, 4, 0.0, true, GN_GEMM_DMA, true, 6, 15, 0},
+    /*  7 */ {256, 128, 4, 2, 0.0, true, GN_GEMM_DMA, true, 7, 18, 0},
+    /*  8 */ {128, 128, 2, 2, 0.0, true, GN_GEMM_DMA, true, 8, 15, 1},
+    /*  9 */ {128, 64, 2, 2, 0.0, false, GN_GEMM_DMA, true, 9, 16, 2},
+    /* 10 */ {64, 64, 2, 2, 0.0, false, GN_GEMM_DMA, true, 10, 17, 3},
+    /* 11 */ {256, 64, 4, 1, 0.0, true, GN_GEMM_DMA, true, 11, 18, 4},
+    // 320-wide N tiles: the 64x64-latent UNet level (N = 320) without padded-tile waste
+    /* 12 */ {128, 320, 2, 2, 0.0, false, GN_GEMM_DMA, false, 8, 19, 1},
+    /* 13 */ {256, 320, 4, 2, 0.0, false, GN_GEMM_DMA, false, 7, 19, 0},
+    // ping-pong 256x256 (gemm_pp.hip): counted-vmcnt 8-phase K loop
+    /* 14 */ {256, 256, 0, 0, 0.0, false, GN_GEMM_PP, false, 6, 15, 0},
+    // 3-stage LDS-DMA ring (gemm_s3.hip): two K tiles in flight, counted vmcnt -- the latency-bound mid-size launches
+    /* 15 */ {128, 128, 2, 2, 0.0, true, GN_GEMM_RING, false, 8, 15, 1},
+    /* 16 */ {128, 64, 2, 2, 0.0, false, GN_GEMM_RING, false, 9, 16, 2},
+    /* 17 */ {64, 64, 2, 2, 0.0, false, GN_GEMM_RING, false, 10, 17, 3},
+    /* 18 */ {256, 64, 4, 1, 0.0, true, GN_GEMM_RING, false, 11, 18, 4},
+    // exact-fit ring tiles: N = 640 / 1280 / 320 problems whose 128x64 / 128x128 grids leave the 256 CUs 1.25 .. 2.5 workgroups each (the
+    // K loop of those launches is bound by L2 -> LDS bytes per CU: bigger tile, fewer bytes)
+    /* 19 */ {128, 160, 4, 1, 0.0, false, GN_GEMM_RING, false, 8, 19, 1},
+    /* 20 */ {64, 160, 2, 1, 0.0, false, GN_GEMM_RING, false, 9, 20, 2},
+    /* 21 */ {64, 320, 2, 2, 0.0, false, GN_GEMM_RING, false, 9, 21, 2},
+    // 2-stage 128x160 (two workgroups per CU)
+    /* 22 */ {128, 160, 4, 1, 0.0, false, GN_GEMM_DMA, false, 8, 19, 1},
+    // 2-stage 128x320 on EIGHT waves of 32x160 (round 5): the wave tile of the 128x160 tile with all of N = 320 in one workgroup -- the A
+    // tile is staged once for both column halves (10.9 instead of 14 LDS-DMA bytes per kFLOP), one workgroup per CU
+    /* 23 */ {128, 320, 4, 2, 0.0, false, GN_GEMM_DMA, false, 8, 19, 1},
+    // persistent skewed ping-pong 256x256 (gemm_ppp.hip, round 6): one workgroup per CU walks the tile list; the next tile's ring is
+    // requested before the finished tile's epilogue, tile boundaries are skewed over the chip, the last partial round is split along K
+    /* 24 */ {256, 256, 0, 0, 0.0, true, GN_GEMM_PPP, false, 6, 15, 0},
+};
+constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
+static_assert(kNumCfg == GN_NUM_GEMM_TILES, "include/genima_hip.h names the tile count");
+
+constexpr bool cfg_substitutes_ok() {
+  for (int i = 0; i < kNumCfg; ++i) {
+    const GemmCfg& c = kCfg[i];
+    if (!kCfg[c.dma].fp8 || kCfg[c.ring].family != GN_GEMM_RING || kCfg[c.reg].family != GN_GEMM_REG) return false;
+    if ((c.fp8 && c.dma != i) || (c.family == GN_GEMM_RING && c.ring != i) || (c.family == GN_GEMM_REG && c.reg != i)) return false;
+    if (c.family != GN_GEMM_PP && c.family != GN_GEMM_PPP && c.wm * c.wn == 0) return false;
+  }
+  return true;
+}
+static_assert(cfg_substitutes_ok(), "kCfg: a substitute is not of its family, or a row of that family does not stand in for itself");
+
+// the row of family f with a bm x bn block tile
+constexpr int cfg_row(int f, int bm, int bn) {
+  for (int c = 0; c < kNumCfg; ++c)
+    if (kCfg[c].family == f && kCfg[c].bm == bm && kCfg[c].bn == bn) return c;
+  return -1;
+}
+
+// f(std::integral_constant<int, cfg>()): the launch sites instantiate their kernel templates from the row's constants (if constexpr on its
+// family), one per row of that family, so a new row cannot miss a case
+template <int C = 0, typename F>
+void with_cfg(int cfg, F&& f) {
+  if constexpr (C < kNumCfg) {
+    if (cfg == C) f(std::integral_constant<int, C>());
+    else with_cfg<C + 1>(cfg, f);
+  }
+}
+
 }  // namespace
 
 // the ping-pong 256x256 kernel lives in its own translation unit (gemm_pp.hip); `params` is a GemmParams
@@ -714,5 +799,5 @@ void gn_launch_gemm_pp(const void* params, bool conv, int grid_x, int grid_y, in
 // the persistent skewed ping-pong kernel (gemm_ppp.hip); the plan fields pp* of `params` are filled by gn_ppp_plan
 void gn_launch_gemm_ppp(const void* params, bool conv, hipStream_t st);
 int gn_ppp_plan(void* params, int tiles, int G);  // fills the pp* plan fields -> hand-off slabs (of 256 KB) the launch may use
-// the 3-stage ring variants (gemm_s3.hip); cfg 0..3 = {128x128, 128x64, 64x64, 256x64}
+// the 3-stage ring variants (gemm_s3.hip); cfg = a kCfg row of family GN_GEMM_RING
 void gn_launch_gemm_s3(const void* params, int cfg, bool conv, int grid_x, int grid_y, int grid_z, hipStream_t st);

@@ -2,7 +2,7 @@
 // the 2-stage kernel of gemm.hip has one K tile in flight and drains it (`vmcnt(0)` + barrier) every iteration, so each iteration costs
 // a full L2 / MALL round trip; here two tiles are in flight and the wait is counted.  Same tiles, loaders, swizzle and epilogue as
 // gemm_dma_kernel (gemm.hip); the per-lane validity selects become OR-masks so that every path issues the same number of VMEM
-// instructions (the counted vmcnt depends on it).  Tiles 16..19 of gn_gemm_desc::tile.
+// instructions (the counted vmcnt depends on it).  The GN_GEMM_RING rows of kCfg (gemm_common.h).
 #include <type_traits>
 
 #include "gemm_common.h"
@@ -418,14 +418,8 @@ void launch_s3(const GemmParams& p, bool conv, dim3 grid, hipStream_t st) {
 void gn_launch_gemm_s3(const void* params, int cfg, bool conv, int grid_x, int grid_y, int grid_z, hipStream_t st) {
   const GemmParams& p = *static_cast<const GemmParams*>(params);
   const dim3 grid(grid_x, grid_y, grid_z);
-  switch (cfg) {
-    case 0: launch_s3<128, 128, 2, 2>(p, conv, grid, st); break;
-    case 1: launch_s3<128, 64, 2, 2>(p, conv, grid, st); break;
-    case 2: launch_s3<64, 64, 2, 2>(p, conv, grid, st); break;
-    case 3: launch_s3<256, 64, 4, 1>(p, conv, grid, st); break;
-    // exact-fit tiles: N = 640 / 1280 / 320 problems whose 128x64 or 128x128 grids leave 256 CUs with 1.25 .. 2.5 workgroups each
-    case 4: launch_s3<128, 160, 4, 1>(p, conv, grid, st); break;
-    case 5: launch_s3<64, 160, 2, 1>(p, conv, grid, st); break;
-    default: launch_s3<64, 320, 2, 2>(p, conv, grid, st); break;
-  }
+  with_cfg(cfg, [&](auto row) {
+    constexpr GemmCfg c = kCfg[row];
+    if constexpr (c.family == GN_GEMM_RING) launch_s3<c.bm, c.bn, c.wm, c.wn>(p, conv, grid, st);
+  });
 }

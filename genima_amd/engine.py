@@ -22,7 +22,8 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, OUT_BATCH_TRANSPOSED, OUT_ROWMAJOR, TBLOCK_FRONT, TBLOCK_MID,
+from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, GEMM_DMA, GEMM_PP, GEMM_PPP, GEMM_RING,
+                   OUT_BATCH_TRANSPOSED, OUT_ROWMAJOR, TBLOCK_FRONT, TBLOCK_MID,
                    TBLOCK_TAIL, AttnDesc, ConvGnDesc, GemmDesc, GenimaHipError, GroupNormDesc, NormOut, StatsSink, TBlockDesc, TBlockTapeSrc, check)
 
 F16 = torch.float16
@@ -292,7 +293,6 @@ class Engine:
     # change the per-element summation order (K is walked identically), only split-K does, and split-K is a deterministic
     # function of (shape, tile).  The table measured on MI355X ships as genima_amd/gemm_tune_gfx950.json.
     _retuned = set()  # shapes already re-raced in this process (GN_RETUNE)
-    N_TILE_CFGS = 25  # 1..6 register-staged, 7..14 LDS-DMA, 15 ping-pong 256x256, 16..22 3-stage ring, 23 2-stage 128x160, 24 2-stage 128x320 on 8 waves, 25 persistent skewed ping-pong (csrc/gemm.hip kCfg, gemm_pp.hip, gemm_s3.hip, gemm_ppp.hip)
 
     @staticmethod
     def _tune_key(d: GemmDesc) -> str:
@@ -334,6 +334,31 @@ class Engine:
         if cap == 1 or (cap > 1 and d.splitk > cap):
             d.splitk = cap
 
+    @classmethod
+    def _race_candidates(cls, d: GemmDesc, key: str, table: dict, challengers: list) -> list:
+        """-> the plans ``_autotune`` races for this problem, in race order (``challengers``: the GN_RETUNE tiles).  Which tile carries what
+        comes from the library's tile table (_lib.gemm_tiles)."""
+        tiles = _lib.gemm_tiles()
+        fam = {t: c.family for t, c in tiles.items()}
+        geglu = [t for t, c in tiles.items() if c.geglu]
+        cands = geglu if d.act == ACT_GEGLU else list(tiles)
+        if key in table:
+            cands = [table[key]] + [c for c in challengers if c != table[key] % 100 and (d.act != ACT_GEGLU or c in geglu)]
+        if not cls._ppp_candidate(d):  # the persistent ping-pong tile needs whole 256 x 256 tiles, at least one per CU (the library would run
+            cands = [c for c in cands if fam.get(c % 100) != GEMM_PPP]  # the ping-pong tile instead: no second race of it)
+        if d.fp8:  # the fp8 kernel exists for the LDS-DMA block tiles 256x256 .. 256x64
+            cands = [t for t, c in tiles.items() if c.fp8 and (c.geglu or d.act != ACT_GEGLU)]
+        if d.ln_c1:  # the LayerNorm fold lives in the LDS-DMA kernels (the library maps the other tiles onto them)
+            cands = [c for c in cands if fam.get(c % 100) in (GEMM_DMA, GEMM_RING, GEMM_PPP)]
+        if d.k_append:  # so does the appended 1x1 segment
+            cands = [c for c in cands if fam.get(c % 100) in (GEMM_DMA, GEMM_PP, GEMM_RING, GEMM_PPP)]
+        if d.norm_in.stats:  # the normalising A path lives in the ring kernels, within the limits of gn_gemm_norm_in_tile_fits
+            rps = d.Ho * d.Wo if d.conv else d.norm_in.rows_per_sample
+            ct = (d.C1 if d.k_append else d.C1 + d.C2) if d.conv else (d.K - d.C2 if d.k_append else d.K)
+            cands = [t for t in tiles if fam[t] == GEMM_RING and _lib.load().gn_gemm_norm_in_tile_fits(t, rps, ct)
+                     and (not challengers or t in [table.get(key, 0) % 100] + challengers)]
+        return cands
+
     def _autotune(self, d: GemmDesc, key: Optional[str] = None) -> int:
         """-> the plan (``tile + 100 * splitk``) of this problem: from the table, or measured now and remembered."""
         key = key or self._tune_key(d)
@@ -343,27 +368,9 @@ class Engine:
         if key in table and not ((challengers or sk_chal) and key not in self._retuned):          # against each shape's incumbent
             return table[key]
         resplit = key in table and bool(sk_chal)
-        cands = (1, 2, 5, 6, 7, 8, 9, 12, 16, 19, 25) if d.act == ACT_GEGLU else range(1, self.N_TILE_CFGS + 1)
         if key in table:
             self._retuned.add(key)
-            cands = [table[key]] + [c for c in challengers if c != table[key] % 100 and (d.act != ACT_GEGLU or c in (1, 2, 5, 6, 7, 8, 9, 12, 16, 19, 25))]
-        if not self._ppp_candidate(d):  # tile 25 needs whole 256 x 256 tiles, at least one per CU (the library would run tile 15 instead: no second race of it)
-            cands = [c for c in cands if c % 100 != 25]
-        if d.fp8:  # the fp8 kernel exists for the six LDS-DMA block tiles 256x256 .. 256x64
-            cands = (7, 8, 9, 12) if d.act == ACT_GEGLU else range(7, 13)
-        if d.ln_c1:  # the LayerNorm fold lives in the LDS-DMA kernels (the library maps the other tiles onto them)
-            cands = [c for c in cands if c % 100 >= 7 and c % 100 != 15]
-        if d.k_append:  # so does the appended 1x1 segment
-            cands = [c for c in cands if c % 100 >= 7]
-        if d.norm_in.stats:  # the normalising A path lives in the ring kernels; a row tile spans at most four samples
-            rps = d.Ho * d.Wo if d.conv else d.norm_in.rows_per_sample
-            bmn = {16: (128, 128), 17: (128, 64), 18: (64, 64), 19: (256, 64), 20: (128, 160), 21: (64, 160), 22: (64, 320)}
-            ct = (d.C1 if d.k_append else d.C1 + d.C2) if d.conv else (d.K - d.C2 if d.k_append else d.K)
-
-            def fits(c):  # the ring + the scale / shift table of the samples a row tile touches inside the CU's 160 KB of LDS
-                bm, bn = bmn[c]
-                return bm <= 4 * rps and 3 * (bm + bn) * 128 + max(1, bm // rps) * ct * 8 <= 160 * 1024
-            cands = [c for c in bmn if fits(c) and (not challengers or c in [table.get(key, 0) % 100] + challengers)]
+        cands = self._race_candidates(d, key, table, challengers)
         e0, e1 = self.event(), self.event()
 
         def race(plan: int) -> float:

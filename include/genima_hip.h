@@ -207,6 +207,19 @@ int64_t gn_gemm_workspace_bytes(const gn_gemm_desc* d);
  * gn_program_set_gemm_plan asks here before it patches a recorded op. */
 int32_t gn_gemm_plan_valid(const gn_gemm_desc* d);
 #define GN_NUM_GEMM_TILES 25
+/* kernel families of the GEMM tiles: register-staged, two-stage LDS-DMA, ping-pong 256x256, three-stage LDS-DMA ring, persistent ping-pong */
+enum { GN_GEMM_REG = 0, GN_GEMM_DMA = 1, GN_GEMM_PP = 2, GN_GEMM_RING = 3, GN_GEMM_PPP = 4 };
+typedef struct gn_gemm_tile {
+  int32_t bm, bn;   /* block tile */
+  int32_t family;   /* GN_GEMM_* */
+  int32_t geglu;    /* carries GN_ACT_GEGLU */
+  int32_t fp8;      /* the fp8 kernel exists for this tile */
+} gn_gemm_tile;
+/* fills *out for tile 1 .. GN_NUM_GEMM_TILES (the gn_gemm_desc::tile values); GN_ERR_INVALID outside that range */
+int32_t gn_gemm_tile_info(int32_t tile, gn_gemm_tile* out);
+/* 1 when ring tile `tile` can carry norm_in for rows_per_sample output rows per sample and ct normalised channels: its rows span at most
+ * 4 samples, and the ring plus their scale / shift table fit the CU's LDS */
+int32_t gn_gemm_norm_in_tile_fits(int32_t tile, int64_t rows_per_sample, int64_t ct);
 /* tile 25's in-launch hand-offs wait with a bound; -> how many waits have given up on the current device since the library was loaded (0 in a
  * healthy process; tests assert it). */
 int64_t gn_ppp_timeouts(void);

@@ -29,10 +29,9 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402  (synthetic inputs, workloads)
 from genima_amd import configs, engine as engine_mod  # noqa: E402
-from genima_amd._lib import GemmDesc, check  # noqa: E402
+from genima_amd._lib import GEMM_PP, GEMM_PPP, GEMM_REG, GemmDesc, check, gemm_tiles  # noqa: E402
 from genima_amd.engine import ACT_GEGLU, OUT_ROWMAJOR, Engine  # noqa: E402
 
-GEGLU_TILES = (1, 2, 5, 6, 7, 8, 9, 12, 16, 19)
 
 
 def gemm_ops(E):
@@ -53,11 +52,15 @@ def gemm_ops(E):
 
 
 def valid_plans(d):
-    tiles = list(GEGLU_TILES) if d.act == ACT_GEGLU else list(range(1, Engine.N_TILE_CFGS + 1))
-    if d.ln_c1:
-        tiles = [t for t in tiles if t >= 7 and t not in (15, 24)]
+    fam = {t: c.family for t, c in gemm_tiles().items()}
+    if d.act == ACT_GEGLU:  # (the persistent ping-pong tile has not been raced in the call for GEGLU)
+        tiles = [t for t, c in gemm_tiles().items() if c.geglu and c.family != GEMM_PPP]
+    else:
+        tiles = list(fam)
+    if d.ln_c1:  # the LDS-DMA kernels carry the LayerNorm fold; tile 24 stays out of this race as it always has
+        tiles = [t for t in tiles if fam[t] not in (GEMM_REG, GEMM_PP) and t != 24]
     if d.k_append:  # the appended 1x1 segment lives in the LDS-DMA loaders
-        tiles = [t for t in tiles if t >= 7]
+        tiles = [t for t in tiles if fam[t] != GEMM_REG]
     return tiles
 
 
