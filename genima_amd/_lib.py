@@ -167,6 +167,9 @@ SIGNATURES = {
     "gn_conv3x3_gn_supported": (_I32, [_I32, _I32, _I32, _I32, _I32]),
     "gn_conv3x3_gn": (_I32, [_P, C.POINTER(ConvGnDesc)]),
     "gn_program_add_conv3x3_gn": (_I32, [_P, C.POINTER(ConvGnDesc)]),
+    "gn_tiny_block_supported": (_I32, [_I32, _I32, _I32]),
+    "gn_tiny_block": (_I32, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
+    "gn_program_add_tiny_block": (_I32, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
     "gn_attention_bwd": (_I32, [_P, C.POINTER(AttnBwdDesc)]),
     "gn_attention_fp8_quantize": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _F, _P, _P, _P, _I32]),
     "gn_attention_fp8_fwd": (_I32, [_P, C.POINTER(AttnDesc)]),

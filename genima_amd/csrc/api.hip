@@ -20,7 +20,7 @@ namespace {
 enum OpType {
   OP_GEMM = 0, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_TEMB, OP_SCALE_PAD, OP_EULER, OP_F16_TO_U8, OP_U8_TO_F16, OP_ADD,
   OP_ACT, OP_EMBED, OP_SOFTMAX, OP_MAXPOOL, OP_NORMALIZE_U8, OP_GATHER_ROWS, OP_COPY4D, OP_ARGMAX, OP_ADD_NOISE, OP_FILM, OP_SCALE_CAT_PAD,
-  OP_TBLOCK, OP_CONV_GN, OP_ADD_MULTI, OP_MEMSET,
+  OP_TBLOCK, OP_CONV_GN, OP_ADD_MULTI, OP_MEMSET, OP_TINY_BLOCK,
   OP_FORK, OP_MAIN, OP_JOIN  // stream control: ops after FORK go to the program's side stream until MAIN; JOIN makes main wait for it
 };
 
@@ -29,7 +29,7 @@ struct GenericArgs {  // argument block of the small ops
   int64_t n0, n1;
   int32_t i0, i1, i2, i3;
   float f0, f1;
-  int64_t m[12];  // copy4d: sizes[4], in_strides[4], out_strides[4]
+  int64_t m[12];  // copy4d: sizes[4], in_strides[4], out_strides[4]; tiny block: w[3], bias[3]
   float g[6];     // normalize: mul[3], add[3]
 };
 
@@ -91,6 +91,11 @@ static int32_t run_op(gn_ctx* ctx, const Op& op) {
     case OP_GATHER_ROWS: return gn_gather_rows(ctx, g.p0, (const int32_t*)g.p1, g.p3, g.i0, g.i1, g.i2);
     case OP_COPY4D: return gn_copy4d(ctx, g.p0, g.p3, g.m, g.m + 4, g.m + 8, g.i0);
     case OP_ARGMAX: return gn_argmax_rows_i32(ctx, (const int32_t*)g.p0, (int32_t*)g.p3, g.i0, g.i1);
+    case OP_TINY_BLOCK: {
+      const void* w[3] = {(const void*)(uintptr_t)g.m[0], (const void*)(uintptr_t)g.m[1], (const void*)(uintptr_t)g.m[2]};
+      const void* bias[3] = {(const void*)(uintptr_t)g.m[3], (const void*)(uintptr_t)g.m[4], (const void*)(uintptr_t)g.m[5]};
+      return gn_tiny_block(ctx, g.p0, w, bias, g.p3, g.i0, g.i1, g.i2, g.i3);
+    }
     case OP_ADD_NOISE: return gn_add_noise(ctx, g.p0, g.p1, (const float*)g.p2, (const float*)(uintptr_t)g.m[0], g.p3, g.i0, g.n0);
     default: gn_set_error("gn_program: unknown op type %d", op.type); return GN_ERR_INVALID;
   }
@@ -218,6 +223,19 @@ int32_t gn_program_add_groupnorm(gn_program* p, const gn_groupnorm_desc* d) {
   op.gnorm = *d;
   p->ops.push_back(op);
   return GN_OK;
+}
+int32_t gn_program_add_tiny_block(gn_program* p, const void* x, const void* const w[3], const void* const bias[3], void* out, int32_t B,
+                                 int32_t H, int32_t W, int32_t C) {
+  GN_REQUIRE(w && bias, "gn_program_add_tiny_block: null weight / bias array");
+  GN_REQUIRE(x && out && B > 0 && gn_tiny_block_supported(C, H, W), "gn_program_add_tiny_block: null x / out or unsupported shape (B %d, %dx%d, C %d)", B, H,
+             W, C);
+  const int32_t rc = push_generic(p, OP_TINY_BLOCK, x, nullptr, nullptr, out, 0, 0, B, H, W, C, 0.f, 0.f);
+  if (rc == GN_OK)
+    for (int k = 0; k < 3; ++k) {
+      p->ops.back().g.m[k] = (int64_t)(uintptr_t)w[k];
+      p->ops.back().g.m[3 + k] = (int64_t)(uintptr_t)bias[k];
+    }
+  return rc;
 }
 int32_t gn_program_add_layernorm(gn_program* p, const void* x, const void* gamma, const void* beta, void* y, int64_t M, int32_t C, float eps) {
   return push_generic(p, OP_LAYERNORM, x, gamma, beta, y, M, 0, C, 0, 0, 0, eps, 0.f);

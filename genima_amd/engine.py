@@ -113,6 +113,9 @@ class Engine:
         # tail 147 vs 201 us at 32768 rows, 121 vs 113 at 16384, 114 vs 64 at 8192)
         self.tblock_min_rows = int(os.environ.get("GN_TBLOCK_MIN_ROWS", "24576"))
         self.tblock_front_on = os.environ.get("GN_TBLOCK_FRONT", "1") != "0"  # the GroupNorm + proj_in + q | k | v chain (A/B switch of its own)
+        # graphs: TAESD encoder blocks as one fused launch (csrc/taesd.hip) instead of three conv launches.  Opt-in: the fused kernel is
+        # LDS-bound and loses at every size measured (tools/bench_taesd.py on MI355X, B = 8: 512^2 1349 vs 1033 us, 256^2 327 vs 247 us)
+        self.tiny_block_on = os.environ.get("GN_TINY_BLOCK", "0") == "1"
         self.ln_fold = os.environ.get("GN_LN_FOLD", "1") != "0"  # graphs: LayerNorm folded into the consuming Linear (A/B switch)
         # graphs: self-attention takes V row-major out of one plain q | k | v launch (gn_attn_desc.v_rowmajor) instead of the two-destination
         # launch + V^T.  Measured neutral in the call (107.59 vs 107.67 ms tiled b8, same box) although the kernel alone is 4-7 % faster at
@@ -1061,6 +1064,33 @@ class Engine:
             self.meta.append(dict(kind="conv3x3", flops=2.0 * M * N * K, bytes=2.0 * (M * Cin + N * K + M * N), shape=(M, N, K), ref_flops=2.0 * M * N * K))
         else:
             check(self.lib.gn_conv3x3_gn(self._ctx, C.byref(d)), "gn_conv3x3_gn")
+        return out
+
+    def tiny_block_supported(self, x: torch.Tensor) -> bool:
+        _, H, W, Cc = x.shape
+        return bool(self.lib.gn_tiny_block_supported(Cc, H, W))
+
+    def tiny_block(self, x: torch.Tensor, ws, biases, *, out: Optional[torch.Tensor] = None, name: Optional[str] = None) -> torch.Tensor:
+        """diffusers AutoencoderTinyBlock at 64 channels as one launch (gn_tiny_block, csrc/taesd.hip):
+        relu(conv3(relu(conv2(relu(conv1(x))))) + x).  x: NHWC [B, H, W, 64]; ws: three packed [64, 9 * 64] weights; biases: three [64]."""
+        B, H, W, Cc = x.shape
+        assert len(ws) == 3 and len(biases) == 3 and all(tuple(w.shape) == (Cc, 9 * Cc) for w in ws), [tuple(w.shape) for w in ws]
+        assert x.is_contiguous()
+        if out is None:
+            out = self.buf(name, (B, H, W, Cc))
+        else:
+            self._wrote(out)
+        wp = (C.c_void_p * 3)(*[_ptr(w) for w in ws])
+        bp = (C.c_void_p * 3)(*[_ptr(b) for b in biases])
+        args = (_ptr(x), wp, bp, _ptr(out), B, H, W, Cc)
+        if self.record:
+            check(self.lib.gn_program_add_tiny_block(self._prog, *args), "gn_program_add_tiny_block")
+            self._keepalive(x, out, *ws, *biases)
+            M, K = B * H * W, 9 * Cc
+            self.meta.append(dict(kind="tiny_block", flops=3 * 2.0 * M * Cc * K, bytes=2.0 * (2 * M * Cc + 3 * Cc * K), shape=(M, Cc, K),
+                                  ref_flops=3 * 2.0 * M * Cc * K))
+        else:
+            check(self.lib.gn_tiny_block(self._ctx, *args), "gn_tiny_block")
         return out
 
     def layernorm(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, *,

@@ -472,6 +472,48 @@ def _emit_tiny_block(E: Engine, W, p: str, x):
         return E.conv2d(h, W[p + ".conv.4.weight"], W[p + ".conv.4.bias"], residual=sk, act=ACT_RELU, residual_before_act=True, name="c4")
 
 
+def _taesd_in_affine(E: Engine, W) -> torch.Tensor:
+    """FiLM rows of EncoderTiny's input affine x.add(1).div(2): (1 + gamma, beta) = (0.5, 0.5) on the 3 image channels, (0, 0) on the
+    padding channels 3..7 (they stay 0, not 0.5).  [1, 16] f16 = gamma[8] | beta[8]; packed by host.AutoencoderTiny, made here otherwise."""
+    t = W.get("encoder.in_affine")
+    if t is None:
+        t = torch.tensor([[-0.5] * 3 + [-1.0] * 5 + [0.5] * 3 + [0.0] * 5], dtype=torch.float16).to(E.device)
+        W["encoder.in_affine"] = t
+    return t
+
+
+def emit_taesd_encode(E: Engine, W, cfg, x8: torch.Tensor) -> torch.Tensor:
+    """diffusers ``EncoderTiny.forward``: ``layers(x.add(1).div(2))`` -- conv_in 3 -> 64 (no activation), then per stage a bias-free
+    stride-2 conv (stages 2..) and ``num_encoder_blocks`` AutoencoderTinyBlocks, then conv 64 -> 4.  x8: image in [-1, 1], [B, H, W, 8]
+    (channels >= 3 zero) -> latents [B, H/8, W/8, 8] (channels 4..7 zero: the lat8 convention of train_ops.latent_sample).
+    The affine is its own pass, as f16(x + 1) / 2, and NOT folded into conv_in: conv_in zero-pads in [0, 1] space.
+    Blocks run as the three conv launches of _emit_tiny_block, or with GN_TINY_BLOCK=1 as one fused launch each (Engine.tiny_block,
+    where gn_tiny_block_supported allows; slower today: DESIGN.md)."""
+    nb = cfg["num_encoder_blocks"]
+    with E.scope("taesd_enc"):
+        aff = _taesd_in_affine(E, W)
+        B, H, Wd, _ = x8.shape
+        h = E.film(x8, aff[:, :8], aff[:, 8:], B * H * Wd, name="in")
+        idx = 0
+        for i, n in enumerate(nb):
+            p = f"encoder.layers.{idx}"
+            if i == 0:
+                h = E.conv2d(h, W[p + ".weight"], W[p + ".bias"], name="conv_in")
+            else:
+                h = E.conv2d(h, W[p + ".weight"], None, stride=2, name=f"down{i}")
+            idx += 1
+            for _ in range(n):
+                p = f"encoder.layers.{idx}"
+                if getattr(E, "tiny_block_on", True) and (p + ".skip.weight") not in W and E.tiny_block_supported(h):
+                    ks = (0, 2, 4)
+                    h = E.tiny_block(h, [W[f"{p}.conv.{k}.weight"] for k in ks], [W[f"{p}.conv.{k}.bias"] for k in ks], name=p)
+                else:
+                    h = _emit_tiny_block(E, W, p, h)
+                idx += 1
+        p = f"encoder.layers.{idx}"
+        return E.conv2d(h, W[p + ".weight"], W[p + ".bias"], name="conv_out")
+
+
 def emit_taesd_decode(E: Engine, W, cfg, z8: torch.Tensor) -> torch.Tensor:
     """diffusers ``DecoderTiny.forward``: x = 3 tanh(x / 3); conv + relu; per stage {blocks, nearest-2x + bias-free conv}; last stage
     {block, conv to RGB}; x * 2 - 1 (the affine is folded into the last conv: out_scale 2 and the pre-shifted bias

@@ -293,9 +293,10 @@ class AutoencoderKL(HipModule):
 
 
 class AutoencoderTiny(HipModule):
-    """diffusers ``AutoencoderTiny`` (TAESD): the fast decoder the agents swap in when ``autoencoder`` names a taesd checkpoint
-    (controller/agent/sd_controlnet_agent.py:45-49, sdxl_controlnet_agent.py:44-49).  Decode only: the trainer encodes with the
-    AutoencoderKL."""
+    """diffusers ``AutoencoderTiny`` (TAESD / TAESDXL): the fast decoder the agents swap in when ``autoencoder`` names a taesd checkpoint
+    (controller/agent/sd_controlnet_agent.py:45-49, sdxl_controlnet_agent.py:44-49), and the frozen VAE of the ControlNet trainers'
+    ``--tiny_vae`` (diffusion/train_controlnet_genima.py:1049-1050, 1324-1327): ``encode(x).latents`` -- no scaling factor, no posterior
+    sample (graphs.emit_taesd_encode)."""
     schema_fn = staticmethod(schema.taesd_schema)
 
     def _pack(self):
@@ -303,6 +304,8 @@ class AutoencoderTiny(HipModule):
         last = max(int(k.split(".")[2]) for k in self._sd if k.startswith("decoder.layers.") and k.endswith(".bias"))
         b = self._sd[f"decoder.layers.{last}.bias"]
         self.W["decoder.out_bias_shifted"] = packing.pack_vec(b - 0.5, self.W[f"decoder.layers.{last}.weight"].shape[0]).to(self.device)
+        # EncoderTiny's input affine x.add(1).div(2) as FiLM rows (graphs._taesd_in_affine)
+        self.W["encoder.in_affine"] = torch.tensor([[-0.5] * 3 + [-1.0] * 5 + [0.5] * 3 + [0.0] * 5], dtype=torch.float16).to(self.device)
 
     def decode(self, z, return_dict=True, **kw):
         E = self.engine()
@@ -312,8 +315,12 @@ class AutoencoderTiny(HipModule):
         return SimpleNamespace(sample=out) if return_dict else (out,)
 
     def encode(self, x, return_dict=True):
-        raise NotImplementedError("AutoencoderTiny.encode is not on the Genima hot path (the trainer encodes with AutoencoderKL, "
-                                  "diffusion/train_controlnet_genima.py:1329-1332)")
+        """x: NCHW image in [-1, 1] -> ``latents`` NCHW f16 [B, 4, H/8, W/8] (diffusers ``AutoencoderTinyOutput``)."""
+        E = self.engine()
+        x8 = nchw_to_nhwc(x.to(self.device, torch.float16), 8)
+        lat = graphs.emit_taesd_encode(E, self.W, self.config, x8)
+        out = nhwc_to_nchw(lat, self.config["latent_channels"])
+        return SimpleNamespace(latents=out) if return_dict else (out,)
 
 
 class CLIPTextModel(HipModule):

@@ -1065,10 +1065,13 @@ class ControlNetTrainer:
 
     # ---- the whole step body from a collated batch (VAE encode + text encode + noise sampling in front of step())
     def attach_frozen(self, vae_cfg, vae_W, text_cfg, text_W, noise_scheduler, seed: int = 0, text2_cfg=None, text2_W=None,
-                      augmentations: Optional[str] = None):
+                      augmentations: Optional[str] = None, tiny_vae: bool = False):
         """Frozen fp16 VAE / CLIP text tower(s) (packed weights) and the DDPMScheduler (diffusion/train_controlnet_genima.py:1038-1060;
-        SDXL: the second, projection tower of train_controlnet_sdxl_genima.py:1027-1071 as ``text2_*``)."""
+        SDXL: the second, projection tower of train_controlnet_sdxl_genima.py:1027-1071 as ``text2_*``).  ``tiny_vae`` (the reference's
+        --tiny_vae, :469-473, 1049-1050, 1324-1327; SDXL :504-508, 1077-1078, 1408-1411): the VAE is an AutoencoderTiny (taesd / taesdxl
+        config and packed weights) and the latents are ``vae.encode(pixel_values).latents`` -- no scaling factor, no posterior draw."""
         self.vae_cfg, self.vae_W, self.text_cfg, self.text_W, self.noise_scheduler = vae_cfg, vae_W, text_cfg, text_W, noise_scheduler
+        self.tiny_vae = bool(tiny_vae)
         self.text2_cfg, self.text2_W = text2_cfg, text2_W
         pt = noise_scheduler.config.get("prediction_type", "epsilon")
         if pt not in ("epsilon", "v_prediction"):  # the reference's own refusal (diffusion/train_controlnet_genima.py:1396-1399)
@@ -1164,10 +1167,14 @@ class ControlNetTrainer:
         ids = batch["input_ids"].to(dev, torch.int32).contiguous()
         B = x8.shape[0]
         Cl = self.vae_cfg["latent_channels"]
-        mom = graphs.emit_vae_encode_moments(E, self.vae_W, self.vae_cfg, x8)
-        shape = tuple(mom.shape[:-1]) + (Cl,)
-        lat8 = T.latent_sample(E, mom, torch.randn(shape, generator=self._gen_dev, device=dev, dtype=F32).to(F16), Cl,
-                               self.vae_cfg.get("scaling_factor", 0.18215))
+        if getattr(self, "tiny_vae", False):  # the noise is then the device generator's first draw of the step, as in the reference
+            lat8 = graphs.emit_taesd_encode(E, self.vae_W, self.vae_cfg, x8)
+            shape = tuple(lat8.shape[:-1]) + (Cl,)
+        else:
+            mom = graphs.emit_vae_encode_moments(E, self.vae_W, self.vae_cfg, x8)
+            shape = tuple(mom.shape[:-1]) + (Cl,)
+            lat8 = T.latent_sample(E, mom, torch.randn(shape, generator=self._gen_dev, device=dev, dtype=F32).to(F16), Cl,
+                                   self.vae_cfg.get("scaling_factor", 0.18215))
         noise8 = E.scale_pad(torch.randn(shape, generator=self._gen_dev, device=dev, dtype=F32).to(F16), 1.0, 8)
         t = torch.randint(0, int(self.noise_scheduler.config.num_train_timesteps), (B,), generator=self._gen_cpu)
         sa, s1 = self.noise_scheduler.add_noise_coeffs(t)

@@ -390,6 +390,15 @@ typedef struct gn_conv3x3_gn_desc {
 int32_t gn_conv3x3_gn_supported(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
 int32_t gn_conv3x3_gn(gn_ctx* ctx, const gn_conv3x3_gn_desc* d);
 
+/* ---- diffusers AutoencoderTinyBlock at 64 channels as one launch (csrc/taesd.hip) ----------------------------------------------------
+ * out = relu(conv3(relu(conv2(relu(conv1(x))))) + x): 3x3 convs, stride 1, padding 1, NHWC f16 [B, H, W, 64] -- every block of the
+ * TAESD / TAESDXL encoder.  w[k]: packed conv weight [64][9 * 64] f16 (gn_pack_conv_weight), bias[k]: [64] f16.  The two intermediate
+ * maps stay in LDS, rounded to f16 and ReLU'd as the three-launch route stores them; out must not overlap x.
+ * gn_tiny_block_supported: C == 64, any H, W > 0. */
+int32_t gn_tiny_block_supported(int32_t C, int32_t H, int32_t W);
+int32_t gn_tiny_block(gn_ctx* ctx, const void* x, const void* const w[3], const void* const bias[3], void* out, int32_t B, int32_t H,
+                      int32_t W, int32_t C);
+
 /* ---- K7: LayerNorm over the last dim of [M, C] (C % 8 == 0, C <= 4096) --------------------------------------------- */
 int32_t gn_layernorm_fwd(gn_ctx* ctx, const void* x, const void* gamma, const void* beta, void* y,
                          int64_t M, int32_t C, float eps);
@@ -587,6 +596,8 @@ int32_t gn_program_add_attention(gn_program* p, const gn_attn_desc* d);
 int32_t gn_program_add_tblock(gn_program* p, const gn_tblock_desc* d);
 int32_t gn_program_add_conv3x3_gn(gn_program* p, const gn_conv3x3_gn_desc* d);
 int32_t gn_program_add_groupnorm(gn_program* p, const gn_groupnorm_desc* d);
+int32_t gn_program_add_tiny_block(gn_program* p, const void* x, const void* const w[3], const void* const bias[3], void* out, int32_t B,
+                                 int32_t H, int32_t W, int32_t C);
 int32_t gn_program_add_layernorm(gn_program* p, const void* x, const void* gamma, const void* beta, void* y, int64_t M,
                                  int32_t C, float eps);
 int32_t gn_program_add_timestep_embedding(gn_program* p, const float* t, void* out, int32_t B, int32_t dim,
