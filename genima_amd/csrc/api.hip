@@ -126,7 +126,7 @@ int32_t gn_ctx_create(int32_t device, void* stream, gn_ctx** out) {
   GN_HIP(hipGetDeviceCount(&n));
   GN_REQUIRE(device >= 0 && device < n, "gn_ctx_create: device %d out of range (%d visible)", device, n);
   GN_HIP(hipSetDevice(device));
-  if (gn_ppp_pool_init(device) != GN_OK) return GN_ERR_HIP;  // the persistent GEMM's hand-off flags (2 MB, zeroed once; never allocated inside a capture)
+  if (gn_ppp_pool_init(device) != GN_OK) return GN_ERR_HIP;  // the persistent GEMM's hand-off flags (1 MB, zeroed once; never allocated inside a capture)
   gn_ctx* c = new gn_ctx();
   c->device = device;
   c->stream = (hipStream_t)stream;

@@ -826,7 +826,13 @@ int ppp_workgroups() {
   return ncu[dev];
 }
 int64_t ppp_tiles(const gn_gemm_desc* d) { return cdiv64(d->M, 256) * cdiv64(d->N, 256) * (d->up_phases ? 4 : 1); }
-// the persistent skewed ping-pong kernel's restrictions on top of pp_eligible (gemm_ppp.hip header)
+// tile 25's plan from the descriptor fields it depends on (K, ln_c1, up_phases, the tile count) -> hand-off slabs of 256 x 256 floats; the
+// workspace query and the launch both plan through here, so they agree on the slab count
+int ppp_plan(const gn_gemm_desc* d, GemmParams& p) {
+  p.K = (int)d->K; p.ln_c1 = d->ln_c1; p.up_ph = d->up_phases ? 1 : 0;
+  return gn_ppp_plan(&p, (int)ppp_tiles(d), ppp_workgroups());
+}
+// the persistent ping-pong kernel's restrictions on top of pp_eligible (gemm_ppp.hip header)
 bool ppp_eligible(const gn_gemm_desc* d) {
   const bool ff = d->act == GN_ACT_GEGLU || d->ln_c1 != nullptr;
   if (ff) {  // the feed-forward variant: LayerNorm fold AND GEGLU together (diffusers FeedForward.net[0] behind BasicTransformerBlock.norm3), dense, c2 in bias
@@ -1045,8 +1051,7 @@ extern "C" int64_t gn_gemm_workspace_bytes(const gn_gemm_desc* d) {
   Plan pl = plan_gemm(d);
   if (kCfg[pl.cfg].family == GN_GEMM_PPP) {  // hand-off slabs of the tiles whose K range several workgroups share (gemm_ppp.hip)
     GemmParams p = {};
-    p.K = (int)d->K;
-    return (int64_t)gn_ppp_plan(&p, (int)ppp_tiles(d), ppp_workgroups()) * 256 * 256 * (int64_t)sizeof(float);
+    return (int64_t)ppp_plan(d, p) * 256 * 256 * (int64_t)sizeof(float);
   }
   if (pl.splitk <= 1) return 0;
   return (int64_t)pl.splitk * d->M * d->N * (int64_t)sizeof(float);
@@ -1211,8 +1216,8 @@ int32_t gn_launch_gemm(gn_ctx* ctx, const gn_gemm_desc* d) {
   switch (kCfg[pl.cfg].family) {
     case GN_GEMM_PP: gn_launch_gemm_pp(&p, conv, p.tiles_m * p.tiles_n, p.splitk, p.nbatch > 0 ? p.nbatch : 1, ctx->stream); break;
     case GN_GEMM_PPP: {
-      GN_REQUIRE(d->workspace, "gn_gemm: tile 25 (persistent ping-pong) needs a workspace of gn_gemm_workspace_bytes()");
-      (void)gn_ppp_plan(&p, (int)ppp_tiles(d), ppp_workgroups());
+      const int slabs = ppp_plan(d, p);
+      GN_REQUIRE(slabs == 0 || d->workspace, "gn_gemm: tile 25 (persistent ping-pong) splits K here and needs a workspace of gn_gemm_workspace_bytes()");
       GN_REQUIRE(gn_ppp_pool_init(ctx->device) == GN_OK, "gn_gemm: tile 25 could not allocate its flag pool (first use inside a stream capture?): %s", gn_last_error());
       gn_launch_gemm_ppp(&p, conv, ctx->stream);
       break;

@@ -50,13 +50,13 @@ struct GemmParams {
   struct NormOutP { f16* y; const f16* gamma; const f16* beta; float eps; int groups, act, rps; } nout;  // GroupNorm inside the split-K reduce (gemm.hip)
   GnSinkP sink;                          // GroupNorm bridge, producer side (gn_bridge.h): stats == nullptr = off
   GnInP gin;                             // GroupNorm bridge, consumer side (gemm_s3.hip's normalising A path): stats == nullptr = off
-  // persistent skewed ping-pong kernel (gemm_ppp.hip, tile 25): the grid is ppG workgroups (one per CU) that walk the tile list; `ws` holds the f32
+  // persistent ping-pong kernel (gemm_ppp.hip, tile 25): the grid is ppG workgroups (one per CU) that walk the tile list; `ws` holds the f32
   // hand-off slabs of the tiles whose K range two (or more) workgroups share, ppflags their ready words (zero between launches: the consumer resets them)
   struct FastDiv { unsigned mul, shift; };  // n / d for 32-bit n as (umulhi(n, mul) + n) >> shift (Granlund - Montgomery; gn_ppp_plan fills them)
-  FastDiv dG, dS, dTm, dTn, dTmn, dHw, dWo, dCin, dKW, dOrw;
+  FastDiv dS, dTm, dTn, dTmn, dHw, dWo, dCin, dKW, dOrw;
   unsigned* ppflags;
   unsigned* pptmo;                       // counts bounded hand-off waits that gave up (gn_ppp_timeouts)
-  int ppG, ppR, ppTail, ppS, ppNz, ppSkew;  // workgroups, full rounds, tiles of the last partial round, workgroups per such tile, blockIdx.z extent folded in, skew on
+  int ppG, ppR, ppTail, ppS, ppNz;       // workgroups, full rounds, tiles of the last partial round, workgroups per such tile, blockIdx.z extent folded in
 };
 
 // GroupNorm bridge, producer side (gn_bridge.h).  Where the workgroup's LDS can hold its f16 output tile, the epilogue's 16-byte row stores
@@ -757,8 +757,8 @@ constexpr GemmCfg kCfg[] = {
     // 2-stage 128x320 on EIGHT waves of 32x160 (round 5): the wave tile of the 128x160 tile with all of N = 320 in one workgroup -- the A
     // tile is staged once for both column halves (10.9 instead of 14 LDS-DMA bytes per kFLOP), one workgroup per CU
     /* 23 */ {128, 320, 4, 2, 0.0, false, GN_GEMM_DMA, false, 8, 19, 1},
-    // persistent skewed ping-pong 256x256 (gemm_ppp.hip, round 6): one workgroup per CU walks the tile list; the next tile's ring is
-    // requested before the finished tile's epilogue, tile boundaries are skewed over the chip, the last partial round is split along K
+    // persistent ping-pong 256x256 (gemm_ppp.hip, round 6): one workgroup per CU walks the tile list; the next tile's ring is
+    // requested before the finished tile's epilogue, the last partial round is split along K
     /* 24 */ {256, 256, 0, 0, 0.0, true, GN_GEMM_PPP, false, 6, 15, 0},
 };
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
@@ -796,7 +796,7 @@ void with_cfg(int cfg, F&& f) {
 
 // the ping-pong 256x256 kernel lives in its own translation unit (gemm_pp.hip); `params` is a GemmParams
 void gn_launch_gemm_pp(const void* params, bool conv, int grid_x, int grid_y, int grid_z, hipStream_t st);
-// the persistent skewed ping-pong kernel (gemm_ppp.hip); the plan fields pp* of `params` are filled by gn_ppp_plan
+// the persistent ping-pong kernel (gemm_ppp.hip); the plan fields pp* of `params` are filled by gn_ppp_plan
 void gn_launch_gemm_ppp(const void* params, bool conv, hipStream_t st);
 int gn_ppp_plan(void* params, int tiles, int G);  // fills the pp* plan fields -> hand-off slabs (of 256 KB) the launch may use
 // the 3-stage ring variants (gemm_s3.hip); cfg = a kCfg row of family GN_GEMM_RING

@@ -1,5 +1,5 @@
-// Persistent, SKEWED ping-pong implicit GEMM for gfx950 (tile 25): the 256 x 256 x 64 ping-pong K loop of gemm_pp.hip inside a workgroup that
-// stays on its CU and walks a list of tiles, so that a tile's fill and drain stop being a chip-wide event.
+// Persistent ping-pong implicit GEMM for gfx950 (tile 25): the 256 x 256 x 64 ping-pong K loop of gemm_pp.hip inside a workgroup that stays on its
+// CU and walks a list of tiles, so that a tile's fill and drain stop being a chip-wide event.
 //
 // What the one-launch-round form costs (profiles/r05_v15_pp_ksweep.txt, r05_v16_pp_epilogue_ablation.txt): a round of 256 one-per-CU tiles spends
 // 14.3 us beside its K loop -- ~2 us until the first K tile has landed, ~11 us in an epilogue in which all 256 workgroups store 33.5 MB at the same
@@ -9,19 +9,15 @@
 //     and the ring fill share one memory round trip.  Then `s_waitcnt vmcnt(0)`, then ALL of the tile's stores back to back, then the next K loop
 //     starts at once: its first K iteration reads only what the prologue brought and carries no wait at all, so the stores have a whole K
 //     iteration (~1.8 us) to be acknowledged before the first counted wait that (gfx9's vmcnt retires in order) would have to sit them out.
-//   * SKEW: workgroup c enters its first tile at K iteration k_c = c * nk / G and hands the partial sums to workgroup c - 1, which computes the K
-//     prefix [0, k_c) of that tile as the LAST thing it does and writes the tile.  Every workgroup does the same amount of work, their tile
-//     boundaries are spread evenly over a tile period, and the chip never drains in one write burst (the stagger experiment of round 5 with the
-//     offset made of useful work).  Hand-off = f32 slab (256 KB, register order: fully coalesced 16-byte write-through `sc1` stores), drained
-//     vmcnt, one agent-scope flag; the consumer polls that one word, one agent acquire, plain loads (cdna_hip_programming.md Guideline 16, R1).
-//     The producer publishes at the very start of the launch, the consumer needs it at the very end: nobody waits in practice.
-//   * TAIL: the tiles of the last, partial round are split along K over floor(G / tail tiles) workgroups each through the same hand-off (the part
-//     that holds k = 0 owns the tile and adds the others' slabs in a fixed order): 640 tiles cost 2.5 tile times instead of 3, 320 tiles 1.25 of 2.
+//   * TAIL: the tiles of the last, partial round are split along K over floor(G / tail tiles) workgroups each (the part that holds k = 0 owns the
+//     tile and adds the others' slabs in a fixed order): 640 tiles cost 2.5 tile times instead of 3, 320 tiles 1.25 of 2.  Hand-off = f32 slab
+//     (256 KB, register order: fully coalesced 16-byte write-through `sc1` stores), drained vmcnt, one agent-scope flag; the owner polls that one
+//     word, one agent acquire, plain loads (cdna_hip_programming.md Guideline 16, R1).
 //   Flags are self-cleaning (their one consumer resets them) inside a library-owned, zero-initialised pool: no memset node per launch.
-//   Deadlock freedom without co-residency: a workgroup only ever waits for a segment that is the FIRST thing its producer does (skew) or that the
-//   producer reaches without waiting on anything later-dispatched than itself (tail); waits are bounded and counted (gn_ppp_timeouts).
+//   Deadlock freedom without co-residency: a workgroup only ever waits for a tail part that its producer reaches without waiting on anything
+//   later-dispatched than itself; waits are bounded and counted (gn_ppp_timeouts).
 // Results: a tile whose K range is not shared is bit-identical to every other tile configuration (K walked alike); a shared tile adds its f32 partial
-// sums in a fixed order (prefix + suffix; part 0 + part 1 + ...): deterministic run to run, a K split's rounding against the unsplit sum.
+// sums in a fixed order (part 0 + part 1 + ...): deterministic run to run, a K split's rounding against the unsplit sum.
 // Restrictions on top of gemm_pp.hip's (the planner falls back to tile 15): row-major f16 output through 16-byte stores (N, ldo % 8 == 0), bias /
 // shift OR residual / activation / scale epilogues, >= one tile per CU; no split-K, out2, LayerNorm fold, GEGLU, GroupNorm bridge.
 #include <atomic>
@@ -35,7 +31,7 @@ constexpr int PP_HALF = 16384;   // one half-tile (128 rows)
 constexpr int PPP_SLAB = 256 * 256;  // floats of one hand-off slab
 
 constexpr int PPP_POOL_HEAD = 64;      // words in front of the regions; word 0 counts bounded waits that gave up
-constexpr int PPP_REGION = 512;        // flag words of one launch: [0, 256) the skew hand-offs, [256, 512) the tail's
+constexpr int PPP_REGION = 256;        // flag words of one launch: one per tail slot (fewer than G <= 256)
 constexpr int PPP_REGIONS = 1024;
 constexpr int PPP_PROF_WORDS = 256 * 8;  // behind the regions: per-workgroup cycle sums of a profiling build (-DGN_PPP_PROFILE, tools/probes/ppp_profile.py)
 
@@ -103,37 +99,28 @@ __global__ __launch_bounds__(512) void gemm_ppp_kernel(const GemmParams p) {
     KArgs* q = ppp_kargs();
     int c = blockIdx.x;
     asm volatile("" : "+s"(c));
-    const int G = q->ppG, nk = q->K / BK;
-    const int kc1 = (q->ppSkew && c + 1 < G) ? PPP_DIV((c + 1) * nk, dG) : 0;
-    return q->ppR + (kc1 > 0 ? 1 : 0) + ((q->ppTail > 0 && c < q->ppTail * q->ppS) ? 1 : 0);
+    return q->ppR + ((q->ppTail > 0 && c < q->ppTail * q->ppS) ? 1 : 0);
   };
   auto get_seg = [&](int i) __attribute__((always_inline)) {
     KArgs* q = ppp_kargs();
     int c = blockIdx.x;
     asm volatile("" : "+s"(c));  // (opaque: the values derived from it are not hoisted out of the segment loop)
-    const int G = q->ppG, nk = q->K / BK, R = q->ppR, S = q->ppS, skew = q->ppSkew;
+    const int G = q->ppG, nk = q->K / BK, R = q->ppR, S = q->ppS;
     auto vid = [&](int b) __attribute__((always_inline)) {  // XCD-aware position of hardware workgroup b inside a round: an XCD's workgroups take a contiguous run of tiles
       const int qq = G >> 3, r = G & 7, xcd = b & 7, idx = b >> 3;
       return (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + idx;
     };
-    const int kc0 = skew ? PPP_DIV(c * nk, dG) : 0;  // (c * nk < 2^31: the planner keeps nk < 2^20)
-    const int kc1 = (skew && c + 1 < G) ? PPP_DIV((c + 1) * nk, dG) : 0;
     Seg s;
     s.slot = 0; s.nslot = 0;
-    if (i == 0) {  // round 0: the K suffix from this workgroup's skew offset
-      s.tile = vid(c); s.k0 = kc0; s.k1 = nk;
-      s.role = kc0 == 0 ? ROLE_FULL : ROLE_PRODUCER; s.slot = c;
-    } else if (i < R) {
+    if (i < R) {  // a full round
       s.tile = i * G + vid(c); s.k0 = 0; s.k1 = nk; s.role = ROLE_FULL;
-    } else if (i == R && kc1 > 0) {  // the K prefix of the next workgroup's round-0 tile: this workgroup writes that tile
-      s.tile = vid(c + 1); s.k0 = 0; s.k1 = kc1; s.role = ROLE_OWNER; s.slot = c + 1; s.nslot = 1;
     } else {  // a tile of the last partial round, split along K over ppS workgroups
       const int j = PPP_DIV(c, dS), part = c - j * S;
       s.tile = R * G + j;
       s.k0 = PPP_DIV(part * nk, dS); s.k1 = PPP_DIV((part + 1) * nk, dS);
       if (S == 1) s.role = ROLE_FULL;
-      else if (part == 0) { s.role = ROLE_OWNER; s.slot = 256 + j * (S - 1); s.nslot = S - 1; }
-      else { s.role = ROLE_PRODUCER; s.slot = 256 + j * (S - 1) + part - 1; }
+      else if (part == 0) { s.role = ROLE_OWNER; s.slot = j * (S - 1); s.nslot = S - 1; }
+      else { s.role = ROLE_PRODUCER; s.slot = j * (S - 1) + part - 1; }
     }
     return s;
   };
@@ -742,7 +729,7 @@ __global__ __launch_bounds__(512) void gemm_ppp_kernel(const GemmParams p) {
     int tm0, tn0, tz;
     tile_origin(done.tile, tm0, tn0, tz);
     const int role = done.role;
-    // a shared tile's partial sums go out first (once or twice per workgroup and launch): the accumulators are dead before the next segment's
+    // a shared tile's partial sums go out first (at most once per workgroup and launch): the accumulators are dead before the next segment's
     // loader state and ring come in.  The OWNER of a shared tile adds the other parts' slabs inside its epilogue (the accumulators are only READ there:
     // as values modified on one path they would need a second copy of themselves at the join, i.e. scratch)
     if constexpr (!FF) {
@@ -764,7 +751,7 @@ __global__ __launch_bounds__(512) void gemm_ppp_kernel(const GemmParams p) {
       PPP_DRAIN();  // the ring of the next segment
     } else {
       if constexpr (FF) {
-        finish_tile_ff(tm0, tn0);  // (the planner neither skews nor splits these problems: a tile's statistics want its whole K range)
+        finish_tile_ff(tm0, tn0);  // (the planner does not split these problems: a tile's statistics want its whole K range)
       } else {
         if (role == ROLE_OWNER) wait_parts(done.slot, done.nslot);
         finish_tile(tm0, tn0, tz, done.slot, role == ROLE_OWNER ? done.nslot : 0);
@@ -807,7 +794,7 @@ int32_t gn_ppp_pool_init(int device) {
   return GN_OK;
 }
 
-// rounds / tail split / skew of a problem of `tiles` 256 x 256 tiles and nk K iterations on G workgroups; -> hand-off slabs the launch may use
+// rounds / tail split of a problem of `tiles` 256 x 256 tiles and nk K iterations on G workgroups; -> hand-off slabs the launch may use
 static GemmParams::FastDiv fast_div(unsigned d) {
   GemmParams::FastDiv f;
   if (d == 0) d = 1;
@@ -843,17 +830,11 @@ int gn_ppp_plan(void* params, int tiles, int G) {
   }
   if (p.ln_c1) s = 1;  // the feed-forward variant takes a tile's LayerNorm statistics from its whole K range
   p.ppS = s;
-  // SKEW (workgroup c enters its first tile at K iteration c * nk / G): measured NOT to pay -- with the next tile's ring requested ahead of the
-  // epilogue and no wait behind the stores, the lock-step store bursts drain under the next K loop, and the skew's two hand-offs per workgroup cost
-  // more than the desynchronisation wins (profiles/r06_ppp_ksweep*.txt: 67 / 155 / 505 us without against 79 / 164 / 548 with, K = 256 / 1024 / 4096 at
-  // 1024 tiles).  GN_PPP_SKEW=1 turns it on (tests run both).
-  static const int skew_env = [] { const char* e = getenv("GN_PPP_SKEW"); return e ? atoi(e) : 0; }();
-  p.ppSkew = (skew_env && nk >= 4 && !p.ln_c1) ? 1 : 0;
-  p.dG = fast_div((unsigned)G); p.dS = fast_div((unsigned)s);
+  p.dS = fast_div((unsigned)s);
   p.dTm = fast_div((unsigned)p.tiles_m); p.dTn = fast_div((unsigned)p.tiles_n); p.dTmn = fast_div((unsigned)(p.tiles_m * p.tiles_n));
   p.dOrw = fast_div((unsigned)p.orw);
   p.dHw = fast_div((unsigned)(p.Ho * p.Wo)); p.dWo = fast_div((unsigned)p.Wo); p.dCin = fast_div((unsigned)p.C1); p.dKW = fast_div((unsigned)p.KW);
-  return 256 + p.ppTail * (s > 1 ? s - 1 : 0);
+  return p.ppTail * (s - 1);
 }
 
 void gn_launch_gemm_ppp(const void* params, bool conv, hipStream_t st) {
@@ -861,13 +842,13 @@ void gn_launch_gemm_ppp(const void* params, bool conv, hipStream_t st) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64 || !g_pool[dev]) { (void)gn_ppp_pool_init(dev); }
-  // Flag regions.  Only launches that hand partial sums over use their region (a K-split tail, the skewed walk).  A launch being CAPTURED bakes its
+  // Flag regions.  Only launches that hand partial sums over (a K-split tail) use their region.  A launch being CAPTURED bakes its
   // region into the graph, which may be replayed at any later time beside anything else: it takes a region of the lower half of the pool for good
   // (never recycled; once those 512 are gone a captured launch runs without hand-offs: its tail unsplit, correct and slower).  Eager launches rotate
   // through the upper half: two of them could only collide with 512 flag-using launches in flight between them.
   static std::atomic<unsigned> next_captured{0}, next_eager{0};
   unsigned region = 0;
-  const bool needs_flags = p.ppSkew || (p.ppTail > 0 && p.ppS > 1);
+  const bool needs_flags = p.ppTail > 0 && p.ppS > 1;
   if (needs_flags) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = st != nullptr && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
@@ -876,7 +857,6 @@ void gn_launch_gemm_ppp(const void* params, bool conv, hipStream_t st) {
       if (r < PPP_REGIONS / 2) {
         region = r;
       } else {  // pool exhausted: no hand-offs in this launch (every tile by one workgroup; the workspace named for the split plan is simply not used)
-        p.ppSkew = 0;
         p.ppS = 1;
         p.dS.mul = 1; p.dS.shift = 0;
       }

@@ -319,7 +319,7 @@ class Engine:
 
     @staticmethod
     def _ppp_candidate(d: GemmDesc) -> bool:
-        """Is the persistent skewed ping-pong tile (25, csrc/gemm_ppp.hip) worth racing?  (The library decides eligibility; this only keeps shapes it
+        """Is the persistent ping-pong tile (25, csrc/gemm_ppp.hip) worth racing?  (The library decides eligibility; this only keeps shapes it
         would map back onto tile 15 out of the race.)"""
         if d.M % 256 or d.N % 256 or d.K % 64 or d.K < 256 or d.out_mode != OUT_ROWMAJOR or d.out2 or d.fp8 or d.k_append or d.a2:
             return False

@@ -130,11 +130,11 @@ typedef struct gn_gemm_desc {
                              16..22 = {128x128, 128x64, 64x64, 256x64, 128x160, 64x160, 64x320} with a 3-stage LDS-DMA ring (two K tiles
                              in flight, counted vmcnt); 20..22 are the exact-fit tiles of the N = 640 / 1280 / 320 launches,
                              23 = 128x160 two-stage LDS-DMA, 24 = 128x320 two-stage LDS-DMA on eight waves of 32x160,
-                             25 = PERSISTENT skewed ping-pong 256x256 (round 6, csrc/gemm_ppp.hip): one workgroup per CU walks the tile list, the next
-                             tile's LDS ring is requested before the finished tile's epilogue, tile boundaries are skewed over the chip, the last
-                             partial round is split along K; needs >= one 256x256 tile per CU, a row-major f16 output with N, ldo % 8 == 0, no
-                             split-K / out2 / ln_c1 / GEGLU / shift + residual together (else tile 15 runs), and a workspace of
-                             gn_gemm_workspace_bytes() for the f32 hand-off slabs of the tiles two workgroups share
+                             25 = PERSISTENT ping-pong 256x256 (round 6, csrc/gemm_ppp.hip): one workgroup per CU walks the tile list, the next
+                             tile's LDS ring is requested before the finished tile's epilogue, the last partial round is split along K; needs
+                             >= one 256x256 tile per CU, a row-major f16 output with N, ldo % 8 == 0, no split-K / out2 / shift + residual
+                             together, ln_c1 and GEGLU only together (else tile 15 runs), and, where gn_gemm_workspace_bytes() is not 0, a
+                             workspace of that size for the f32 hand-off slabs of the tiles several workgroups share
                              (the host autotunes this per shape: genima_amd/engine.py) */
   int32_t residual_before_act; /* 1: v = act(acc + bias + shift + residual) (ResNet basic block); 0: residual added last */
   float out_scale;        /* 1.0f = none */

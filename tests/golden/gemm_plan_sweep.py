@@ -149,11 +149,11 @@ def candidates(keys, table):
     return np.array(out, np.int16)
 
 
-def tile_shapes(gemm_hip):
-    """bm x bn of every tile from the kCfg initializer of csrc/gemm.hip (as written when the fixture was made)."""
+def tile_shapes(header):
+    """bm x bn of every tile from the kCfg initializer of csrc/gemm_common.h (as written when the fixture was made)."""
     import re
 
-    src = open(gemm_hip).read()
+    src = open(header).read()
     body = src[src.index("kCfg[] = {"):]
     body = body[:body.index("};")]
     return np.array([(int(a), int(b)) for a, b in re.findall(r"\{(\d+),\s*(\d+),", body)], np.int32)
@@ -170,7 +170,7 @@ def main():
         with open(os.path.join(ROOT, "genima_amd", "gemm_tune_gfx950.json")) as f:
             table = {k: int(v) for k, v in json.load(f).items()}
         keys = sorted(k for k in table if not k.startswith("wg|"))  # (wg: the weight-gradient kernels of gemm_tn.hip, another table)
-        shapes = tile_shapes(os.path.join(ROOT, "genima_amd", "csrc", "gemm.hip"))
+        shapes = tile_shapes(os.path.join(ROOT, "genima_amd", "csrc", "gemm_common.h"))
         assert len(shapes) == NUM_TILES, len(shapes)
         out, plans_of = GOLDEN, np.array([table[k] for k in keys], np.int32)
     else:

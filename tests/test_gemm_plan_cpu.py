@@ -1,6 +1,6 @@
 """-m "not gpu": the GEMM planner (the tile that runs, the K split, gn_gemm_plan_valid) and the autotuner's candidate lists over the corpus of
-tests/golden/gemm_plan_sweep.py agree with the fixture recorded from the library before its tile table became one table
-(tests/golden/gemm_plan_golden.npz), and the library's tile export agrees with the tile shapes recorded there."""
+tests/golden/gemm_plan_sweep.py agree with the fixture that script recorded (tests/golden/gemm_plan_golden.npz; rewritten only where a change
+of the plan is intended), and the library's tile export agrees with the tile shapes recorded there."""
 import ctypes as C
 import os
 import subprocess
@@ -22,7 +22,7 @@ def test_tile_export_matches_the_recorded_shapes():
     assert _lib.load().gn_gemm_tile_info(len(tiles) + 1, C.byref(_lib.GemmTile())) != 0
 
 
-def test_planner_and_autotune_candidates_match_the_fixture(tmp_path):
+def test_planner_workspace_and_autotune_candidates_match_the_fixture(tmp_path):
     out = str(tmp_path / "sweep.npz")
     env = dict(os.environ, GN_GEMM_LOG_FALLBACK="1")  # read once per process: a fresh interpreter
     subprocess.run([sys.executable, os.path.join(HERE, "golden", "gemm_plan_sweep.py"), "--out", out], env=env, check=True, timeout=600)

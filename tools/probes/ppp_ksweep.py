@@ -1,6 +1,5 @@
-"""Tile 25 (persistent skewed ping-pong, csrc/gemm_ppp.hip) against tile 15 (one launch round per 256 tiles, csrc/gemm_pp.hip): time vs K at fixed
-(M, N) -- slope = per-K-tile cost of a tile, intercept / rounds = what a tile costs BESIDE its K loop (<= 6 us per tile asked).
-GN_PPP_SKEW=0 in the environment: the same kernel with every workgroup starting at K = 0 (the chip-wide bursts back)."""
+"""Tile 25 (persistent ping-pong, csrc/gemm_ppp.hip) against tile 15 (one launch round per 256 tiles, csrc/gemm_pp.hip): time vs K at fixed
+(M, N) -- slope = per-K-tile cost of a tile, intercept / rounds = what a tile costs BESIDE its K loop (<= 6 us per tile asked)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from genima_amd.engine import Engine
@@ -17,7 +16,7 @@ def t(fn, n=20):
 shapes = ((131072, 512), (65536, 256), (40960, 1024), (20480, 1024), (524288, 256))
 for tile in (15, 25):
     E.lib.gn_set_gemm_tile_override(tile - 1)
-    print(f"tile {tile}  GN_PPP_SKEW={os.environ.get('GN_PPP_SKEW', '1')}")
+    print(f"tile {tile}")
     for (M, N) in shapes:
         tiles = (M // 256) * (N // 256)
         row = []
