@@ -231,6 +231,8 @@ SIGNATURES = {
     "gn_color_jitter_workspace_bytes": (_I64, [_I32]),
     "gn_color_jitter": (_I32, [_P, _P, _P, _I32, _I64, _I32, _P, _P, _P]),
     "gn_reflect_pad_crop": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "gn_gaussian_blur": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "gn_affine_nearest": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "gn_latent_sample":(_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _F]),
     "gn_ema_flat": (_I32, [_P, _P, _P, _I64, _F]),
     "gn_cast_f32_f16": (_I32, [_P, _P, _P, _I64]),

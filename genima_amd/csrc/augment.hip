@@ -1,7 +1,12 @@
 // Device-side train-time augmentation of the ControlNet trainer (SURVEY.md section 8 rows a12 "augment (:1321)" / a13;
-// diffusion/train_controlnet_genima.py:775-830 with the README recipe `--augmentations=crop,colorjitter`):
+// diffusion/train_controlnet_genima.py:775-830 with `--augmentations` from colorjitter, blur, affine, crop -- README recipe crop,colorjitter;
+// InstructPix2Pix: train_instruct_pix2pix_genima.py:655-710, the edited image in the conditioning role):
 //   * torchvision ColorJitter(brightness 0.2, contrast 0.2, saturation 0.1, hue 0.05) on the conditioning images -- the four
 //     adjust_* ops in the drawn order with the drawn factors (one draw per batch tensor, as torchvision does for a batched call),
+//   * GaussianBlur(kernel_size 3, sigma in (0.1, 2.0)) on the conditioning images: F.pad(mode="reflect") + a depthwise conv with the
+//     outer product of the host's f32 1-D taps,
+//   * RandomAffine.get_params + F.affine (NEAREST, fill None) on both: the host's f32 inverse matrix, torchvision's affine grid and
+//     grid_sample(nearest, zeros, align_corners=False), one matrix for the whole batch,
 //   * reflect-pad by 2 + one random crop back to the resolution, shared by target and conditioning images.
 // Images are NHWC f16 with 8-channel pixels (3 valid), values in [0, 1] (conditioning) or [-1, 1] (targets).  All colour math is
 // f32 in registers; the only cross-pixel dependency is adjust_contrast's per-image grey mean, so the jitter is two passes: pass 1
@@ -126,6 +131,72 @@ __global__ void reflect_pad_crop_kernel(const uint4* __restrict__ x, uint4* __re
   out[idx] = x[(((long)b * H + sy) * W + sx) * C8 + c];
 }
 
+// out[b, y, x, :] = sum_{dy, dx} (k[dy] * k[dx]) * in[b, refl(y + dy - R), refl(x + dx - R), :]  (torchvision gaussian_blur: reflect
+// pad by R = ksize / 2, depthwise conv2d with the 2-D kernel k[:, None] @ k[None, :]); one thread per 8-channel pixel, f32 sums
+struct BlurP {
+  float k[9];  // 1-D taps, k[0 .. 2R]
+};
+template <int R>
+__global__ __launch_bounds__(256) void gaussian_blur_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, int B, int H, int W, int C8, BlurP p) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)B * H * W * C8) return;
+  const int c = (int)(idx % C8);
+  long r = idx / C8;
+  const int ox = (int)(r % W); r /= W;
+  const int oy = (int)(r % H);
+  const int b = (int)(r / H);
+  const uint4* img = x + (long)b * H * W * C8 + c;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int dy = 0; dy <= 2 * R; ++dy) {
+    const uint4* row = img + (long)reflect(oy + dy - R, H) * W * C8;
+#pragma unroll
+    for (int dx = 0; dx <= 2 * R; ++dx) {
+      const float w = p.k[dy] * p.k[dx];  // the 2-D tap as torch.mm forms it: one rounded product
+      const uint4 rv = row[(long)reflect(ox + dx - R, W) * C8];
+      const f16x8 v = *reinterpret_cast<const f16x8*>(&rv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += w * (float)v[e];
+    }
+  }
+  f16x8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (f16)acc[e];
+  out[idx] = *reinterpret_cast<const uint4*>(&o);
+}
+
+// torchvision F_t.affine with NEAREST and no fill: output pixel (x, y) -> base (x - W/2 + 0.5, y - H/2 + 0.5) -> grid = base @ theta^T /
+// [W/2, H/2] -> grid_sample(nearest, zeros, align_corners=False): source index ((g + 1) * W - 1) / 2 rounded half to even, 0 outside.
+// The grid must round like torch's separate f32 ops, so no product may fuse with the add after it.  -ffp-contract=fast fuses across
+// statements and ignores `#pragma clang fp contract`, and __fmul_rn / __fadd_rn are plain `x * y` / `x + y` in clang's header, so each
+// product goes through `rounded` (an empty asm the combiner cannot look through).  `/` is the correctly rounded division.
+__device__ __forceinline__ float rounded(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+struct AffineP {
+  float t[6];  // the f32 inverse matrix [[t0, t1, t2], [t3, t4, t5]]
+};
+__global__ __launch_bounds__(256) void affine_nearest_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, int B, int H, int W, int C8,
+                                                             AffineP p) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)B * H * W * C8) return;
+  const int c = (int)(idx % C8);
+  long r = idx / C8;
+  const int ox = (int)(r % W); r /= W;
+  const int oy = (int)(r % H);
+  const int b = (int)(r / H);
+  const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
+  const float bx = (-hw + 0.5f) + (float)ox, by = (-hh + 0.5f) + (float)oy;  // exact: torch.linspace with step 1
+  const float gx = (rounded(bx * (p.t[0] / hw)) + rounded(by * (p.t[1] / hw))) + p.t[2] / hw;  // base_grid.bmm(theta^T / [W/2, H/2])
+  const float gy = (rounded(bx * (p.t[3] / hh)) + rounded(by * (p.t[4] / hh))) + p.t[5] / hh;
+  const float ix = rintf((rounded((gx + 1.0f) * (float)W) - 1.0f) / 2.0f);  // grid_sampler_unnormalize, then nearbyint
+  const float iy = rintf((rounded((gy + 1.0f) * (float)H) - 1.0f) / 2.0f);
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (ix >= 0.0f && ix < (float)W && iy >= 0.0f && iy < (float)H) v = x[(((long)b * H + (int)iy) * W + (int)ix) * C8 + c];
+  out[idx] = v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -166,6 +237,37 @@ int32_t gn_reflect_pad_crop(gn_ctx* ctx, const void* x, void* out, int32_t B, in
   GN_REQUIRE(crop_i >= 0 && crop_i <= 2 * pad && crop_j >= 0 && crop_j <= 2 * pad, "gn_reflect_pad_crop: crop offset outside the padded image");
   hipLaunchKernelGGL(reflect_pad_crop_kernel, dim3(nblk((long)B * H * W * (C / 8))), dim3(256), 0, ctx->stream, (const uint4*)x, (uint4*)out, B, H,
                      W, C / 8, pad, crop_i, crop_j);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+/* torchvision gaussian_blur with a square odd kernel: reflect padding by ksize / 2 (torch's rule: H, W > ksize / 2), depthwise conv with
+ * the 2-D kernel taps[i] * taps[j] over every channel.  taps: ksize host f32 1-D taps.  C % 8 == 0; out must not alias x. */
+int32_t gn_gaussian_blur(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ksize, const float* taps) {
+  GN_REQUIRE(ctx && x && out && taps && x != out && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "gn_gaussian_blur: bad arguments");
+  GN_REQUIRE(ksize >= 3 && ksize <= 9 && ksize % 2 == 1, "gn_gaussian_blur: ksize must be odd, 3..9");
+  GN_REQUIRE(H > ksize / 2 && W > ksize / 2, "gn_gaussian_blur: reflect padding needs H, W > ksize / 2");
+  BlurP p{};
+  for (int i = 0; i < ksize; ++i) p.k[i] = taps[i];
+  const unsigned grid = nblk((long)B * H * W * (C / 8));
+  switch (ksize / 2) {
+    case 1: hipLaunchKernelGGL(gaussian_blur_kernel<1>, dim3(grid), dim3(256), 0, ctx->stream, (const uint4*)x, (uint4*)out, B, H, W, C / 8, p); break;
+    case 2: hipLaunchKernelGGL(gaussian_blur_kernel<2>, dim3(grid), dim3(256), 0, ctx->stream, (const uint4*)x, (uint4*)out, B, H, W, C / 8, p); break;
+    case 3: hipLaunchKernelGGL(gaussian_blur_kernel<3>, dim3(grid), dim3(256), 0, ctx->stream, (const uint4*)x, (uint4*)out, B, H, W, C / 8, p); break;
+    default: hipLaunchKernelGGL(gaussian_blur_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, (const uint4*)x, (uint4*)out, B, H, W, C / 8, p); break;
+  }
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+/* torchvision F.affine(NEAREST, fill=None) of every image with one f32 inverse matrix theta[6] (_get_inverse_affine_matrix, centre 0):
+ * output pixel (x, y) reads the rounded grid_sample(align_corners=False) source pixel, or 0 outside the image.  C % 8 == 0; no alias. */
+int32_t gn_affine_nearest(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C, const float* theta) {
+  GN_REQUIRE(ctx && x && out && theta && x != out && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "gn_affine_nearest: bad arguments");
+  AffineP p;
+  for (int i = 0; i < 6; ++i) p.t[i] = theta[i];
+  hipLaunchKernelGGL(affine_nearest_kernel, dim3(nblk((long)B * H * W * (C / 8))), dim3(256), 0, ctx->stream, (const uint4*)x, (uint4*)out, B, H, W,
+                     C / 8, p);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

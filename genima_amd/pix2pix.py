@@ -331,8 +331,9 @@ class InstructPix2PixTrainer(ControlNetTrainer):
     # ---- the whole step body from a collated batch
     def train_step(self, batch) -> torch.Tensor:
         """batch: ``original_pixel_values`` / ``edited_pixel_values`` (NCHW in [-1, 1], or NHWC f16 8-channel) and ``input_ids`` [b, 77]
-        -- the collate_fn output of diffusion/train_instruct_pix2pix_genima.py:1018-1037.  RNG draws in the reference's order: posterior
-        sample, noise, timesteps, then the dropout's ``random_p``."""
+        -- the collate_fn output of diffusion/train_instruct_pix2pix_genima.py:1018-1037.  RNG draws in the reference's order: the
+        augmentations of ``attach_frozen(..., augmentations=)`` (augment_data, :1166-1167), posterior sample, noise, timesteps, then the
+        dropout's ``random_p``."""
         E, dev = self.E, self.E.device
         if self.vae_W is None:
             raise GenimaHipError("attach_frozen(...) first")
@@ -345,6 +346,11 @@ class InstructPix2PixTrainer(ControlNetTrainer):
         E, dev = self.E, self.E.device
         edited8 = self._nhwc8(batch["edited_pixel_values"])
         orig8 = self._nhwc8(batch["original_pixel_values"])
+        if self.augmentations:  # augment_data(args, batch) (:1166-1167, :655-710) first: the edited image in the conditioning role
+            from .augment import P2P_ROLES, augment_data
+            aug = augment_data(E, self.augmentations, dict(original_pixel_values=orig8, edited_pixel_values=edited8), self._gen_cpu,
+                               roles=P2P_ROLES)
+            orig8, edited8 = aug["original_pixel_values"], aug["edited_pixel_values"]
         ids = batch["input_ids"].to(dev, torch.int32).contiguous()
         B = edited8.shape[0]
         Cl = self.vae_cfg["latent_channels"]

@@ -1077,7 +1077,9 @@ class ControlNetTrainer:
         if pt not in ("epsilon", "v_prediction"):  # the reference's own refusal (diffusion/train_controlnet_genima.py:1396-1399)
             raise ValueError(f"Unknown prediction type {pt!r}")
         self.prediction_type = pt
-        self.augmentations = augmentations  # the reference's --augmentations comma list ("crop,colorjitter" in the README recipe)
+        # the reference's --augmentations comma list (colorjitter, blur, affine, crop; "crop,colorjitter" in the README recipe), run by
+        # augment.augment_data at the start of the step's front with draws from _gen_cpu (InstructPix2PixTrainer: edited image = conditioning)
+        self.augmentations = augmentations
         self._gen_dev = torch.Generator(device=self.E.device).manual_seed(seed)
         self._gen_cpu = torch.Generator().manual_seed(seed)
 
@@ -1160,7 +1162,7 @@ class ControlNetTrainer:
             batch = to_device(E, batch)
         x8 = self._nhwc8(batch["pixel_values"])
         cond8 = self._nhwc8(batch["conditioning_pixel_values"])
-        if self.augmentations:  # augment_data(args, batch) (:1321): colour jitter on the conditioning image, shared reflect-pad crop
+        if self.augmentations:  # augment_data(args, batch) (:1321): jitter + blur on the conditioning image, shared affine and crop
             from .augment import augment_data
             aug = augment_data(E, self.augmentations, dict(pixel_values=x8, conditioning_pixel_values=cond8), self._gen_cpu)
             x8, cond8 = aug["pixel_values"], aug["conditioning_pixel_values"]

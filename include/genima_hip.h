@@ -575,16 +575,25 @@ int32_t gn_ema_flat(gn_ctx* ctx, float* shadow, const float* param, int64_t n, f
 int32_t gn_cast_f32_f16(gn_ctx* ctx, const float* x, void* out, int64_t n);
 int32_t gn_fill_f32(gn_ctx* ctx, float* x, int64_t n, float v);
 
-/* ---- train-time augmentation on the device (diffusion/train_controlnet_genima.py:775-830, README `--augmentations=crop,colorjitter`) --
+/* ---- train-time augmentation on the device (diffusion/train_controlnet_genima.py:775-830, `--augmentations` colorjitter, blur, affine,
+ * crop; README recipe crop,colorjitter) --
  * gn_color_jitter: torchvision ColorJitter's four adjust_* ops on [B, HW, ld] f16 RGB pixels in [0, 1], applied in `order`
  * (op ids 0 brightness, 1 contrast, 2 saturation, 3 hue = ColorJitter.get_params' fn_idx) with `factors[id]`; f32 colour math,
  * adjust_contrast's per-image grey mean by a deterministic two-stage sum.  out may alias x.
+ * gn_gaussian_blur: torchvision gaussian_blur on NHWC f16 [B, H, W, C], C % 8 == 0: reflect padding by ksize / 2 (odd ksize 3..9,
+ * H, W > ksize / 2) and a depthwise conv with the 2-D taps taps[i] * taps[j] of the host's ksize f32 1-D taps; f32 sums, no alias.
+ * gn_affine_nearest: torchvision F.affine(NEAREST, fill=None) on NHWC f16 [B, H, W, C], C % 8 == 0, with one f32 inverse matrix
+ * theta[6] for the batch: the affine grid and grid_sample(nearest, zeros, align_corners=False) source index (round half to even),
+ * 0 outside the image; no alias.
  * gn_reflect_pad_crop: F.pad(mode="reflect", pad on all sides) + crop of the original H x W at (crop_i, crop_j). */
 int64_t gn_color_jitter_workspace_bytes(int32_t B);
 int32_t gn_color_jitter(gn_ctx* ctx, const void* x, void* out, int32_t B, int64_t HW, int32_t ld, const int32_t* order,
                         const float* factors, void* workspace);
 int32_t gn_reflect_pad_crop(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t pad,
                             int32_t crop_i, int32_t crop_j);
+int32_t gn_gaussian_blur(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ksize,
+                         const float* taps);
+int32_t gn_affine_nearest(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C, const float* theta);
 
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
