@@ -103,6 +103,13 @@ __device__ __forceinline__ float wave_max(float v) {
                fmaxf(__int_as_float(__builtin_amdgcn_readlane(b, 32)), __int_as_float(__builtin_amdgcn_readlane(b, 48))));
 }
 
+// XCD-aware, bijective block -> tile remap: hardware workgroup `bid` of `nwg` runs on XCD bid % 8; give each XCD a contiguous run of tiles
+// (its L2 then holds what neighbouring tiles share)
+__device__ __forceinline__ int xcd_tile_id(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // LDS tile layout shared by the GEMM and attention kernels: rows of ROWB bytes split into 16-byte chunks, chunk index
 // XOR-swizzled by the row so that the four 16-lane groups of a ds_read_b128 MFMA-fragment read (rows = lane&31, one chunk
 // column) hit 16 distinct 16-byte slots of the 256-byte bank row (conflict-free; MI355X_MICROARCH.md LDS table).

@@ -59,14 +59,9 @@ __device__ __forceinline__ void conv3x3_gn_body(const CgParams& p, unsigned char
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, hi = lane >> 5;
 
-  // XCD-aware block -> tile map (block b runs on XCD b % 8): an XCD walks a contiguous run of tiles, the N tiles of one patch side by
+  // XCD-aware block -> tile map (xcd_tile_id): an XCD walks a contiguous run of tiles, the N tiles of one patch side by
   // side, then the next patch along the image row -- neighbours share their halo and their weights in one L2
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tile_n = bid % p.tiles_n;
   int t = bid / p.tiles_n;
   const int tx = t % p.tiles_x;

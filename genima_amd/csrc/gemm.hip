@@ -8,8 +8,12 @@
 //     (tap-major K = KH*KW*Cin) and a Linear's A operand is the same loader with a dense row stride;
 //   * weights are [N][K] f16 (K contiguous) for both;
 //   * BMxBNx64 block tile, 4 or 8 waves, v_mfma_f32_32x32x16_f16 with f32 accumulation;
-//   * global -> registers -> LDS staging, double-buffered, next tile's loads in flight under the current tile's MFMAs
-//     (one barrier per K tile); LDS rows are 128 B with the XOR swizzle of common.h (conflict-free ds_read_b128);
+//   * K tiles are staged in LDS (128-byte rows with the XOR swizzle of common.h: conflict-free ds_read_b128), the next tile's loads in
+//     flight under the current tile's MFMAs.  Who stages them, and where the kernel lives:
+//       gemm_kernel      (here)         global -> registers -> LDS, two buffers, one barrier per K tile: operands of any size
+//       gemm_dma_kernel  (here)         global -> LDS by LDS-DMA, two buffers, drained wait; gemm_fp8_kernel is its fp8 twin
+//       gemm_s3_kernel   (gemm_s3.hip)  LDS-DMA, three-slot ring, counted wait; the normalising A path
+//       gemm_pp_kernel / gemm_ppp_kernel (gemm_pp.hip / gemm_ppp.hip)  256 x 256 ping-pong on half-tile streams, the second persistent;
 //   * the conv gather keeps, per staged row, the source pixel of the CURRENT filter tap (or -1 when the tap falls in the
 //     padding); it is recomputed only when the K walk crosses into the next tap (every Cin/64 tiles), so the per-tile cost
 //     of a gathered load is one multiply-add -- the same as the dense loader;

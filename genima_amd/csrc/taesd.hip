@@ -137,13 +137,8 @@ __global__ __launch_bounds__(512, 1) void tiny_block_kernel(const TbParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // XCD-aware block -> tile map (block b runs on XCD b % 8): an XCD walks a contiguous run of tiles, so neighbours share halos in one L2
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  // XCD-aware block -> tile map (xcd_tile_id): an XCD walks a contiguous run of tiles, so neighbours share halos in one L2
+  const int bid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tx = bid % p.tiles_x;
   const int t = bid / p.tiles_x;
   const int ty = t % p.tiles_y;
