@@ -49,18 +49,8 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(2 * (BM + BN) * 12
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, hi = lane >> 5;
 
-  // XCD-aware, bijective block -> tile remap (block b runs on XCD b % 8; give each XCD a contiguous run of tiles)
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // tile order inside an XCD's contiguous run: row-major (the tiles of one A row band side by side: they share the band in L2) -- or, when the
-  // WEIGHT is the big operand (few rows under a long K: the 8x8 / 16x16 latent levels), column-major, so that the row tiles of one weight
-  // column tile run on ONE XCD and the tile is fetched from HBM once instead of once per L2
-  const int tile_n = p.cm_tiles ? bid / p.tiles_m : bid % p.tiles_n, tile_m = p.cm_tiles ? bid % p.tiles_m : bid / p.tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  int m0, n0;
+  gemm_tile_origin<BM, BN>(p, m0, n0);
   const int z = blockIdx.y;
   const int kbeg = z * p.kper;
   const int kend = min(p.K, kbeg + p.kper);
@@ -80,31 +70,13 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(2 * (BM + BN) * 12
 
   auto set_tap = [&]() {
 #pragma unroll
-    for (int i = 0; i < RA; ++i) {
-      const int iy = iy0[i] + dy, ix = ix0[i] + dx;
-      const bool ok = (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Win;
-      const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;
-      pix[i] = ok ? pbase[i] + sy * p.W + sx : -1;
-    }
+    for (int i = 0; i < RA; ++i) pix[i] = conv_tap_pixel(p, Hin, Win, iy0[i], ix0[i], pbase[i], dy, dx);
   };
 
   if constexpr (CONV) {
     const int hw = p.Ho * p.Wo;
 #pragma unroll
-    for (int i = 0; i < RA; ++i) {
-      const int m = m0 + row0 + RPP * i;
-      if (m < p.M) {
-        const int b = m / hw, rem = m - b * hw;
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        iy0[i] = oy * p.stride - p.pad_t;
-        ix0[i] = ox * p.stride - p.pad_l;
-        pbase[i] = b * p.H * p.W;
-      } else {
-        iy0[i] = -(1 << 28);
-        ix0[i] = -(1 << 28);
-        pbase[i] = 0;
-      }
-    }
+    for (int i = 0; i < RA; ++i) conv_row_decode(p, hw, m0 + row0 + RPP * i, iy0[i], ix0[i], pbase[i]);
     const int tap = kcur / Cin;
     cc = kcur - tap * Cin;
     dy = tap / p.KW;
@@ -249,17 +221,8 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(2 * (BM + BN) * 12
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, hi = lane >> 5;
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // tile order inside an XCD's contiguous run: row-major (the tiles of one A row band side by side: they share the band in L2) -- or, when the
-  // WEIGHT is the big operand (few rows under a long K: the 8x8 / 16x16 latent levels), column-major, so that the row tiles of one weight
-  // column tile run on ONE XCD and the tile is fetched from HBM once instead of once per L2
-  const int tile_n = p.cm_tiles ? bid / p.tiles_m : bid % p.tiles_n, tile_m = p.cm_tiles ? bid % p.tiles_m : bid / p.tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  int m0, n0;
+  gemm_tile_origin<BM, BN>(p, m0, n0);
   const int z = blockIdx.y;
   const int kbeg = z * p.kper;
   const int kend = min(p.K, kbeg + p.kper);
@@ -280,31 +243,13 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(2 * (BM + BN) * 12
 
   auto set_tap = [&]() {
 #pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const int iy = iy0[i] + dy, ix = ix0[i] + dx;
-      const bool ok = (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Win;
-      const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;
-      pix[i] = ok ? pbase[i] + sy * p.W + sx : -1;
-    }
+    for (int i = 0; i < GA; ++i) pix[i] = conv_tap_pixel(p, Hin, Win, iy0[i], ix0[i], pbase[i], dy, dx);
   };
 
   if constexpr (CONV) {
     const int hw = p.Ho * p.Wo;
 #pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const int m = m0 + 8 * (wave + NW * i) + lr;
-      if (m < p.M) {
-        const int b = m / hw, rem = m - b * hw;
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        iy0[i] = oy * p.stride - p.pad_t;
-        ix0[i] = ox * p.stride - p.pad_l;
-        pbase[i] = b * p.H * p.W;
-      } else {
-        iy0[i] = -(1 << 28);
-        ix0[i] = -(1 << 28);
-        pbase[i] = 0;
-      }
-    }
+    for (int i = 0; i < GA; ++i) conv_row_decode(p, hw, m0 + 8 * (wave + NW * i) + lr, iy0[i], ix0[i], pbase[i]);
     const int tap = kcur / Cin;
     cc = kcur - tap * Cin;
     dy = tap / p.KW;
@@ -423,9 +368,8 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(2 * (BM + BN) * 12
   if constexpr (LNF) ln_stats_init(lnst);
 
   int cur = 0;
-  // wsel: which of the WN column waves' share of the K steps this copy of the loop takes the LayerNorm statistics on (LNF).  The choice is
-  // made ONCE, outside the K loop (one specialised copy of the loop per column wave): conditional branches inside it cost issue slots even when
-  // they fall through (measured on the whole call: DESIGN.md, round 3); the loop body itself has the back edge and nothing else.
+  // wsel: whose share of the K steps this copy of the loop takes the LayerNorm statistics on (ln_fold_dispatch picks the copy, outside the
+  // loop); the loop body itself has the back edge and nothing else
   auto k_tile = [&](auto wsel_c) __attribute__((always_inline)) {
     constexpr int WSEL = decltype(wsel_c)::value;
     const unsigned char* As = smem + cur * (A_BYTES + B_BYTES);
@@ -461,14 +405,7 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(2 * (BM + BN) * 12
     }
     k_tile(wsel_c);
   };
-  if constexpr (LNF && WN > 1) {
-    if (wn == 0) k_loop(std::integral_constant<int, 0>{});
-    else if (WN > 2 && wn == 2) k_loop(std::integral_constant<int, 2 % WN>{});
-    else if (WN > 2 && wn == 3) k_loop(std::integral_constant<int, 3 % WN>{});
-    else k_loop(std::integral_constant<int, 1>{});
-  } else {
-    k_loop(std::integral_constant<int, 0>{});
-  }
+  ln_fold_dispatch<LNF ? WN : 1>(wn, k_loop);
 
   if constexpr (LNF)  // (the barrier that ended the K loop freed the LDS tiles)
     ln_fold_apply<TM, TN, WN, BM>(p, acc, lnst, reinterpret_cast<float*>(smem), wm * WTM, wn,
@@ -504,17 +441,8 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(2 * (BM + BN) * 12
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, hi = lane >> 5;
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // tile order inside an XCD's contiguous run: row-major (the tiles of one A row band side by side: they share the band in L2) -- or, when the
-  // WEIGHT is the big operand (few rows under a long K: the 8x8 / 16x16 latent levels), column-major, so that the row tiles of one weight
-  // column tile run on ONE XCD and the tile is fetched from HBM once instead of once per L2
-  const int tile_n = p.cm_tiles ? bid / p.tiles_m : bid % p.tiles_n, tile_m = p.cm_tiles ? bid % p.tiles_m : bid / p.tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  int m0, n0;
+  gemm_tile_origin<BM, BN>(p, m0, n0);
   const int nk = (p.K + BKB - 1) / BKB;
 
   const int lr = lane >> 3;

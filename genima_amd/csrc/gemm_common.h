@@ -1,5 +1,5 @@
-// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm_pp.hip): kernel parameter block, activations and the fused
-// epilogues (bias / time shift / residual / activation / GEGLU / f32 + accumulate / transposed / split-K slab).
+// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm_s3.hip, gemm_pp.hip, gemm_ppp.hip): kernel parameter block, tile walk, conv gather,
+// activations and the fused epilogues (bias / time shift / residual / activation / GEGLU / f32 + accumulate / transposed / split-K slab).
 #pragma once
 #include <stdlib.h>
 
@@ -100,7 +100,7 @@ __device__ __forceinline__ void gemm_sink_tail(const GemmParams& p, int m0, int 
 }
 
 // the appended 1x1 segment of a k_append conv: source offset of staged row i for the K tile whose lane offset inside the segment is `co`
-// (iy0 / ix0 / pbase as the conv loaders keep them: the row's top-left tap coordinate and image base; rows >= M carry -(1 << 28))
+// (iy0 / ix0 / pbase as the conv loaders keep them: the row's top-left tap coordinate and image base; rows >= M carry conv_row_decode's sentinel)
 // cs / co: channel count of the source this K tile lies in and the lane's channel inside it (kapp_src below)
 __device__ __forceinline__ unsigned kapp_voff(const GemmParams& p, int iy0, int ix0, int pbase, int cs, int co) {
   const int cy = iy0 + p.pad_t, cx = ix0 + p.pad_l;  // stride 1: the output pixel itself
@@ -706,6 +706,60 @@ constexpr int gemm_waves_per_simd(int lds_bytes, int waves_per_block) {
 // tile in the 128x128 kernel) -- removing them: 98.8 vs 100.3 ms per tiled call on one box.
 #define GN_PIN(x) asm volatile("" : "+v"(x))
 constexpr unsigned kOOB = 0xFFFFFFF0u;  // out-of-range buffer offset: the hardware writes zeros to LDS for such lanes
+
+// ---- the front half of the tile kernels (gemm.hip, gemm_s3.hip, gemm_pp.hip): tile walk, conv gather, LayerNorm-fold dispatch ---------------------
+// What a kernel computes once and its loader lambdas capture (Hin / Win, Ho * Wo) is PASSED to these helpers, never recomputed inside them:
+// recomputing it restructures the conv kernels' K loops (profiles/r08_gemm_shared_front_isa.txt).
+
+// origin of this workgroup's BM x BN tile: the XCD remap (xcd_tile_id, common.h), then the tile order inside an XCD's contiguous run
+template <int BM, int BN>
+__device__ __forceinline__ void gemm_tile_origin(const GemmParams& p, int& m0, int& n0) {
+  const int bid = xcd_tile_id(blockIdx.x, gridDim.x);
+  // row-major (the tiles of one A row band side by side: they share the band in L2) -- or, when the WEIGHT is the big operand (few rows under
+  // a long K: the 8x8 / 16x16 latent levels), column-major, so that the row tiles of one weight column tile run on ONE XCD and the tile is
+  // fetched from HBM once instead of once per L2
+  const int tile_n = p.cm_tiles ? bid / p.tiles_m : bid % p.tiles_n, tile_m = p.cm_tiles ? bid % p.tiles_m : bid / p.tiles_n;
+  m0 = tile_m * BM;
+  n0 = tile_n * BN;
+}
+
+// conv gather, per staged row: output row m (hw = Ho * Wo) -> top-left tap coordinate and the first pixel of its sample; rows >= M get a
+// coordinate no tap brings back into the image (kapp_voff tests for it)
+__device__ __forceinline__ void conv_row_decode(const GemmParams& p, int hw, int m, int& iy0, int& ix0, int& pbase) {
+  if (m < p.M) {
+    const int b = m / hw, rem = m - b * hw;
+    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
+    iy0 = oy * p.stride - p.pad_t;
+    ix0 = ox * p.stride - p.pad_l;
+    pbase = b * p.H * p.W;
+  } else {
+    iy0 = ix0 = -(1 << 28);
+    pbase = 0;
+  }
+}
+// ... and the source pixel of filter tap (dy, dx) for that row, -1 in the padding (Hin x Win: the input as the taps see it, 2 H x 2 W under `ups`)
+__device__ __forceinline__ int conv_tap_pixel(const GemmParams& p, int Hin, int Win, int iy0, int ix0, int pbase, int dy, int dx) {
+  const int iy = iy0 + dy, ix = ix0 + dx;
+  const bool ok = (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Win;
+  const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;
+  return ok ? pbase + sy * p.W + sx : -1;
+}
+
+// LayerNorm fold: one specialised copy of the K loop per column wave, chosen ONCE outside it -- k_loop(wsel) takes the row statistics on the
+// K steps kk with kk % WN == wsel (WN = 1: one copy).  Conditional branches inside the loop cost issue slots even when they fall through
+// (measured on the whole call: DESIGN.md, round 3).
+template <int WN, class F>
+__device__ __forceinline__ void ln_fold_dispatch(int wn, F&& k_loop) {
+  if constexpr (WN > 1) {
+    if (wn == 0) k_loop(std::integral_constant<int, 0>{});
+    else if (WN > 2 && wn == 2) k_loop(std::integral_constant<int, 2 % WN>{});
+    else if (WN > 2 && wn == 3) k_loop(std::integral_constant<int, 3 % WN>{});
+    else k_loop(std::integral_constant<int, 1>{});
+  } else {
+    k_loop(std::integral_constant<int, 0>{});
+  }
+}
+
 
 // The block-tile configurations of gn_gemm: row index + 1 is the public gn_gemm_desc::tile value.  A row is its block and wave tile, its
 // relative MFMA rate on large problems (tools/bench_gemm.py; the fallback heuristic only considers eff > 0, the host autotuner times every

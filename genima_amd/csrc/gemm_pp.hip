@@ -38,17 +38,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams pin) {
   const int wr = wave >> 2, wc = wave & 3;  // wr = ping-pong group = which 64 rows of each A half; wc = which 32 rows of each W half
   const int l31 = lane & 31, hi = lane >> 5;
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // tile order inside an XCD's contiguous run: row-major (the tiles of one A row band side by side: they share the band in L2) -- or, when the
-  // WEIGHT is the big operand (few rows under a long K: the 8x8 / 16x16 latent levels), column-major, so that the row tiles of one weight
-  // column tile run on ONE XCD and the tile is fetched from HBM once instead of once per L2
-  const int tile_n = p.cm_tiles ? bid / p.tiles_m : bid % p.tiles_n, tile_m = p.cm_tiles ? bid % p.tiles_m : bid / p.tiles_n;
-  const int m0 = tile_m * 256, n0 = tile_n * 256;
+  int m0, n0;
+  gemm_tile_origin<256, 256>(p, m0, n0);
   const int z = blockIdx.y;
   const int kbeg = z * p.kper;
   const int kend = min(p.K, kbeg + p.kper);
@@ -71,12 +62,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams pin) {
 
   auto set_tap = [&](int h) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int iy = iy0[h][i] + dyA[h], ix = ix0[h][i] + dxA[h];
-      const bool ok = (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Win;
-      const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;
-      pix[h][i] = ok ? pbase[h][i] + sy * p.W + sx : -1;
-    }
+    for (int i = 0; i < 2; ++i) pix[h][i] = conv_tap_pixel(p, Hin, Win, iy0[h][i], ix0[h][i], pbase[h][i], dyA[h], dxA[h]);
   };
 
 #pragma unroll
@@ -86,18 +72,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams pin) {
       const int row = 128 * h + 8 * (wave + 8 * i) + lr;
       const int m = m0 + row;
       if constexpr (CONV) {
-        const int hw = p.Ho * p.Wo;
-        if (m < p.M) {
-          const int b = m / hw, rem = m - b * hw;
-          const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-          iy0[h][i] = oy * p.stride - p.pad_t;
-          ix0[h][i] = ox * p.stride - p.pad_l;
-          pbase[h][i] = b * p.H * p.W;
-        } else {
-          iy0[h][i] = -(1 << 28);
-          ix0[h][i] = -(1 << 28);
-          pbase[h][i] = 0;
-        }
+        conv_row_decode(p, p.Ho * p.Wo, m, iy0[h][i], ix0[h][i], pbase[h][i]);
       } else {
         aoff[h][i] = (m < p.M) ? (unsigned)((long)m * p.lda * 2) : 0u;
         amask[h][i] = (m < p.M) ? 0u : kOOB;

@@ -106,14 +106,10 @@ __global__ __launch_bounds__(512) void gemm_ppp_kernel(const GemmParams p) {
     int c = blockIdx.x;
     asm volatile("" : "+s"(c));  // (opaque: the values derived from it are not hoisted out of the segment loop)
     const int G = q->ppG, nk = q->K / BK, R = q->ppR, S = q->ppS;
-    auto vid = [&](int b) __attribute__((always_inline)) {  // XCD-aware position of hardware workgroup b inside a round: an XCD's workgroups take a contiguous run of tiles
-      const int qq = G >> 3, r = G & 7, xcd = b & 7, idx = b >> 3;
-      return (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + idx;
-    };
     Seg s;
     s.slot = 0; s.nslot = 0;
-    if (i < R) {  // a full round
-      s.tile = i * G + vid(c); s.k0 = 0; s.k1 = nk; s.role = ROLE_FULL;
+    if (i < R) {  // a full round: hardware workgroup c takes the XCD-aware position xcd_tile_id(c, G) inside it
+      s.tile = i * G + xcd_tile_id(c, G); s.k0 = 0; s.k1 = nk; s.role = ROLE_FULL;
     } else {  // a tile of the last partial round, split along K over ppS workgroups
       const int j = PPP_DIV(c, dS), part = c - j * S;
       s.tile = R * G + j;

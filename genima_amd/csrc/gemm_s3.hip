@@ -1,8 +1,9 @@
 // 3-stage LDS-DMA ring for the LATENCY-BOUND mid-size launches (Linears / small convs with one workgroup per CU and 5..40 K tiles):
 // the 2-stage kernel of gemm.hip has one K tile in flight and drains it (`vmcnt(0)` + barrier) every iteration, so each iteration costs
-// a full L2 / MALL round trip; here two tiles are in flight and the wait is counted.  Same tiles, loaders, swizzle and epilogue as
-// gemm_dma_kernel (gemm.hip); the per-lane validity selects become OR-masks so that every path issues the same number of VMEM
-// instructions (the counted vmcnt depends on it).  The GN_GEMM_RING rows of kCfg (gemm_common.h).
+// a full L2 / MALL round trip; here two tiles are in flight and the wait is counted.  The tile walk (gemm_tile_origin), the conv gather
+// (conv_row_decode, conv_tap_pixel), the LayerNorm-fold dispatch (ln_fold_dispatch), swizzle and epilogue are gemm_common.h's, as in
+// gemm_dma_kernel (gemm.hip); the DMA issue loop is this kernel's own: the per-lane validity selects become OR-masks so that every path
+// issues the same number of VMEM instructions (the counted vmcnt depends on it).  The GN_GEMM_RING rows of kCfg (gemm_common.h).
 #include <type_traits>
 
 #include "gemm_common.h"
@@ -56,17 +57,8 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(3 * (BM + BN) * 12
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, hi = lane >> 5;
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // tile order inside an XCD's contiguous run: row-major (the tiles of one A row band side by side: they share the band in L2) -- or, when the
-  // WEIGHT is the big operand (few rows under a long K: the 8x8 / 16x16 latent levels), column-major, so that the row tiles of one weight
-  // column tile run on ONE XCD and the tile is fetched from HBM once instead of once per L2
-  const int tile_n = p.cm_tiles ? bid / p.tiles_m : bid % p.tiles_n, tile_m = p.cm_tiles ? bid % p.tiles_m : bid / p.tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  int m0, n0;
+  gemm_tile_origin<BM, BN>(p, m0, n0);
   const int z = blockIdx.y;
   const int kbeg = z * p.kper;
   const int kend = min(p.K, kbeg + p.kper);
@@ -87,31 +79,13 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(3 * (BM + BN) * 12
 
   auto set_tap = [&]() {
 #pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const int iy = iy0[i] + dy, ix = ix0[i] + dx;
-      const bool ok = (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Win;
-      const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;
-      pix[i] = ok ? pbase[i] + sy * p.W + sx : -1;
-    }
+    for (int i = 0; i < GA; ++i) pix[i] = conv_tap_pixel(p, Hin, Win, iy0[i], ix0[i], pbase[i], dy, dx);
   };
 
   if constexpr (CONV) {
     const int hw = p.Ho * p.Wo;
 #pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const int m = m0 + 8 * (wave + NW * i) + lr;
-      if (m < p.M) {
-        const int b = m / hw, rem = m - b * hw;
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        iy0[i] = oy * p.stride - p.pad_t;
-        ix0[i] = ox * p.stride - p.pad_l;
-        pbase[i] = b * p.H * p.W;
-      } else {
-        iy0[i] = -(1 << 28);
-        ix0[i] = -(1 << 28);
-        pbase[i] = 0;
-      }
-    }
+    for (int i = 0; i < GA; ++i) conv_row_decode(p, hw, m0 + 8 * (wave + NW * i) + lr, iy0[i], ix0[i], pbase[i]);
     const int tap = kcur / Cin;
     cc = kcur - tap * Cin;
     dy = tap / p.KW;
@@ -327,8 +301,7 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(3 * (BM + BN) * 12
   if constexpr (LNF) ln_stats_init(lnst);
 
   int cur = 0;
-  // LNF: one specialised copy of the K loop per column wave, chosen ONCE outside it (wsel = whose share of the K steps the copy takes the
-  // LayerNorm statistics on): conditional branches inside the loop cost issue slots even when they fall through (measured: DESIGN.md, round 3)
+  // wsel: whose share of the K steps this copy of the loop takes the LayerNorm statistics on (ln_fold_dispatch picks the copy, outside the loop)
   auto k_loop = [&](auto wsel_c) __attribute__((always_inline)) {
     constexpr int WSEL = decltype(wsel_c)::value;
     for (int kt = 0; kt < nk; ++kt) {
@@ -366,14 +339,7 @@ __global__ __launch_bounds__(WM* WN * 64, gemm_waves_per_simd(3 * (BM + BN) * 12
       cur = cur == 2 ? 0 : cur + 1;
     }
   };
-  if constexpr (LNF && WN > 1) {
-    if (wn == 0) k_loop(std::integral_constant<int, 0>{});
-    else if (WN > 2 && wn == 2) k_loop(std::integral_constant<int, 2 % WN>{});
-    else if (WN > 2 && wn == 3) k_loop(std::integral_constant<int, 3 % WN>{});
-    else k_loop(std::integral_constant<int, 1>{});
-  } else {
-    k_loop(std::integral_constant<int, 0>{});
-  }
+  ln_fold_dispatch<LNF ? WN : 1>(wn, k_loop);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the run-ahead zero fills
 
   if constexpr (LNF) {

@@ -2,7 +2,11 @@
 """Per-kernel instruction-stream comparison of two builds of one object (a refactor's "what did the compiler make of it").
 
     llvm-objdump --offloading a/gemm.o && llvm-objdump -d a/gemm.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 > a.txt   (same for b)
-    tools/probes/isa_diff.py a.txt b.txt
+    tools/probes/isa_diff.py [--opcodes] a.txt b.txt
+
+Every run prints three tallies for the object: kernels with an identical instruction stream, with an identical MNEMONIC stream (the same
+instructions in the same order, operands aside: a commuted operand pair or another register assignment) and with equal length.  --opcodes
+compares mnemonics only: kernels that differ in operands alone are not listed.
 
 Addresses and encodings are stripped (branch operands are relative, so the text is position-independent).  A kernel whose stream differs
 gets two rows of counts, before and after: instructions, then VMEM / DS / MFMA / s_waitcnt / barrier of the whole kernel and of its K-loop
@@ -67,14 +71,24 @@ def row(body):
     return "%6d | %s | %s" % (len(body), " ".join("%4d" % w[k] for k in w), " ".join("%4d" % l[k] for k in l))
 
 
+def stream(body, opcodes):
+    return [i.split()[0] if opcodes else i for _, i in body]
+
+
 def main():
-    if len(sys.argv) != 3:
+    args = [x for x in sys.argv[1:] if x != "--opcodes"]
+    opcodes = len(args) != len(sys.argv) - 1
+    if len(args) != 2:
         sys.exit(__doc__)
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    a, b = kernels(args[0]), kernels(args[1])
     if sorted(a) != sorted(b):
         print("KERNEL SETS DIFFER:", sorted(set(a) ^ set(b)))
-    same = [k for k in a if k in b and [i for _, i in a[k]] == [i for _, i in b[k]]]
-    print("%d kernels, %d with an identical instruction stream" % (len(a), len(same)))
+    both = [k for k in a if k in b]
+    ident = [k for k in both if stream(a[k], False) == stream(b[k], False)]
+    mnem = [k for k in both if stream(a[k], True) == stream(b[k], True)]
+    print("%d kernels, %d with an identical instruction stream, %d with an identical mnemonic stream, %d of equal length"
+          % (len(a), len(ident), len(mnem), sum(len(a[k]) == len(b[k]) for k in both)))
+    same = mnem if opcodes else ident
     print("differing kernels:  insns | whole kernel: vmem ds mfma wait bar | K-loop bodies: vmem ds mfma wait bar")
     for k in sorted(a):
         if k in b and k not in same:
