@@ -51,6 +51,7 @@ def parse_args(argv=None):
                     help="gradient exchange: bucketed RS+AG overlapped with the backward (default), one RS+AG after it, or the C-ABI "
                          "RCCL communicator (gn_comm_*; -bf16: bf16 on the wire)")
     ap.add_argument("--graph", action="store_true", help="capture the forward + backward walk into one hipGraph after two eager steps and replay it")
+    ap.add_argument("--use_8bit_adam", action="store_true", help="8-bit blockwise AdamW moments (the reference's --use_8bit_adam; csrc/optim8.hip)")
     ap.add_argument("--gemm-table", default=None, help="write the per-(shape, tile) HIP-event GEMM timing table of one extra step to this CSV")
     return ap.parse_args(argv)
 
@@ -82,7 +83,7 @@ def run(args, quiet: bool = False):
         exchange = {"buckets": lambda: dist.GradBuckets(n_buckets=8), "flat": lambda: dist.allreduce_sum_flat,
                     "abi": lambda: dist.AbiComm(E, rank, world), "abi-bf16": lambda: dist.AbiComm(E, rank, world, bf16_wire=True)}[args.exchange]()
     tr = ControlNetTrainer(E, fam["unet"], fam["controlnet"], unet_W, cn_sd, lr=args.lr, allreduce=exchange,
-                           hip_graph=bool(args.graph) and not args.gemm_table)
+                           hip_graph=bool(args.graph) and not args.gemm_table, use_8bit_adam=bool(getattr(args, "use_8bit_adam", False)))
     del cn_sd
     text2_W = pack_state_dict(synth(schema.clip_text_schema(fam["text_2"]), 5), dev) if "text_2" in fam else None
     tr.attach_frozen(fam["vae"], vae_W, fam["text"], text_W, DDPMScheduler(), seed=1234 + rank,
@@ -137,7 +138,8 @@ def run(args, quiet: bool = False):
                                     "BASELINE.json configs[3]: SD-Turbo ControlNet fine-tune, 512x512 (4x256x256 tiled views)"),
                        "family": args.family,
                        "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}", "gradient_exchange": args.exchange if world > 1 else None,
-                       "hip_graph": bool(tr._graphs), "optimizer": "AdamW fp32 master, f16 compute, loss scale",
+                       "hip_graph": bool(tr._graphs), "optimizer": ("AdamW 8-bit blockwise moments, fp32 master, f16 compute, loss scale" if tr.use_8bit_adam
+                                                                   else "AdamW fp32 master, f16 compute, loss scale"),
                        "trainable_params_padded": int(tr.cn.numel), "fp8_frozen_linears": n_fp8},
             "loss_first": float(losses[0]), "loss_last": float(losses[-1]), "grad_norm_last": tr.last.get("grad_norm"),
             "loss_scale": tr.loss_scale, "applied_steps": tr.opt_step,

@@ -319,7 +319,7 @@ class InstructPix2PixTrainer(ControlNetTrainer):
         if self.use_ema:
             _, sd = weights.load_diffusers_dir(os.path.join(checkpoint_dir, "unet_ema"))
             sd = OrderedDict((k, sd[k]) for k in self._trainable_schema())
-            self.ema.copy_(TrainParams(self.E, sd).master)
+            self.ema.copy_(TrainParams(self.E, sd, use_8bit_adam=self.use_8bit_adam).master)
             self.ema_steps = int(load_file(os.path.join(checkpoint_dir, "ema_flat.safetensors"))["ema_steps"][0])
         return step
 

@@ -380,6 +380,20 @@ def adamw(E: Engine, param, grad, m, v, lr, beta1, beta2, eps, wd, step: int, cl
                               _ptr(half_out), int(zero_grad)), "gn_adamw_flat")
 
 
+def adamw8(E: Engine, param, grad, m_codes, v_codes, m_absmax, v_absmax, table, map_signed, map_unsigned, lr, beta1, beta2, eps, wd, step: int,
+           clip: Optional[torch.Tensor] = None, grad_scale: float = 1.0, half_out: Optional[torch.Tensor] = None, zero_grad: bool = False):
+    """8-bit blockwise AdamW (csrc/optim8.hip) over the quantisation blocks of ``table`` (optim8.build_block_table, on the device):
+    m_codes / v_codes uint8, m_absmax / v_absmax f32 [n_blocks], map_* f32 [256] (optim8.dynamic_map); the rest as ``adamw``."""
+    n_blocks = table.shape[0]
+    assert table.dtype == torch.int64 and table.is_contiguous() and m_codes.dtype == torch.uint8 and v_codes.dtype == torch.uint8
+    assert m_codes.numel() == v_codes.numel() and m_absmax.numel() == n_blocks == v_absmax.numel()
+    assert map_signed.numel() == 256 == map_unsigned.numel() and map_signed.dtype == F32 and map_unsigned.dtype == F32
+    assert half_out is None or half_out.numel() == param.numel()
+    check(E.lib.gn_adamw8_flat(E._ctx, _ptr(param), _ptr(grad), param.numel(), _ptr(m_codes), _ptr(v_codes), m_codes.numel(), _ptr(m_absmax),
+                               _ptr(v_absmax), _ptr(table), n_blocks, _ptr(map_signed), _ptr(map_unsigned), lr, beta1, beta2, eps, wd, step,
+                               _ptr(clip), grad_scale, _ptr(half_out), int(zero_grad)), "gn_adamw8_flat")
+
+
 def latent_sample(E: Engine, moments: torch.Tensor, eps: torch.Tensor, C_lat: int, scale: float, ld_out: int = 8) -> torch.Tensor:
     """moments [..., >= 2*C_lat] (mean | logvar), eps [..., >= C_lat] -> f16 [..., ld_out] scaled posterior sample, zero padded."""
     out = torch.empty(tuple(moments.shape[:-1]) + (ld_out,), dtype=F16, device=E.device)

@@ -71,25 +71,47 @@ class FrozenParams:
         return t
 
 
-class TrainParams(FrozenParams):
-    """Flat fp32 master / gradient / Adam-moment buffers + flat f16 working copy of one trainable network (packed layout)."""
+def flat_layout(packed) -> Tuple["OrderedDict[str, Tuple[int, Tuple[int, ...]]]", int]:
+    """name -> (offset, shape) of every trainable tensor of a packed state dict in the flat buffers, each at a multiple of 8 elements;
+    -> (layout, total elements)."""
+    layout: "OrderedDict[str, Tuple[int, Tuple[int, ...]]]" = OrderedDict()
+    off = 0
+    for name, t in packed.items():
+        if name == "__meta__" or name.endswith(_DUP_SUFFIXES):
+            continue  # covered by attn1.to_qk (+ to_v) / time_emb_proj_all
+        layout[name] = (off, tuple(t.shape))
+        off += _rup(t.numel(), 8)
+    return layout, off
 
-    def __init__(self, E: Engine, state_dict: Dict[str, torch.Tensor]):
+
+class TrainParams(FrozenParams):
+    """Flat fp32 master / gradient / Adam-moment buffers + flat f16 working copy of one trainable network (packed layout).
+    ``use_8bit_adam``: the moments are kept as 8-bit blockwise codes instead (optim8.py: ``m_codes`` / ``v_codes`` + one absmax per
+    quantisation block and moment, compact fp32 moments for the parameters under optim8.MIN_8BIT_SIZE elements) -- never both forms."""
+
+    def __init__(self, E: Engine, state_dict: Dict[str, torch.Tensor], use_8bit_adam: bool = False):
         packed = pack_state_dict(state_dict, E.device, dtype=F32)
         meta = packed.pop("__meta__")
-        self.layout: "OrderedDict[str, Tuple[int, Tuple[int, ...]]]" = OrderedDict()
-        off = 0
-        for name, t in packed.items():
-            if name.endswith(_DUP_SUFFIXES):
-                continue  # covered by attn1.to_qk (+ to_v) / time_emb_proj_all
-            self.layout[name] = (off, tuple(t.shape))
-            off += _rup(t.numel(), 8)
+        self.layout, off = flat_layout(packed)
         self.numel = off
         dev = E.device
         self.master = torch.zeros(off, dtype=F32, device=dev)
         self.grad = torch.zeros(off, dtype=F32, device=dev)
-        self.exp_avg = torch.zeros(off, dtype=F32, device=dev)
-        self.exp_avg_sq = torch.zeros(off, dtype=F32, device=dev)
+        self.use_8bit_adam = bool(use_8bit_adam)
+        if self.use_8bit_adam:
+            from . import optim8
+            table, self.small_ranges, n8, n_small = optim8.build_block_table(self.layout)
+            self.block_table = table.to(dev)
+            self.m_codes = torch.zeros(n8, dtype=torch.uint8, device=dev)  # absmax 0: every code reads as 0 until the first step
+            self.v_codes = torch.zeros(n8, dtype=torch.uint8, device=dev)
+            self.m_absmax = torch.zeros(table.shape[0], dtype=F32, device=dev)
+            self.v_absmax = torch.zeros(table.shape[0], dtype=F32, device=dev)
+            self.exp_avg_small = torch.zeros(n_small, dtype=F32, device=dev)
+            self.exp_avg_sq_small = torch.zeros(n_small, dtype=F32, device=dev)
+            self.map_signed, self.map_unsigned = optim8.dynamic_map(True).to(dev), optim8.dynamic_map(False).to(dev)
+        else:
+            self.exp_avg = torch.zeros(off, dtype=F32, device=dev)
+            self.exp_avg_sq = torch.zeros(off, dtype=F32, device=dev)
         self.half = torch.zeros(off, dtype=F16, device=dev)
         W, G = OrderedDict(), OrderedDict()
         for name, (o, shape) in self.layout.items():
@@ -156,6 +178,28 @@ class TrainParams(FrozenParams):
 
     def zero_grad(self):
         T.fill_f32(self.E, self.grad, 0.0)
+
+    def optimizer_state(self) -> "OrderedDict[str, torch.Tensor]":
+        """The optimizer's state tensors under their checkpoint names."""
+        names = (("m_codes", "v_codes", "m_absmax", "v_absmax", "exp_avg_small", "exp_avg_sq_small") if self.use_8bit_adam
+                 else ("exp_avg", "exp_avg_sq"))
+        return OrderedDict((k, getattr(self, k)) for k in names)
+
+    def adamw(self, lr, beta1, beta2, eps, wd, step: int, clip, grad_scale: float):
+        """One pass: AdamW on the fp32 master, the f16 working copy refreshed from the new values, the gradient cleared."""
+        E = self.E
+        if not self.use_8bit_adam:
+            T.adamw(E, self.master, self.grad, self.exp_avg, self.exp_avg_sq, lr, beta1, beta2, eps, wd, step, clip, grad_scale,
+                    half_out=self.half, zero_grad=True)
+            return
+        if self.block_table.shape[0]:
+            T.adamw8(E, self.master, self.grad, self.m_codes, self.v_codes, self.m_absmax, self.v_absmax, self.block_table, self.map_signed,
+                     self.map_unsigned, lr, beta1, beta2, eps, wd, step, clip, grad_scale, half_out=self.half, zero_grad=True)
+        at = 0
+        for a, b in self.small_ranges:  # biases, norm weights: fp32 moments (bitsandbytes' min_8bit_size), the fp32 kernel on sub-ranges
+            T.adamw(E, self.master[a:b], self.grad[a:b], self.exp_avg_small[at:at + b - a], self.exp_avg_sq_small[at:at + b - a], lr, beta1,
+                    beta2, eps, wd, step, clip, grad_scale, half_out=self.half[a:b], zero_grad=True)
+            at += b - a
 
     def packed_master(self) -> "OrderedDict[str, torch.Tensor]":
         out = OrderedDict()
@@ -765,8 +809,10 @@ class ControlNetTrainer:
     def __init__(self, E: Engine, unet_cfg, controlnet_cfg, unet_W, controlnet_sd, *, lr: float = 1e-5, betas=(0.9, 0.999),
                  weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, loss_scale: float = 65536.0,
                  growth_interval: int = 2000, allreduce=None, gradient_accumulation_steps: int = 1, lr_lambda=None, gc_freeze: bool = True,
-                 hip_graph: Optional[bool] = None):
-        """``gradient_accumulation_steps``: micro-batches per optimizer step (``accelerator.accumulate`` + the 1/N loss scaling of
+                 hip_graph: Optional[bool] = None, use_8bit_adam: bool = False):
+        """``use_8bit_adam`` (the reference's --use_8bit_adam, diffusion/train_controlnet_genima.py:224, :1163-1175: AdamW8bit): the Adam
+        moments are 8-bit blockwise codes (csrc/optim8.hip), ~2.03 instead of 8 bytes of optimizer state per parameter; off: unchanged.
+        ``gradient_accumulation_steps``: micro-batches per optimizer step (``accelerator.accumulate`` + the 1/N loss scaling of
         ``accelerator.backward``, diffusion/train_controlnet_genima.py:1319, :1402); ``lr_lambda``: step -> multiplier of ``lr``
         (train_loop.get_scheduler = the reference's ``get_scheduler(args.lr_scheduler, ...)``, :1206-1213), advanced once per APPLIED
         optimizer step as accelerate's scheduler wrapper does (a step skipped by the GradScaler does not advance it)."""
@@ -788,7 +834,8 @@ class ControlNetTrainer:
         self._graphs: Dict[tuple, dict] = {}
         self._graph_seen: Dict[tuple, int] = {}
         self.unet = FrozenParams(E, unet_W)
-        self.cn = TrainParams(E, controlnet_sd)
+        self.use_8bit_adam = bool(use_8bit_adam)
+        self.cn = TrainParams(E, controlnet_sd, use_8bit_adam=self.use_8bit_adam)
         self.lr, self.betas, self.wd, self.eps, self.max_grad_norm = lr, betas, weight_decay, eps, max_grad_norm
         self.loss_scale, self.growth_interval, self._clean = float(loss_scale), growth_interval, 0
         self.opt_step = 0
@@ -918,12 +965,15 @@ class ControlNetTrainer:
         T.clip_coef(E, self._ss, self._clip, self.max_grad_norm, inv)
         self.opt_step += 1
         # one pass: AdamW on the fp32 master, the f16 working copy refreshed from the new values, the gradient cleared
-        T.adamw(E, cn.master, cn.grad, cn.exp_avg, cn.exp_avg_sq, self.current_lr(), self.betas[0], self.betas[1], self.eps, self.wd,
-                self.opt_step, self._clip, inv, half_out=cn.half, zero_grad=True)
+        cn.adamw(self.current_lr(), self.betas[0], self.betas[1], self.eps, self.wd, self.opt_step, self._clip, inv)
         if self._use_graph or os.environ.get("GN_MULTI_WT") == "0":
             cn._wt.clear()  # derived (transposed / rotated) weight copies are stale: rebuilt inside the captured graph
         else:
             cn.refresh_derived()  # ... and rebuilt here, in one launch
+
+    def optimizer_state_bytes(self) -> int:
+        """Bytes of device memory the optimizer's state occupies (the moments in either form; not master, gradient or working copy)."""
+        return sum(t.numel() * t.element_size() for t in self.cn.optimizer_state().values())
 
     def current_lr(self) -> float:
         return self.lr * (float(self.lr_lambda(self.sched_step)) if self.lr_lambda is not None else 1.0)
@@ -1037,24 +1087,37 @@ class ControlNetTrainer:
         from safetensors.torch import save_file
         d = os.path.join(output_dir, f"checkpoint-{global_step}")
         self.save_pretrained(os.path.join(d, self.trainable_subfolder))
-        save_file({"exp_avg": self.cn.exp_avg.cpu(), "exp_avg_sq": self.cn.exp_avg_sq.cpu(),
-                   "scalars": torch.tensor([self.opt_step, self.loss_scale, self._clean, global_step, self.sched_step], dtype=torch.float64)},
-                  os.path.join(d, "optimizer_flat.safetensors"))
+        st = {k: t.cpu() for k, t in self.cn.optimizer_state().items() if t.numel()}
+        st["scalars"] = torch.tensor([self.opt_step, self.loss_scale, self._clean, global_step, self.sched_step], dtype=torch.float64)
+        # the 8-bit state carries its kind in the file's metadata; the fp32 file is the one it always was
+        save_file(st, os.path.join(d, "optimizer_flat.safetensors"), metadata={"optimizer": self._optimizer_kind()} if self.use_8bit_adam else None)
         return d
+
+    def _optimizer_kind(self) -> str:
+        from . import optim8
+        return optim8.KIND if self.use_8bit_adam else "adamw"
 
     def load_state(self, checkpoint_dir: str) -> int:
         """Resume from ``save_state``'s directory.  Returns the global step it was written at."""
         import os
+        from safetensors import safe_open
         from safetensors.torch import load_file
         from . import weights
+        opt_path = os.path.join(checkpoint_dir, "optimizer_flat.safetensors")
+        with safe_open(opt_path, "pt") as f:
+            kind = (f.metadata() or {}).get("optimizer", "adamw")  # files written before the 8-bit optimizer existed carry no marker
+        if kind != self._optimizer_kind():
+            raise ValueError(f"{opt_path} holds {kind!r} optimizer state, this trainer runs {self._optimizer_kind()!r} "
+                             f"(use_8bit_adam={self.use_8bit_adam}): the kinds 'adamw' (fp32 moments) and 'adamw8bit' do not convert")
         _, sd = weights.load_diffusers_dir(os.path.join(checkpoint_dir, self.trainable_subfolder))
         sd = OrderedDict((k, sd[k]) for k in self._trainable_schema())  # safetensors files are key-sorted
-        fresh = TrainParams(self.E, sd)
+        fresh = TrainParams(self.E, sd, use_8bit_adam=self.use_8bit_adam)
         assert fresh.layout == self.cn.layout, "checkpoint does not match this network's configuration"
         self.cn.master.copy_(fresh.master)
-        st = load_file(os.path.join(checkpoint_dir, "optimizer_flat.safetensors"))
-        self.cn.exp_avg.copy_(st["exp_avg"])
-        self.cn.exp_avg_sq.copy_(st["exp_avg_sq"])
+        st = load_file(opt_path)
+        for k, t in self.cn.optimizer_state().items():
+            if t.numel():
+                t.copy_(st[k])
         sc = [float(v) for v in st["scalars"]]
         self.opt_step, self.loss_scale, self._clean, gstep = sc[:4]
         self.sched_step = int(sc[4]) if len(sc) > 4 else int(gstep)

@@ -565,6 +565,16 @@ int32_t gn_clip_coef(gn_ctx* ctx, const float* sumsq, float* clip, float max_nor
 int32_t gn_adamw_flat(gn_ctx* ctx, float* param, float* grad, float* m, float* v, int64_t n, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int32_t step, const float* clip_dev, float grad_scale,
                       void* half_out, int32_t zero_grad);
+/* 8-bit blockwise AdamW (the reference's --use_8bit_adam = bitsandbytes.optim.AdamW8bit; csrc/optim8.hip): gn_adamw_flat's update with both
+ * moments stored as one code byte per element + one f32 absmax per quantisation block, value = map[code] * absmax (m: map_signed, v:
+ * map_unsigned; 256 ascending f32 entries each, built by the host).  block_table: n_blocks rows of two int64 on the device, (element
+ * offset into param / grad / half_out, a multiple of 4; code offset * 512 + length, 1 <= length <= 256); block b owns m_absmax[b] /
+ * v_absmax[b].  A row that reaches outside [0, n) or [0, n_codes) is ignored.  Re-quantisation picks the NEAREST code, the lower index
+ * on a tie.  A skipped step (clip_dev[2] != 0) leaves codes and absmax untouched and still clears the gradient.  No workspace. */
+int32_t gn_adamw8_flat(gn_ctx* ctx, float* param, float* grad, int64_t n, void* m_codes, void* v_codes, int64_t n_codes, float* m_absmax,
+                       float* v_absmax, const int64_t* block_table, int32_t n_blocks, const float* map_signed, const float* map_unsigned,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* clip_dev,
+                       float grad_scale, void* half_out, int32_t zero_grad);
 /* VAE posterior sample of the train step (diffusion/train_controlnet_genima.py:1329-1332): moments [p, ld_moments] = (mean | logvar),
  * out[p, 0:C] = (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) * scale, out[p, C:ld_out] = 0 */
 int32_t gn_latent_sample(gn_ctx* ctx, const void* moments, const void* eps, void* out, int64_t pixels, int32_t C,

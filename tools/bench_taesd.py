@@ -36,6 +36,7 @@ def main():
     ap.add_argument("--resolution", type=int, default=512)
     ap.add_argument("--train", action="store_true", help="also time one SD-Turbo ControlNet train step, default VAE vs --tiny_vae")
     ap.add_argument("--train-steps", type=int, default=10)
+    ap.add_argument("--use_8bit_adam", action="store_true", help="the train step with 8-bit blockwise AdamW moments")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -72,14 +73,14 @@ def main():
               f"({fl / t_3 / 1e9:6.1f} TF/s) | {t_3 / t_f:5.2f}x", flush=True)
 
     if args.train:
-        res.update(train_steps(dev, R, args.block_batch, args.train_steps))
+        res.update(train_steps(dev, R, args.block_batch, args.train_steps, args.use_8bit_adam))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
 
 
-def train_steps(dev, R, B, steps):
+def train_steps(dev, R, B, steps, use_8bit_adam=False):
     """one SD-Turbo ControlNet train step (bench_train.py's synthetic set-up) with the default VAE and with --tiny_vae"""
     from genima_amd.packing import pack_state_dict
     from genima_amd.scheduler import DDPMScheduler
@@ -103,7 +104,8 @@ def train_steps(dev, R, B, steps):
     out = {}
     for tiny in (False, True):
         E = Engine(dev, autotune=True)
-        tr = ControlNetTrainer(E, fam["unet"], fam["controlnet"], unet_W, synth(schema.controlnet_schema(fam["controlnet"]), 2), lr=1e-5)
+        tr = ControlNetTrainer(E, fam["unet"], fam["controlnet"], unet_W, synth(schema.controlnet_schema(fam["controlnet"]), 2), lr=1e-5,
+                               use_8bit_adam=use_8bit_adam)
         tr.attach_frozen(vaes[tiny][0], vaes[tiny][1], fam["text"], text_W, DDPMScheduler(), seed=1234, tiny_vae=tiny)
         for _ in range(3):
             tr.train_step(batch)
