@@ -184,6 +184,7 @@ SIGNATURES = {
     "gn_image_u8_to_f16": (_I32, [_P, _P, _P, _I64, _I32, _F, _F]),
     "gn_image_f16_to_u8": (_I32, [_P, _P, _P, _I64, _I32]),
     "gn_image_normalize_u8": (_I32, [_P, _P, _P, _I64, _I32, _F, _F, _F, _F, _F, _F]),
+    "gn_gather_u8_to_f16": (_I32, [_P, _P, _P, _I32, _I64, _I32, _F, _F]),
     "gn_gather_rows": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_argmax_rows_i32": (_I32, [_P, _P, _P, _I32, _I32]),
     "gn_copy4d": (_I32, [_P, _P, _P, _P, _P, _P, _I32]),

@@ -66,6 +66,9 @@ __global__ void add_noise_kernel(const f16* __restrict__ x0, const f16* __restri
   out[idx] = (f16)(a[b] * (float)x0[idx] + c[b] * (float)noise[idx]);
 }
 
+// ToTensor + Normalize of one byte: the ONE expression both byte -> half kernels below evaluate (their outputs are compared bit for bit)
+__device__ __forceinline__ f16 u8_to_f16_value(uint8_t v, float mul, float add) { return (f16)((float)v / 255.0f * mul + add); }
+
 __global__ void image_u8_to_f16_kernel(const uint8_t* __restrict__ in, f16* __restrict__ out, long pixels, int Cpad, float mul,
                                        float add) {
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -74,8 +77,43 @@ __global__ void image_u8_to_f16_kernel(const uint8_t* __restrict__ in, f16* __re
 #pragma unroll
   for (int c = 0; c < 8; ++c) v[c] = (f16)0.0f;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) v[c] = (f16)((float)in[p * 3 + c] / 255.0f * mul + add);
+  for (int c = 0; c < 3; ++c) v[c] = u8_to_f16_value(in[p * 3 + c], mul, add);
   for (int c = 0; c < Cpad; ++c) out[p * Cpad + c] = v[c < 8 ? c : 7];
+}
+
+// image_u8_to_f16 over B frames that live anywhere on the device (the DataLoader's frame cache): blockIdx.y = frame, src[frame] = its
+// uint8 [pixels, 3] bytes.  A thread converts four pixels: 12 bytes in as three dwords (frames are 4-byte aligned; one that is not takes the
+// byte loads of the tail), and at Cpad == 8 one 16-byte store per pixel.  pixels % 4 leftovers go through the same per-pixel function.
+__device__ __forceinline__ void gather_store_pixel(f16* __restrict__ o, int Cpad, uint8_t r, uint8_t g, uint8_t b, float mul, float add) {
+  const f16 v0 = u8_to_f16_value(r, mul, add), v1 = u8_to_f16_value(g, mul, add), v2 = u8_to_f16_value(b, mul, add);
+  if (Cpad == 8) {
+    const f16 z = (f16)0.0f;
+    *reinterpret_cast<f16x8*>(o) = f16x8{v0, v1, v2, z, z, z, z, z};
+  } else {
+    o[0] = v0; o[1] = v1; o[2] = v2;
+    for (int c = 3; c < Cpad; ++c) o[c] = (f16)0.0f;
+  }
+}
+__global__ void gather_u8_to_f16_kernel(const uint8_t* const* __restrict__ src, f16* __restrict__ out, long pixels, int Cpad, float mul,
+                                        float add) {
+  typedef const __attribute__((address_space(1))) uint8_t* gptr;  // the frames are global memory: global_load, not flat_load
+  const gptr in = (gptr)src[blockIdx.y];
+  const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (p0 >= pixels) return;
+  f16* __restrict__ o = out + ((long)blockIdx.y * pixels + p0) * Cpad;
+  if (p0 + 4 <= pixels && ((uintptr_t)in & 3) == 0) {
+    const __attribute__((address_space(1))) uint32_t* w = (const __attribute__((address_space(1))) uint32_t*)(in + p0 * 3);
+    const uint32_t q[3] = {w[0], w[1], w[2]};
+    uint8_t by[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) by[i] = (uint8_t)(q[i >> 2] >> ((i & 3) * 8));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gather_store_pixel(o + j * Cpad, Cpad, by[j * 3], by[j * 3 + 1], by[j * 3 + 2], mul, add);
+  } else {
+    const int n = pixels - p0 < 4 ? (int)(pixels - p0) : 4;
+    for (int j = 0; j < n; ++j)
+      gather_store_pixel(o + j * Cpad, Cpad, in[(p0 + j) * 3], in[(p0 + j) * 3 + 1], in[(p0 + j) * 3 + 2], mul, add);
+  }
 }
 
 struct Norm3 { float m[3], a[3]; };
@@ -396,6 +434,14 @@ int32_t gn_add_noise(gn_ctx* ctx, const void* x0, const void* noise, const float
 int32_t gn_image_u8_to_f16(gn_ctx* ctx, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float mul, float add) {
   GN_REQUIRE(ctx && in && out && pixels > 0 && Cpad >= 3 && Cpad <= 8, "gn_image_u8_to_f16: bad arguments");
   hipLaunchKernelGGL(image_u8_to_f16_kernel, dim3(nblk(pixels)), dim3(256), 0, ctx->stream, in, (f16*)out, (long)pixels, Cpad, mul, add);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int32_t gn_gather_u8_to_f16(gn_ctx* ctx, const uint8_t* const* src, void* out, int32_t B, int64_t pixels, int32_t Cpad, float mul, float add) {
+  GN_REQUIRE(ctx && src && out && B > 0 && B <= 65535 && pixels > 0 && Cpad >= 3 && Cpad <= 8, "gn_gather_u8_to_f16: bad arguments");
+  GN_REQUIRE(Cpad != 8 || ((uintptr_t)out & 15) == 0, "gn_gather_u8_to_f16: out must be 16-byte aligned at Cpad == 8");
+  hipLaunchKernelGGL(gather_u8_to_f16_kernel, dim3(nblk(cdiv64(pixels, 4)), B), dim3(256), 0, ctx->stream, src, (f16*)out, (long)pixels, Cpad, mul, add);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

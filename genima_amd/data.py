@@ -11,6 +11,10 @@ quarter of the float32 NCHW volume over PCIe) and ``ToTensor`` / ``Normalize`` /
 per tensor (``gn_image_u8_to_f16``) -- the layout ``ControlNetTrainer.train_step`` consumes directly.  ``collate_fn`` keeps the
 reference's float NCHW contract for callers that want it (numpy; no torch compute).
 
+Opt-in frame cache (``DataLoader(cache="host" | "device")``): the reference trains 100-200 epochs over one small set of files, so a
+decoded frame is kept where the next epoch reads it -- in pinned host chunks, or in device chunks from which ``gn_gather_u8_to_f16``
+assembles the batch (``FrameCache``, ``to_device``).  The cache assumes the files do not change during a run.
+
 Reference quirks reproduced on purpose: the tiled caption is the truncated string
 ``"tiled perspectives of a robot "`` (the task description sits in a dangling f-string statement that is evaluated -- it advances
 numpy's global RNG through ``np.random.choice`` -- and discarded), and the tiled reader drops the last frame of every episode.
@@ -23,8 +27,9 @@ import pickle
 import random
 import re
 import threading
+from concurrent.futures import ThreadPoolExecutor
 from queue import Queue
-from typing import Dict, Iterator, List, Optional, Sequence
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -137,25 +142,194 @@ def collate_fn(examples: Sequence[Dict], tokenizer, resolution: int, proportion_
 
 def to_device(E, batch_u8: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """uint8 NHWC host batch -> what ``ControlNetTrainer.train_step`` takes: f16 NHWC 8-channel tensors on the device, ToTensor +
-    Normalize fused into the byte -> half conversion kernel (target: v / 255 * 2 - 1, conditioning: v / 255)."""
+    Normalize fused into the byte -> half conversion kernel (target: v / 255 * 2 - 1, conditioning: v / 255).  A device-cache batch
+    (``DataLoader(cache="device")``: ``frame_slots``) has its misses uploaded into their cache slots and is assembled by one
+    ``gn_gather_u8_to_f16`` launch per role, all on the caller's thread and the engine's current stream; the result is the same, bit for bit."""
     dev = E.device
+    if "frame_slots" in batch_u8:
+        return _to_device_cached(E, batch_u8)
     px = batch_u8["pixel_values_u8"].to(dev, non_blocking=True)
     cd = batch_u8["conditioning_pixel_values_u8"].to(dev, non_blocking=True)
     return {"pixel_values": E.image_u8_to_f16(px, 8, 2.0, -1.0), "conditioning_pixel_values": E.image_u8_to_f16(cd, 8, 1.0, 0.0),
             "input_ids": batch_u8["input_ids"].to(dev, non_blocking=True)}
 
 
+def _to_device_cached(E, batch) -> Dict[str, torch.Tensor]:
+    cache, R, slots = batch["frame_cache"], int(batch["resolution"]), batch["frame_slots"]
+    dev = E.device
+    cache.upload(dev, R, batch["frame_uploads"])
+    staging = batch["frame_staging_u8"]
+    if staging is not None:  # misses over the budget: this batch's own device copy, freed with the batch
+        staging = staging.to(dev, non_blocking=True)
+    fb = R * R * 3
+    addr = [staging.data_ptr() + i * fb if c < 0 else cache.address(R, c, i) for c, i in slots.tolist()]
+    ptrs = torch.tensor(addr, dtype=torch.int64)
+    if torch.cuda.is_available():
+        ptrs = ptrs.pin_memory()
+    ptrs = ptrs.to(dev, non_blocking=True)
+    B = len(addr) // 2  # rows 0..B-1: the targets, B..2B-1: the conditioning images
+    out = {"pixel_values": E.gather_u8_to_f16(ptrs[:B], (R, R), 8, 2.0, -1.0),
+           "conditioning_pixel_values": E.gather_u8_to_f16(ptrs[B:], (R, R), 8, 1.0, 0.0),
+           "input_ids": batch["input_ids"].to(dev, non_blocking=True)}
+    return out
+
+
+class FrameCache:
+    """Decoded training frames -- the uint8 HWC output of ``resize_center_crop_u8`` -- kept for the next epoch, keyed by
+    ``(path, resolution)``: a file used in both roles, or by two loaders that share the cache, is stored once.
+
+    Storage grows in fixed-size chunks of ``chunk_bytes`` (no single giant allocation): pinned host tensors for ``where="host"``, device
+    ``torch.uint8`` tensors for ``where="device"``.  ``cache_bytes`` is a budget, not a working-set size: frames are admitted in the order
+    they are first used until the chunks would exceed it; later frames are never admitted and nothing is evicted, so a frame that did not
+    get in is decoded on every use, exactly as without a cache.  (Eviction would buy nothing here: every epoch reads every frame once.)
+
+    The cache ASSUMES THAT THE FILES DO NOT CHANGE during a run: a frame is decoded once and never looked at again (no mtime or size
+    check); ``clear()`` after rewriting the data.  Memory: resolution^2 * 3 bytes per frame -- 786 432 at 512^2, so a task of 25 demos
+    (a few thousand frames) is 2-4 GB and eight tasks in two roles are in the order of 50 GB of the MI355X's 288 GB.
+
+    ``hits`` / ``misses`` count frame uses served from / not found in the cache, ``decodes`` the frames decoded through it."""
+
+    def __init__(self, where: str = "host", cache_bytes: int = 8 << 30, chunk_bytes: int = 256 << 20):
+        if where not in ("host", "device"):
+            raise ValueError(f"FrameCache(where={where!r}): 'host' or 'device'")
+        self.where, self.cache_bytes, self.chunk_bytes = where, int(cache_bytes), int(chunk_bytes)
+        self._lock = threading.Lock()
+        self.clear()
+
+    def clear(self):
+        """Forget every frame and free the chunks (batches still in flight must not be handed to ``to_device`` afterwards)."""
+        with self._lock:
+            self._index: Dict[Tuple[str, int], Tuple[int, int]] = {}  # (path, resolution) -> (chunk, frame in chunk)
+            self._caps: Dict[int, List[int]] = {}  # resolution -> frames per chunk (the last chunk is cut to the budget)
+            self._chunks: Dict[int, List[torch.Tensor]] = {}  # resolution -> [frames, R, R, 3] uint8 tensors (device: made in upload())
+            self._used: Dict[int, int] = {}  # resolution -> slots handed out so far
+            self._free: Dict[int, List[Tuple[int, int]]] = {}  # slots given back by a failed batch
+            self._pending: Dict[Tuple[int, int, int], torch.Tensor] = {}  # device cache: (resolution, chunk, frame) -> frame not uploaded yet
+            self._ready = None  # device cache: event after the last upload (a gather on another stream waits for it)
+            self._allocated = 0
+            self.hits = self.misses = self.decodes = 0
+
+    def __len__(self):
+        return len(self._index)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the frames held (the chunks' capacity, ``allocated_bytes``, is what the budget bounds: nbytes <= allocated_bytes <= cache_bytes)."""
+        with self._lock:
+            return sum(k[1] * k[1] * 3 for k in self._index)
+
+    @property
+    def allocated_bytes(self) -> int:
+        return self._allocated
+
+    # ---- producer side (the loader's thread) ----
+    def lookup(self, key):
+        """-> (slot, frame still waiting for its upload or None) of a cached frame, or None."""
+        with self._lock:
+            slot = self._index.get(key)
+            if slot is None:
+                self.misses += 1
+                return None
+            self.hits += 1
+            return slot, self._pending.get((key[1],) + slot)
+
+    def reserve(self, resolution: int) -> Optional[Tuple[int, int]]:
+        """A free slot for one frame, or None when the budget is spent."""
+        R, fb = resolution, resolution * resolution * 3
+        with self._lock:
+            if self._free.get(R):
+                return self._free[R].pop()
+            caps = self._caps.setdefault(R, [])
+            used = self._used.get(R, 0)
+            if used == sum(caps):
+                cap = min(max(1, self.chunk_bytes // fb), (self.cache_bytes - self._allocated) // fb)
+                if cap <= 0:
+                    return None
+                caps.append(cap)
+                self._allocated += cap * fb
+                if self.where == "host":
+                    self._chunks.setdefault(R, []).append(torch.empty((cap, R, R, 3), dtype=torch.uint8, pin_memory=torch.cuda.is_available()))
+            self._used[R] = used + 1
+            c = len(caps) - 1
+            return c, used - sum(caps[:c])
+
+    def release(self, resolution: int, slot):
+        with self._lock:
+            self._free.setdefault(resolution, []).append(slot)
+
+    def count_decodes(self, n: int):
+        with self._lock:
+            self.decodes += n
+
+    def commit(self, key, slot, frame: np.ndarray):
+        """The decoded ``frame`` now belongs to ``key``: copied into its host chunk, or (device cache) pinned and queued for the upload that
+        ``to_device`` does.  -> (slot, pending frame or None) as ``lookup``; another loader's slot if it got there first."""
+        R = key[1]
+        t = torch.from_numpy(frame)
+        with self._lock:
+            have = self._index.get(key)
+            if have is not None:
+                self._free.setdefault(R, []).append(slot)
+                return have, self._pending.get((R,) + have)
+            if self.where == "host":
+                self._chunks[R][slot[0]][slot[1]].copy_(t)
+                t = None
+            else:
+                t = t.pin_memory() if torch.cuda.is_available() else t
+                self._pending[(R,) + slot] = t
+            self._index[key] = slot
+            return slot, t
+
+    def frame(self, resolution: int, slot) -> torch.Tensor:
+        """Host cache: the stored frame (a view into its chunk)."""
+        return self._chunks[resolution][slot[0]][slot[1]]
+
+    # ---- consumer side (to_device: the caller's thread and current stream) ----
+    def upload(self, device, resolution: int, uploads):
+        """Device cache: make the chunks the loader has planned so far, and copy the frames of ``uploads`` (``(chunk, frame, pinned
+        tensor)``) that are still waiting into their slots.  A later gather on another stream is ordered behind the copies by an event."""
+        R = resolution
+        with self._lock:
+            chunks = self._chunks.setdefault(R, [])
+            for cap in self._caps.get(R, [])[len(chunks):]:
+                chunks.append(torch.empty((cap, R, R, 3), dtype=torch.uint8, device=device))
+            todo = [(c, i, self._pending.pop((R, c, i))) for c, i, _ in uploads if (R, c, i) in self._pending]
+        stream = torch.cuda.current_stream(device)
+        if self._ready is not None:
+            stream.wait_event(self._ready)
+        for c, i, t in todo:
+            chunks[c][i].copy_(t, non_blocking=True)
+        if todo:
+            self._ready = torch.cuda.Event()
+            self._ready.record(stream)
+
+    def address(self, resolution: int, chunk: int, frame: int) -> int:
+        return self._chunks[resolution][chunk].data_ptr() + frame * resolution * resolution * 3
+
+
 class DataLoader:
     """``torch.utils.data.DataLoader(train_dataset, shuffle=True, collate_fn=collate_fn, batch_size=, num_workers=)``
     (train_controlnet_genima.py:1187-1193) for the uint8 path: seeded shuffle per epoch, last partial batch kept, and a background
     thread that decodes / resizes ``prefetch`` batches ahead so PNG decoding overlaps the device step (the reference's default
-    ``num_workers=0`` decodes inline and can starve 8 GPUs)."""
+    ``num_workers=0`` decodes inline and can starve 8 GPUs).
+
+    ``decode_workers`` > 1 (at most 16) fans the image decodes of a batch out over a thread pool, in order; captions are still tokenized
+    on the one producer thread, in batch order, so python's ``random`` draws as before.  ``cache`` = "host" | "device" (or a
+    ``FrameCache`` to share) keeps decoded frames for the following epochs within ``cache_bytes``: "host" yields the same batches as no
+    cache, "device" yields batches that name cache slots (``frame_slots``) for ``to_device`` / ``train_step`` to gather on the device.  The
+    producer thread launches no device work.  The cache assumes the files do not change during a run (``FrameCache``)."""
+
+    MAX_DECODE_WORKERS = 16  # a fixed cap, never the machine's CPU count: a training host runs one loader per GPU
 
     def __init__(self, dataset, batch_size: int, tokenizer, resolution: int, shuffle: bool = True, seed: int = 0, prefetch: int = 2,
-                 proportion_empty_prompts: float = 0.0, rank: int = 0, world: int = 1):
+                 proportion_empty_prompts: float = 0.0, rank: int = 0, world: int = 1, cache=None, cache_bytes: int = 8 << 30,
+                 decode_workers: int = 1):
         self.ds, self.bs, self.tok, self.res = dataset, batch_size, tokenizer, resolution
         self.shuffle, self.seed, self.prefetch, self.pep = shuffle, seed, max(0, prefetch), proportion_empty_prompts
         self.rank, self.world, self.epoch = rank, world, 0
+        self.cache = FrameCache(cache, cache_bytes) if isinstance(cache, str) else cache
+        self.decode_workers = max(1, min(int(decode_workers), self.MAX_DECODE_WORKERS))
+        self._pool = ThreadPoolExecutor(self.decode_workers, thread_name_prefix="genima-decode") if self.decode_workers > 1 else None
 
     def __len__(self):
         n_batches = (len(self.ds) + self.bs - 1) // self.bs
@@ -175,12 +349,87 @@ class DataLoader:
         batches = [idx[i:i + self.bs] for i in range(0, len(idx), self.bs)]
         return batches[self.rank::self.world]
 
+    # ---- the cached / fanned-out batch (cache=None, decode_workers=1 stays collate_u8) ----
+    def _sources(self, i: int):
+        """-> (caption, [(path or None, payload or None)] for the target and the conditioning image).  A dataset that indexes paths
+        (``RLBenchDataset.examples``) is not read here: a cache hit then touches no file, and a miss reads its file in the decode worker."""
+        ex = getattr(self.ds, "examples", None)
+        if ex is not None and isinstance(ex[i].get("image"), str):
+            return ex[i]["text"], [(ex[i][k], None) for k in ("image", "conditioning_image")]
+        e = self.ds[i]
+        return e["text"], [(v.get("path") if isinstance(v, dict) else None, v) for v in (e["image"], e["conditioning_image"])]
+
+    def _decode(self, job) -> np.ndarray:
+        path, payload = job
+        if payload is None:
+            with open(path, "rb") as f:
+                payload = f.read()
+        return np.require(resize_center_crop_u8(payload, self.res), requirements="W")  # PIL's array is read-only; torch wants to own it
+
+    def _decode_all(self, jobs) -> List[np.ndarray]:
+        return list(self._pool.map(self._decode, jobs)) if self._pool is not None and len(jobs) > 1 else [self._decode(j) for j in jobs]
+
+    def _make(self, ix: List[int]) -> Dict[str, object]:
+        R, cache = self.res, self.cache
+        meta = [self._sources(i) for i in ix]
+        uses = [m[1][role] for role in (0, 1) for m in meta]  # the order collate_u8 decodes in: every target, then every conditioning image
+        # plan: per use a cached frame (hit) or a decode job; a frame admitted by this batch is decoded once however often the batch
+        # names it (both roles, the data-parallel tail's wrap-around), one that is over the budget is decoded per use, as without a cache
+        plan, jobs, keys, slots, fresh = [], [], [], [], {}
+        for path, payload in uses:
+            key = (path, R) if cache is not None and path is not None else None
+            got = cache.lookup(key) if key is not None else None
+            if got is None and key in fresh:
+                got = ("job", fresh[key])
+            elif got is None:
+                slot = cache.reserve(R) if key is not None else None
+                if slot is not None:
+                    fresh[key] = len(jobs)
+                got = ("job", len(jobs))
+                jobs.append((path, payload)), keys.append(key if slot is not None else None), slots.append(slot)
+            plan.append(got)
+        try:
+            frames = self._decode_all(jobs)
+        except BaseException:
+            for slot in slots:
+                if slot is not None:
+                    cache.release(R, slot)
+            raise
+        if cache is not None:
+            cache.count_decodes(len(jobs))
+        done = [cache.commit(k, s, f) if k is not None else None for k, s, f in zip(keys, slots, frames)]  # per job: (slot, pending) | None
+        plan = [(done[g[1]] or ("frame", frames[g[1]])) if g[0] == "job" else g for g in plan]
+        ids = tokenize_captions([m[0] for m in meta], self.tok, self.pep)
+        pin = torch.cuda.is_available()
+        if cache is not None and cache.where == "device":
+            uploads, staging, where = {}, [], []
+            for g in plan:
+                if g[0] == "frame":  # over the budget: a staging slot of this batch
+                    where.append((-1, len(staging)))
+                    staging.append(torch.from_numpy(g[1]))
+                else:
+                    where.append(g[0])
+                    if g[1] is not None:
+                        uploads[g[0]] = g[1]
+            stage = torch.stack(staging) if staging else None
+            return {"frame_cache": cache, "resolution": R, "frame_slots": torch.tensor(where, dtype=torch.int64).view(-1, 2),
+                    "frame_uploads": [(c, i, t) for (c, i), t in uploads.items()],
+                    "frame_staging_u8": stage.pin_memory() if pin and stage is not None else stage,
+                    "input_ids": ids.pin_memory() if pin else ids}
+        B = len(ix)
+        out = torch.empty((2 * B, R, R, 3), dtype=torch.uint8, pin_memory=pin)
+        for o, g in zip(out, plan):
+            o.copy_(torch.from_numpy(g[1]) if g[0] == "frame" else cache.frame(R, g[0]))
+        return {"pixel_values_u8": out[:B], "conditioning_pixel_values_u8": out[B:], "input_ids": ids.pin_memory() if pin else ids}
+
     def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
         batches = self._batches()
         self.epoch += 1
 
         def make(ix):
-            return collate_u8([self.ds[i] for i in ix], self.tok, self.res, self.pep)
+            if self.cache is None and self._pool is None:
+                return collate_u8([self.ds[i] for i in ix], self.tok, self.res, self.pep)
+            return self._make(ix)
 
         if self.prefetch == 0:
             for ix in batches:

@@ -1178,6 +1178,18 @@ class Engine:
         self._small("image_u8_to_f16", (img, out), _ptr(img), _ptr(out), img.numel() // 3, cpad, float(mul), float(add))
         return out
 
+    def gather_u8_to_f16(self, ptrs: torch.Tensor, frame_shape, cpad: int = 8, mul: float = 1.0, add: float = 0.0):
+        """``image_u8_to_f16`` over frames that lie anywhere on the device: ``ptrs`` is a DEVICE int64 [B] tensor of the addresses of uint8
+        [H, W, 3] frames (4-byte aligned, repeats allowed) -> f16 [B, H, W, cpad], one launch.  Eager engines only (a recorded program would
+        replay the addresses of one batch)."""
+        if self.record:
+            raise RuntimeError("gather_u8_to_f16 is an eager op: the frame addresses change from batch to batch")
+        assert ptrs.is_cuda and ptrs.dtype == torch.int64 and ptrs.dim() == 1 and ptrs.is_contiguous()
+        H, W = int(frame_shape[0]), int(frame_shape[1])
+        out = torch.empty((ptrs.numel(), H, W, cpad), dtype=F16, device=self.device)
+        check(self.lib.gn_gather_u8_to_f16(self._ctx, _ptr(ptrs), _ptr(out), ptrs.numel(), H * W, cpad, float(mul), float(add)), "gn_gather_u8_to_f16")
+        return out
+
     def image_f16_to_u8(self, x: torch.Tensor, *, out=None, name=None):
         """f16 [B, H, W, ld>=3] -> uint8 [B, H, W, 3] (VaeImageProcessor.postprocess numerics)."""
         if out is None:

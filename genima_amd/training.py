@@ -1155,7 +1155,8 @@ class ControlNetTrainer:
     def train_step(self, batch) -> torch.Tensor:
         """batch: ``pixel_values`` (NCHW in [-1, 1], or NHWC f16 8-channel), ``conditioning_pixel_values`` (same, in [0, 1]),
         ``input_ids`` [b, 77] -- the collate_fn output of diffusion/train_controlnet_genima.py:934-964 -- or the uint8 batch of
-        data.collate_u8 (``pixel_values_u8`` / ``conditioning_pixel_values_u8``).  Returns the device loss."""
+        data.collate_u8 (``pixel_values_u8`` / ``conditioning_pixel_values_u8``), or the device-cache batch of ``data.DataLoader(cache="device")``
+        (``frame_slots``).  Returns the device loss."""
         E, dev = self.E, self.E.device
         # The front of the step -- upload, augmentation, VAE encode, noise draws, text tower(s): frozen networks and fresh inputs only -- runs
         # on its own stream: with the scaler's read-back deferred (update_scale_async) the host gets here while the previous step's
@@ -1220,7 +1221,7 @@ class ControlNetTrainer:
 
     def _front(self, batch):
         E, dev = self.E, self.E.device
-        if "pixel_values_u8" in batch:  # the uint8 NHWC host batch of genima_amd/data.py: ToTensor + Normalize happen on the device
+        if "pixel_values_u8" in batch or "frame_slots" in batch:  # the uint8 NHWC host batch of genima_amd/data.py, or its device frame cache's: ToTensor + Normalize happen on the device
             from .data import to_device
             batch = to_device(E, batch)
         x8 = self._nhwc8(batch["pixel_values"])

@@ -428,6 +428,10 @@ int32_t gn_add_noise(gn_ctx* ctx, const void* x0, const void* noise, const float
  * gn_image_f16_to_u8: f16 [pixels, ld] -> uint8 [pixels, 3]: round(clamp(v/2+0.5, 0, 1)*255)  (postprocess, Appendix D.6) */
 int32_t gn_image_u8_to_f16(gn_ctx* ctx, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float mul, float add);
 int32_t gn_image_f16_to_u8(gn_ctx* ctx, const void* in, uint8_t* out, int64_t pixels, int32_t ld);
+/* The same conversion over B frames that lie anywhere on the device (the DataLoader's frame cache, genima_amd/data.py):
+ * out[b, p, :] = frame src[b] pixel p: v / 255 * mul + add in channels 0..2, zeros up to Cpad (as gn_image_u8_to_f16, bit for bit).
+ * src: DEVICE array of B device pointers to uint8 [pixels, 3] frames (4-byte aligned; pointers may repeat). */
+int32_t gn_gather_u8_to_f16(gn_ctx* ctx, const uint8_t* const* src, void* out, int32_t B, int64_t pixels, int32_t Cpad, float mul, float add);
 /* ACT image path (controller/method/genima_act.py:146-148, :188): uint8 [pixels, 3] -> f16 [pixels, Cpad]: v * m_c + a_c
  * (m_c = 1/(255 std_c), a_c = -mean_c/std_c; channels >= 3 zero) */
 int32_t gn_image_normalize_u8(gn_ctx* ctx, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float m0, float m1,
