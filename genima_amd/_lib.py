@@ -131,6 +131,14 @@ class WgradDesc(C.Structure):
     ]
 
 
+class RenderDesc(C.Structure):
+    """gn_render_desc: one batch of sphere renders + composites (gn_render_spheres)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("cams", "spheres", "tex_index", "count", "atlas", "bg", "bg2", "blend", "tile_index", "bg_frames", "full", "rnd",
+                                           "occupied", "full_f16", "rnd_f16")]
+                + [(n, C.c_int32) for n in ("B", "S", "H", "W", "T", "th", "tw", "samples", "bg_tiled", "n_tiled")]
+                + [(n, C.c_float) for n in ("full_mul", "full_add", "rnd_mul", "rnd_add")])
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/genima_hip.h declares (tests/test_abi.py checks the two agree)
@@ -235,6 +243,7 @@ SIGNATURES = {
     "gn_reflect_pad_crop": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_gaussian_blur": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "gn_affine_nearest": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "gn_render_spheres": (_I32, [_P, C.POINTER(RenderDesc)]),
     "gn_latent_sample":(_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _F]),
     "gn_ema_flat": (_I32, [_P, _P, _P, _I64, _F]),
     "gn_cast_f32_f16": (_I32, [_P, _P, _P, _I64]),

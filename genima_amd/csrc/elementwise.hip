@@ -3,6 +3,7 @@
 // All f16 storage / f32 math, 16-byte accesses where the layout allows.
 #include "common.h"
 #include "gn_bridge.h"
+#include "image_convert.h"
 
 namespace {
 
@@ -66,8 +67,7 @@ __global__ void add_noise_kernel(const f16* __restrict__ x0, const f16* __restri
   out[idx] = (f16)(a[b] * (float)x0[idx] + c[b] * (float)noise[idx]);
 }
 
-// ToTensor + Normalize of one byte: the ONE expression both byte -> half kernels below evaluate (their outputs are compared bit for bit)
-__device__ __forceinline__ f16 u8_to_f16_value(uint8_t v, float mul, float add) { return (f16)((float)v / 255.0f * mul + add); }
+// u8_to_f16_value (image_convert.h): the ONE expression both byte -> half kernels below evaluate (their outputs are compared bit for bit)
 
 __global__ void image_u8_to_f16_kernel(const uint8_t* __restrict__ in, f16* __restrict__ out, long pixels, int Cpad, float mul,
                                        float add) {

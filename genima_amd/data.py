@@ -146,6 +146,8 @@ def to_device(E, batch_u8: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     (``DataLoader(cache="device")``: ``frame_slots``) has its misses uploaded into their cache slots and is assembled by one
     ``gn_gather_u8_to_f16`` launch per role, all on the caller's thread and the engine's current stream; the result is the same, bit for bit."""
     dev = E.device
+    if "render_views" in batch_u8:
+        return _to_device_rendered(E, batch_u8)
     if "frame_slots" in batch_u8:
         return _to_device_cached(E, batch_u8)
     px = batch_u8["pixel_values_u8"].to(dev, non_blocking=True)
@@ -172,6 +174,33 @@ def _to_device_cached(E, batch) -> Dict[str, torch.Tensor]:
            "conditioning_pixel_values": E.gather_u8_to_f16(ptrs[B:], (R, R), 8, 1.0, 0.0),
            "input_ids": batch["input_ids"].to(dev, non_blocking=True)}
     return out
+
+
+def _to_device_rendered(E, batch) -> Dict[str, torch.Tensor]:
+    """A ``DataLoader(render_targets=...)`` batch: the conditioning frames (uploaded, or where they lie in the device cache, through the
+    same pointer table ``gn_gather_u8_to_f16`` reads) are the tiled backgrounds over which ``gn_render_spheres`` draws the targets,
+    straight into the f16 NHWC-8 ``pixel_values``.  The view arrays were packed and pinned by the producer thread."""
+    dev, src = E.device, batch["render_source"]
+    views = [batch["render_views"][k].to(dev, non_blocking=True) for k in ("cams", "spheres", "tex_index", "count")]
+    if "frame_slots" in batch:
+        cache, R = batch["frame_cache"], int(batch["resolution"])
+        cache.upload(dev, R, batch["frame_uploads"])
+        staging = batch["frame_staging_u8"]
+        if staging is not None:
+            staging = staging.to(dev, non_blocking=True)
+        fb = R * R * 3
+        ptrs = torch.tensor([staging.data_ptr() + i * fb if c < 0 else cache.address(R, c, i) for c, i in batch["frame_slots"].tolist()],
+                            dtype=torch.int64)
+        ptrs = (ptrs.pin_memory() if torch.cuda.is_available() else ptrs).to(dev, non_blocking=True)
+        B, bg = ptrs.numel(), dict(bg_frames=ptrs)
+        cond = E.gather_u8_to_f16(ptrs, (R, R), 8, 1.0, 0.0)
+    else:
+        cd = batch["conditioning_pixel_values_u8"].to(dev, non_blocking=True)
+        B, bg = cd.shape[0], dict(bg=cd)
+        cond = E.image_u8_to_f16(cd, 8, 1.0, 0.0)
+    px = torch.empty((B, 2 * src.H, 2 * src.W, 8), dtype=torch.float16, device=dev)
+    E.render_spheres(*views, src.atlas_on(dev), src.H, src.W, src.samples, bg_tiled=True, n_tiled=B, full_f16=px, full_scale=(2.0, -1.0), **bg)
+    return {"pixel_values": px, "conditioning_pixel_values": cond, "input_ids": batch["input_ids"].to(dev, non_blocking=True)}
 
 
 class FrameCache:
@@ -317,14 +346,22 @@ class DataLoader:
     on the one producer thread, in batch order, so python's ``random`` draws as before.  ``cache`` = "host" | "device" (or a
     ``FrameCache`` to share) keeps decoded frames for the following epochs within ``cache_bytes``: "host" yields the same batches as no
     cache, "device" yields batches that name cache slots (``frame_slots``) for ``to_device`` / ``train_step`` to gather on the device.  The
-    producer thread launches no device work.  The cache assumes the files do not change during a run (``FrameCache``)."""
+    producer thread launches no device work.  The cache assumes the files do not change during a run (``FrameCache``).
+
+    ``render_targets`` (a ``render.TrajectorySource``; off by default): the target image of a sample is not read from its PNG but drawn on
+    the device -- the trajectory's spheres over the sample's conditioning frame (``gn_render_spheres``, in ``to_device`` / ``train_step``) --
+    so only the conditioning frames are decoded, and cached when ``cache`` is on.  For datasets whose targets are the rendering of their own
+    conditioning frame (the tiled ``tiled_rgb`` / ``tiled_rgb_rendered`` pair without ``predict_future``)."""
 
     MAX_DECODE_WORKERS = 16  # a fixed cap, never the machine's CPU count: a training host runs one loader per GPU
 
     def __init__(self, dataset, batch_size: int, tokenizer, resolution: int, shuffle: bool = True, seed: int = 0, prefetch: int = 2,
                  proportion_empty_prompts: float = 0.0, rank: int = 0, world: int = 1, cache=None, cache_bytes: int = 8 << 30,
-                 decode_workers: int = 1):
+                 decode_workers: int = 1, render_targets=None):
         self.ds, self.bs, self.tok, self.res = dataset, batch_size, tokenizer, resolution
+        self.render_targets = render_targets
+        if render_targets is not None and (resolution != 2 * render_targets.H or resolution != 2 * render_targets.W):
+            raise ValueError(f"render_targets draws {2 * render_targets.H} x {2 * render_targets.W} tiled targets: resolution must be that, not {resolution}")
         self.shuffle, self.seed, self.prefetch, self.pep = shuffle, seed, max(0, prefetch), proportion_empty_prompts
         self.rank, self.world, self.epoch = rank, world, 0
         self.cache = FrameCache(cache, cache_bytes) if isinstance(cache, str) else cache
@@ -373,6 +410,16 @@ class DataLoader:
         R, cache = self.res, self.cache
         meta = [self._sources(i) for i in ix]
         uses = [m[1][role] for role in (0, 1) for m in meta]  # the order collate_u8 decodes in: every target, then every conditioning image
+        rendered = None
+        if self.render_targets is not None:  # the targets are drawn on the device from the conditioning frames: those alone are decoded
+            uses = uses[len(meta):]
+            packed = [v for path, _ in uses for v in self.render_targets.views(path)]
+            rendered = {"cams": torch.from_numpy(np.stack([v[0] for v in packed])), "spheres": torch.from_numpy(np.stack([v[1] for v in packed])),
+                        "tex_index": torch.from_numpy(np.stack([v[2] for v in packed]).astype(np.int32)),
+                        "count": torch.tensor([v[3] for v in packed], dtype=torch.int32)}
+            if torch.cuda.is_available():
+                rendered = {k: v.pin_memory() for k, v in rendered.items()}
+            rendered = {"render_views": rendered, "render_source": self.render_targets}
         # plan: per use a cached frame (hit) or a decode job; a frame admitted by this batch is decoded once however often the batch
         # names it (both roles, the data-parallel tail's wrap-around), one that is over the budget is decoded per use, as without a cache
         plan, jobs, keys, slots, fresh = [], [], [], [], {}
@@ -412,14 +459,16 @@ class DataLoader:
                     if g[1] is not None:
                         uploads[g[0]] = g[1]
             stage = torch.stack(staging) if staging else None
-            return {"frame_cache": cache, "resolution": R, "frame_slots": torch.tensor(where, dtype=torch.int64).view(-1, 2),
+            return {**(rendered or {}), "frame_cache": cache, "resolution": R, "frame_slots": torch.tensor(where, dtype=torch.int64).view(-1, 2),
                     "frame_uploads": [(c, i, t) for (c, i), t in uploads.items()],
                     "frame_staging_u8": stage.pin_memory() if pin and stage is not None else stage,
                     "input_ids": ids.pin_memory() if pin else ids}
         B = len(ix)
-        out = torch.empty((2 * B, R, R, 3), dtype=torch.uint8, pin_memory=pin)
+        out = torch.empty((len(plan), R, R, 3), dtype=torch.uint8, pin_memory=pin)
         for o, g in zip(out, plan):
             o.copy_(torch.from_numpy(g[1]) if g[0] == "frame" else cache.frame(R, g[0]))
+        if rendered is not None:
+            return {**rendered, "conditioning_pixel_values_u8": out, "input_ids": ids.pin_memory() if pin else ids}
         return {"pixel_values_u8": out[:B], "conditioning_pixel_values_u8": out[B:], "input_ids": ids.pin_memory() if pin else ids}
 
     def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
@@ -427,7 +476,7 @@ class DataLoader:
         self.epoch += 1
 
         def make(ix):
-            if self.cache is None and self._pool is None:
+            if self.cache is None and self._pool is None and self.render_targets is None:
                 return collate_u8([self.ds[i] for i in ix], self.tok, self.res, self.pep)
             return self._make(ix)
 

@@ -1190,6 +1190,31 @@ class Engine:
         check(self.lib.gn_gather_u8_to_f16(self._ctx, _ptr(ptrs), _ptr(out), ptrs.numel(), H * W, cpad, float(mul), float(add)), "gn_gather_u8_to_f16")
         return out
 
+    def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
+                       tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
+                       rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):
+        """``gn_render_spheres`` over device tensors (genima_amd/render.py builds them): cams f32 [B, 18], spheres f32 [B, S, 16], tex_index
+        int32 [B, S], count int32 [B], atlas uint8 [T, th, tw, 4], blend f64 [B], bg_frames int64 [n_tiled] (addresses of tiled uint8 frames, instead of bg); the outputs that are given are written.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("render_spheres is an eager op: the poses change from batch to batch")
+        B, S = int(spheres.shape[0]), int(spheres.shape[1])
+        for t, dt, shape in ((cams, torch.float32, (B, 18)), (spheres, torch.float32, (B, S, 16)), (tex_index, torch.int32, (B, S)),
+                             (count, torch.int32, (B,)), (atlas, torch.uint8, None), (blend, torch.float64, (B,)), (tile_index, torch.int32, (B,)),
+                             (bg_frames, torch.int64, (n_tiled,))):
+            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and (shape is None or tuple(t.shape) == shape)), (dt, shape)
+        assert atlas.dim() == 4 and atlas.shape[3] == 4
+        flat, tiled = (B, H, W, 3), (n_tiled, 2 * H, 2 * W)
+        for t, dt, shape in ((bg, torch.uint8, tiled + (3,) if bg_tiled else flat), (bg2, torch.uint8, tiled + (3,) if bg_tiled else flat),
+                             (full, torch.uint8, flat), (rnd, torch.uint8, flat), (occupied, torch.uint8, (B, H, W)),
+                             (full_f16, F16, tiled + (8,)), (rnd_f16, F16, tiled + (8,))):
+            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape), (dt, shape)
+        d = _lib.RenderDesc(cams=_ptr(cams), spheres=_ptr(spheres), tex_index=_ptr(tex_index), count=_ptr(count), atlas=_ptr(atlas), bg=_ptr(bg),
+                            bg2=_ptr(bg2), blend=_ptr(blend), tile_index=_ptr(tile_index), bg_frames=_ptr(bg_frames), full=_ptr(full), rnd=_ptr(rnd), occupied=_ptr(occupied),
+                            full_f16=_ptr(full_f16), rnd_f16=_ptr(rnd_f16), B=B, S=S, H=int(H), W=int(W), T=int(atlas.shape[0]),
+                            th=int(atlas.shape[1]), tw=int(atlas.shape[2]), samples=int(samples), bg_tiled=int(bool(bg_tiled)), n_tiled=int(n_tiled),
+                            full_mul=float(full_scale[0]), full_add=float(full_scale[1]), rnd_mul=float(rnd_scale[0]), rnd_add=float(rnd_scale[1]))
+        check(self.lib.gn_render_spheres(self._ctx, C.byref(d)), "gn_render_spheres")
+
     def image_f16_to_u8(self, x: torch.Tensor, *, out=None, name=None):
         """f16 [B, H, W, ld>=3] -> uint8 [B, H, W, 3] (VaeImageProcessor.postprocess numerics)."""
         if out is None:

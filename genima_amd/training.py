@@ -1221,7 +1221,7 @@ class ControlNetTrainer:
 
     def _front(self, batch):
         E, dev = self.E, self.E.device
-        if "pixel_values_u8" in batch or "frame_slots" in batch:  # the uint8 NHWC host batch of genima_amd/data.py, or its device frame cache's: ToTensor + Normalize happen on the device
+        if "pixel_values_u8" in batch or "frame_slots" in batch or "render_views" in batch:  # the uint8 NHWC host batch of genima_amd/data.py, or its device frame cache's: ToTensor + Normalize happen on the device
             from .data import to_device
             batch = to_device(E, batch)
         x8 = self._nhwc8(batch["pixel_values"])

@@ -609,6 +609,48 @@ int32_t gn_gaussian_blur(gn_ctx* ctx, const void* x, void* out, int32_t B, int32
                          const float* taps);
 int32_t gn_affine_nearest(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C, const float* theta);
 
+/* ---- dataset generation: the joint-action spheres (render/joint_marker.py:86-181 -- pyrender's flat-shaded textured uv_spheres on an
+ * OpenGL context -- and the composite of render/render_data.py:282-307), ray-cast and composited in one launch per batch of views.
+ * All pointers are device memory.  Per view b < B:
+ *   cams[b]        18 f32: fx fy cx cy | camera-to-world pose 3x4 row-major, already in the OpenGL convention (-z forward, y up:
+ *                  joint_marker.py:101-118 applied by the caller) | znear zfar
+ *   spheres[b][s]  16 f32, s < S <= 8: world pose 3x4 row-major | radius | base colour factor r g b;  count[b] <= S of them are drawn
+ *   tex_index[b][s] layer of atlas uint8 [T, th, tw, 4] (RGBA, row 0 = the image's top row)
+ * Sample (u, v) in pixel (x, y): samples = 1: the centre; samples = 4: (x, y) + (.375, .125), (.875, .375), (.125, .625), (.625, .875).
+ * Ray from the camera origin along pose * (dx, dy, -1), dx = (u - cx) / fx, dy = (cy - v) / fy (signed fx, fy).  Hit: the nearest front
+ * intersection whose eye depth lies in [znear, zfar]; p = Rs^T (hit - centre); uv = (p.xy / radius + 1) / 2 with v = 0 at the texture's
+ * BOTTOM row; bilinear fetch on texel centres, repeat wrap; sample colour = factor * texel / 255 in f32, white on a miss; pixel =
+ * round-to-nearest(255 * mean of the samples).  white = all three channels 255 (the reference keys on the colour):
+ *   full     uint8 [B, H, W, 3] = white ? bg : pixel
+ *   rnd      uint8 [B, H, W, 3] = white ? bg2 : trunc(pixel * blend[b] + bg2 * (1 - blend[b]))  (f64, unfused, as numpy computes it)
+ *   occupied uint8 [B, H, W]    = !white
+ *   full_f16 / rnd_f16: the same two images as f16 NHWC-8 [n_tiled, 2H, 2W, 8] in the 2x2 camera tiling (genima_amd/tiling.py): view b is
+ *            tile t = tile_index ? tile_index[b] : b -- image t / 4, tile row (t % 4) / 2, tile column t % 2; a view whose t is outside
+ *            [0, 4 n_tiled) writes nothing -- each byte converted as gn_image_u8_to_f16 does (v / 255 * mul + add, channels 3..7 zero).
+ * Every output may be NULL.  bg (needed by full*) and bg2 + blend (needed by rnd*) are uint8 [B, H, W, 3], or, with bg_tiled != 0, the
+ * tiled uint8 [n_tiled, 2H, 2W, 3] frames addressed like the f16 outputs; bg_frames (with bg_tiled, instead of bg): a DEVICE array of n_tiled
+ * device pointers to such tiled frames lying anywhere (the DataLoader's frame cache, as gn_gather_u8_to_f16's src). */
+typedef struct gn_render_desc {
+  const float* cams;
+  const float* spheres;
+  const int32_t* tex_index;
+  const int32_t* count;
+  const uint8_t* atlas;
+  const uint8_t* bg;
+  const uint8_t* bg2;
+  const double* blend;
+  const int32_t* tile_index;
+  const uint8_t* const* bg_frames;
+  uint8_t* full;
+  uint8_t* rnd;
+  uint8_t* occupied;
+  void* full_f16;
+  void* rnd_f16;
+  int32_t B, S, H, W, T, th, tw, samples, bg_tiled, n_tiled;
+  float full_mul, full_add, rnd_mul, rnd_add;
+} gn_render_desc;
+int32_t gn_render_spheres(gn_ctx* ctx, const gn_render_desc* d);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */

@@ -5,13 +5,15 @@
   * ms per batch of ``to_device`` (upload / gather + conversion, synchronised) for the uncached and the device-cached batch;
   * us of ``gn_gather_u8_to_f16`` and ``gn_image_u8_to_f16`` at B x resolution^2 (device events);
   * ms per loader-fed ``train_step`` of the SD-Turbo family for ``cache=None`` against ``cache="device"`` from epoch 2 on, and per step on one
-    resident synthetic batch (what bench_train.py times), all three alternating in one process.
+    resident synthetic batch (what bench_train.py times), all three alternating in one process; with ``--render-textures DIR`` also, in the
+    same alternation, ``cache="device"`` on a tree that ``render_episode`` wrote against the same loader with ``render_targets`` (targets
+    drawn on the device instead of read).
 
 The frames are generated (smooth structure + sensor noise, ~400 KB per 512^2 PNG); real renders compress better and decode faster.  Every
 setting is timed ``--rounds`` times, alternating, after a warm-up epoch; the spread over the rounds is printed beside the median.  Needs an
 MI355X.
 
-    python tools/bench_loader.py [--batch 8] [--resolution 512] [--examples 64] [--rounds 3] [--no-train] [--out bench_loader.json]
+    python tools/bench_loader.py [--batch 8] [--resolution 512] [--examples 64] [--rounds 3] [--no-train] [--render-textures DIR] [--out bench_loader.json]
 """
 import argparse
 import json
@@ -27,6 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from genima_amd import data as D  # noqa: E402
+from genima_amd import render as Rn  # noqa: E402
 
 
 def write_tree(root, n_examples, R):
@@ -53,6 +56,20 @@ def write_tree(root, n_examples, R):
     return D.RLBenchDataset(root, tasks="bench_task", num_demos=2)
 
 
+def write_rendered_tree(root, n_examples, R, texture_dir, E):
+    """Two generated episodes (``render.synthetic_episode``) rendered by ``render_episode``: ``n_examples`` tiled examples whose targets
+    are the spheres drawn over their conditioning frames, with the ``traj.npz`` a ``render_targets`` loader draws them from."""
+    assert R == 512, "the rendered tree is the 2x2 tiling of 256^2 views"
+    base = os.path.join(root, "bench_task", "variation0")
+    per_ep = n_examples // 2 + 2  # L steps -> L - 1 tiled frames, of which the reader drops the last
+    for e in range(2):
+        cfg, traj, frames = Rn.synthetic_episode(per_ep, seed=e, texture_dir=texture_dir, action_horizon=20)
+        Rn.render_episode(traj, frames, os.path.join(base, "episodes", f"episode{e}"), cfg, engine=E)
+    with open(os.path.join(base, "variation_descriptions.pkl"), "wb") as f:
+        pickle.dump(["bench"], f)
+    return D.RLBenchDataset(root, tasks="bench_task", num_demos=2, image_type="tiled_rgb_rendered", conditioning_image_type="tiled_rgb"), cfg
+
+
 def epoch_seconds(loader, consume=None):
     t0 = time.perf_counter()
     n = 0
@@ -77,6 +94,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--family", default="sd-turbo")
     ap.add_argument("--no-train", action="store_true")
+    ap.add_argument("--render-textures", default=None, help="directory of the five sphere textures: also time a loader whose targets are drawn "
+                    "on the device (DataLoader(render_targets=...)) against cache=\"device\" on a tree that render_episode wrote (resolution 512)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from genima_amd import configs
@@ -172,10 +191,20 @@ def main():
                     tr.train_step(resident)
                 torch.cuda.synchronize()
                 return (time.perf_counter() - t0) / n_batches
-            times = {"cache_none": [], "cache_device": [], "resident_synthetic_batch": []}
+            drawn = {}
+            if args.render_textures:  # the same number of examples, their targets rendered: read back as PNGs, or drawn in to_device
+                ds2, cfg2 = write_rendered_tree(os.path.join(root, "rendered_tree"), args.examples, R, args.render_textures, E)
+                drawn = {"rendered_tree_cache_device": D.DataLoader(ds2, B, tok, R, shuffle=True, seed=0, cache="device"),
+                         "rendered_tree_cache_device_render_targets": D.DataLoader(ds2, B, tok, R, shuffle=True, seed=0, cache="device",
+                                                                                   render_targets=Rn.TrajectorySource(cfg2))}
+                for ld in drawn.values():
+                    epoch_seconds(ld, step)  # the caches fill
+            times = {"cache_none": [], "cache_device": [], "resident_synthetic_batch": [], **{k: [] for k in drawn}}
             for _ in range(args.rounds):
                 times["cache_none"].append(epoch_seconds(plain, step))
                 times["cache_device"].append(epoch_seconds(cached, step))
+                for k, ld in drawn.items():
+                    times[k].append(epoch_seconds(ld, step))
                 times["resident_synthetic_batch"].append(resident_seconds())
             res["train_step_ms"] = {k: summary(v, 1e3) for k, v in times.items()}
             res["train_family"], res["train_steps_per_epoch"] = args.family, n_batches
