@@ -289,6 +289,11 @@ SIGNATURES = {
     "gn_program_run": (_I32, [_P, _I64, _I64]),
     "gn_program_capture": (_I32, [_P]),
     "gn_program_launch": (_I32, [_P]),
+    "gn_program_begin_segment": (_I32, [_P, C.POINTER(C.c_int32)]),
+    "gn_program_end_segment": (_I32, [_P]),
+    "gn_program_set_segment_enabled": (_I32, [_P, _I32, _I32]),
+    "gn_program_last_run_ops": (_I64, [_P]),
+    "gn_bytes_changed": (_I32, [_P, _P, _P, _I64, _P]),
     "gn_event_create": (_I32, [C.POINTER(_P)]),
     "gn_event_destroy": (_I32, [_P]),
     "gn_event_record": (_I32, [_P, _P]),

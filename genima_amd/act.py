@@ -149,16 +149,18 @@ def emit_act_forward(E: Engine, W, Wclip, cfg, ccfg, img_u8_nhwc: torch.Tensor, 
     dev = E.device
     with E.scope("act"):
         # ---- language conditioning: CLIP text tower -> EOT row -> text_projection -> task token ---------------------------
-        task = None
+        # Guarded segment "task_text" (recorded programs): the tower, the task token and the FiLM generators read the task text and the weights
+        # alone, and the text is the same at every control step -- GenimaACT._run skips the segment while the tokens are unchanged.
+        task = film = None
         if cfg.get("use_lang_cond") and tokens is not None:
-            xt = graphs.emit_clip_text(E, Wclip, ccfg, tokens)
-            eot = E.argmax_rows(tokens, name="eot")
-            pooled = E.gather_rows(xt, eot, name="pooled")
-            task = E.linear(pooled, Wclip["text_projection.weight"], name="task_emb")
-        film = None
-        if task is not None and "backbone.film_fcs.0.weight" in W:
-            film = {li: E.linear(task, W[f"backbone.film_fcs.{j}.weight"], W[f"backbone.film_fcs.{j}.bias"], name=f"film{li}")
-                    for j, (li, _, _) in enumerate(_RESNET18[1:])}
+            with E.segment("task_text"):
+                xt = graphs.emit_clip_text(E, Wclip, ccfg, tokens)
+                eot = E.argmax_rows(tokens, name="eot")
+                pooled = E.gather_rows(xt, eot, name="pooled")
+                task = E.linear(pooled, Wclip["text_projection.weight"], name="task_emb")
+                if "backbone.film_fcs.0.weight" in W:
+                    film = {li: E.linear(task, W[f"backbone.film_fcs.{j}.weight"], W[f"backbone.film_fcs.{j}.bias"], name=f"film{li}")
+                            for j, (li, _, _) in enumerate(_RESNET18[1:])}
         # ---- ResNet-18 per view (FrozenBN folded; ReLU / identity add in the conv epilogues) ---------------------------------
         x = E.image_normalize_u8(img_u8_nhwc.view(B * V, H, Wd, 3), IMAGENET_MEAN, IMAGENET_STD, 8, name="img")
         p = "backbone"
@@ -490,6 +492,8 @@ class GenimaACT:
             io.tokens = E.buf("in_tokens", (B, 77), dtype=torch.int32, zero=True) if lang else None
             io.a_hat, io.is_pad, io.task = emit_act_forward(E, self.W, self.Wclip, self.config, self.clip_config, io.img, io.qpos, io.tokens)
             save_tune_table()
+            io.text_valid = False  # do the task_text segment's outputs belong to the tokens of the last replay?
+            io.tokens_host = None  # the host tokens it last ran with (device tokens are compared by Engine.changed)
             self._progs[key] = io
         return io
 
@@ -500,10 +504,32 @@ class GenimaACT:
         io = self._program(B, V, H, Wd, lang)
         io.img.copy_(img_u8_nhwc)
         io.qpos[:, : qpos.shape[1]].copy_(qpos.to(torch.float16))
+        E = io.engine
+        E.use_stream(torch.cuda.current_stream(self.device))
+        guard = lang and E.hoist and "task_text" in E.segments
+        run_text = True
         if lang:
-            io.tokens.copy_(tokens.reshape(B, -1, tokens.shape[-1])[:, 0].to(torch.int32))  # text does not change across frames
-        io.engine.use_stream(torch.cuda.current_stream(self.device))
-        io.engine.run()
+            tk = tokens.reshape(B, -1, tokens.shape[-1])[:, 0].to(torch.int32)  # text does not change across frames
+            io.tokens.copy_(tk)
+            if guard:
+                if tk.device.type == "cpu":  # compared on the host with the tokens the segment last ran with
+                    changed = io.tokens_host is None or not torch.equal(io.tokens_host, tk)
+                    io.tokens_host = tk.clone()
+                    E.forget("tokens")
+                else:  # one compare launch + a 4-byte read
+                    io.tokens_host = None
+                    changed = E.changed(io.tokens, "tokens")
+                run_text = changed or not io.text_valid
+        if guard:
+            E.set_segment("task_text", run_text)
+            if run_text:
+                io.text_valid = False
+        try:
+            E.run()
+        finally:
+            if guard:
+                E.set_segment("task_text", True)  # a direct replay of io.engine always runs the whole program
+        io.text_valid = True
         return io
 
     def encode_clip_text(self, tokens: torch.Tensor):
@@ -523,7 +549,7 @@ class GenimaACT:
         B, H2, W2, _ = tiled_u8.shape
         v = H2 // 2
         img = torch.stack([tiled_u8[:, y:y + v, x:x + v] for (x, y) in ((0, 0), (v, 0), (0, v), (v, v))], dim=1)  # layout only
-        io = self._run(img, low_dim_state.to(self.device).flatten(1), None if lang_tokens is None else lang_tokens.to(self.device))
+        io = self._run(img, low_dim_state.to(self.device).flatten(1), lang_tokens)
         return io.a_hat[..., : self.config["action_dim"]]
 
     def update(self, replay_iter, step: int = 0, replay_buffer=None, **trainer_kw) -> Dict[str, float]:
@@ -579,5 +605,5 @@ class GenimaACT:
         img_u8 = image.round().clamp(0, 255).to(torch.uint8) if image.dtype != torch.uint8 else image
         img_u8 = img_u8.permute(0, 1, 3, 4, 2).contiguous()
         toks = obs.get("lang_tokens") if self.config.get("use_lang_cond") else None
-        io = self._run(img_u8, qpos, None if toks is None else toks.to(self.device))
+        io = self._run(img_u8, qpos, toks)
         return io.a_hat[..., : self.config["action_dim"]].to(torch.float32)

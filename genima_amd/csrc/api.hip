@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <string.h>
 
+#include <map>
 #include <vector>
 
 #include "common.h"
@@ -53,14 +54,39 @@ struct Op {
 
 }  // namespace
 
+struct Segment { int64_t first, last; };  // op range [first, last) marked at record time (gn_program_begin_segment / end_segment)
+struct CapturedGraph { hipGraph_t graph; hipGraphExec_t exec; int64_t ops; };
+
 struct gn_program {
   gn_ctx* ctx;
   std::vector<Op> ops;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
+  // guarded segments: a FULL replay skips the kernel ops of a disabled segment (their outputs are still there from the replay that ran them);
+  // stream markers always act, and an explicit op range runs exactly what it names
+  std::vector<Segment> segs;
+  int64_t open_seg = -1;           // op index where the open segment began, or -1
+  uint64_t enabled = ~0ull;        // bit s: segment s runs
+  int64_t last_run_ops = 0;        // kernel ops the last full replay issued (gn_program_last_run_ops)
+  std::map<uint64_t, CapturedGraph> graphs;  // one captured graph per set of enabled flags that was launched
+  hipGraphExec_t exec = nullptr;   // non-null once captured (the graph of the flags at gn_program_capture)
   hipStream_t side = nullptr;          // second stream for independent sub-graphs (ControlNet next to the UNet encoder)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
+
+static void drop_graphs(gn_program* p) {
+  for (auto& kv : p->graphs) {
+    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+    if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
+  }
+  p->graphs.clear();
+  p->exec = nullptr;
+}
+
+// does a full replay skip op i?  (segments do not nest and are recorded in op order)
+static bool op_skipped(const gn_program* p, int64_t i) {
+  for (size_t s = 0; s < p->segs.size(); ++s)
+    if (i >= p->segs[s].first && i < p->segs[s].last) return !((p->enabled >> s) & 1ull);
+  return false;
+}
 
 static int32_t run_op(gn_ctx* ctx, const Op& op) {
   const GenericArgs& g = op.g;
@@ -170,8 +196,7 @@ int32_t gn_program_create(gn_ctx* ctx, gn_program** out) {
 }
 int32_t gn_program_destroy(gn_program* p) {
   if (p) {
-    if (p->exec) (void)hipGraphExecDestroy(p->exec);
-    if (p->graph) (void)hipGraphDestroy(p->graph);
+    drop_graphs(p);
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
     if (p->ev_join) (void)hipEventDestroy(p->ev_join);
     if (p->side) (void)hipStreamDestroy(p->side);
@@ -413,6 +438,8 @@ int32_t gn_program_add_memset(gn_program* p, void* ptr, int64_t bytes) {
   return push_generic(p, OP_MEMSET, nullptr, nullptr, nullptr, ptr, bytes, 0, 0, 0, 0, 0, 0.f, 0.f);
 }
 
+static uint64_t seg_mask(const gn_program* p) { return p->segs.size() >= 64 ? ~0ull : ((1ull << p->segs.size()) - 1ull); }
+
 static int32_t ensure_side_stream(gn_program* p) {
   if (!p->side) {
     GN_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
@@ -425,8 +452,12 @@ static int32_t ensure_side_stream(gn_program* p) {
 int32_t gn_program_run(gn_program* p, int64_t first, int64_t last) {
   GN_REQUIRE(p, "gn_program_run: null program");
   const int64_t n = (int64_t)p->ops.size();
+  const bool full = first == 0 && last < 0;  // the whole program by default: honours the segment flags; an explicit range does not
   if (last < 0 || last > n) last = n;
   GN_REQUIRE(first >= 0 && first <= last, "gn_program_run: bad range [%ld, %ld)", (long)first, (long)last);
+  GN_REQUIRE(p->open_seg < 0, "gn_program_run: a segment is still open (gn_program_end_segment)");
+  const bool guarded = full && !p->segs.empty() && (p->enabled & seg_mask(p)) != seg_mask(p);
+  int64_t issued = 0;
   // stream-control ops only act on whole-program replays; a sub-range (per-op timing) runs serially on the context's stream
   const bool two_streams = first == 0 && last == n;
   hipStream_t main_stream = p->ctx->stream;
@@ -437,6 +468,17 @@ int32_t gn_program_run(gn_program* p, int64_t first, int64_t last) {
     if (op.type == OP_FORK || op.type == OP_MAIN || op.type == OP_JOIN) {
       if (!two_streams) continue;
       if (op.type == OP_FORK) {
+        if (guarded) {
+          // a side section whose every kernel is skipped is not opened: an empty branch would hand the next join the same predecessors twice
+          // (the join in front of it already ordered the side stream's work), and there is nothing to overlap
+          bool any = false;
+          for (int64_t j = i + 1; j < last && !any; ++j) {
+            const int t = p->ops[(size_t)j].type;
+            if (t == OP_FORK || t == OP_MAIN || t == OP_JOIN) break;
+            any = !op_skipped(p, j);
+          }
+          if (!any) continue;
+        }
         rc = ensure_side_stream(p);
         if (rc != GN_OK) break;
         if (hipEventRecord(p->ev_fork, main_stream) != hipSuccess || hipStreamWaitEvent(p->side, p->ev_fork, 0) != hipSuccess) {
@@ -455,7 +497,9 @@ int32_t gn_program_run(gn_program* p, int64_t first, int64_t last) {
       }
       continue;
     }
+    if (guarded && op_skipped(p, i)) continue;
     rc = run_op(p->ctx, op);
+    ++issued;
     if (rc != GN_OK) {
       char tmp[900];
       snprintf(tmp, sizeof(tmp), "%s", g_err);
@@ -467,30 +511,75 @@ int32_t gn_program_run(gn_program* p, int64_t first, int64_t last) {
     (void)hipEventRecord(p->ev_join, p->side);
     (void)hipStreamWaitEvent(main_stream, p->ev_join, 0);
   }
+  if (full) p->last_run_ops = issued;
   return rc;
 }
 
-int32_t gn_program_capture(gn_program* p) {
-  GN_REQUIRE(p, "gn_program_capture: null program");
+// capture the whole program under the current segment flags into the graph cache
+static int32_t capture_current(gn_program* p, CapturedGraph** out) {
   GN_REQUIRE(p->ctx->stream != nullptr, "gn_program_capture: needs a non-default stream");
-  if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-  if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
   GN_HIP(hipStreamBeginCapture(p->ctx->stream, hipStreamCaptureModeThreadLocal));
   int32_t rc = gn_program_run(p, 0, -1);
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(p->ctx->stream, &g);
   if (rc != GN_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
   if (e != hipSuccess) { gn_set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return GN_ERR_HIP; }
-  p->graph = g;
-  GN_HIP(hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0));
+  hipGraphExec_t x = nullptr;
+  e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
+  if (e != hipSuccess) { (void)hipGraphDestroy(g); gn_set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return GN_ERR_HIP; }
+  CapturedGraph& c = p->graphs[p->enabled & seg_mask(p)];
+  c.graph = g; c.exec = x; c.ops = p->last_run_ops;
+  *out = &c;
+  return GN_OK;
+}
+
+int32_t gn_program_capture(gn_program* p) {
+  GN_REQUIRE(p, "gn_program_capture: null program");
+  drop_graphs(p);  // a re-capture (after gn_program_set_gemm_plan and its like) forgets the graph of every set of flags
+  CapturedGraph* c = nullptr;
+  int32_t rc = capture_current(p, &c);
+  if (rc != GN_OK) return rc;
+  p->exec = c->exec;
   return GN_OK;
 }
 
 int32_t gn_program_launch(gn_program* p) {
   GN_REQUIRE(p && p->exec, "gn_program_launch: program not captured");
-  GN_HIP(hipGraphLaunch(p->exec, p->ctx->stream));
+  // one graph per set of enabled flags, captured the first time that set is launched (in practice two: everything, and the steady state)
+  auto it = p->graphs.find(p->enabled & seg_mask(p));
+  CapturedGraph* c = it != p->graphs.end() ? &it->second : nullptr;
+  if (!c) {
+    int32_t rc = capture_current(p, &c);
+    if (rc != GN_OK) return rc;
+  }
+  GN_HIP(hipGraphLaunch(c->exec, p->ctx->stream));
+  p->last_run_ops = c->ops;
   return GN_OK;
 }
+
+// ---- guarded segments ------------------------------------------------------------------------------------------------
+int32_t gn_program_begin_segment(gn_program* p, int32_t* seg_id) {
+  GN_REQUIRE(p && seg_id, "gn_program_begin_segment: null argument");
+  GN_REQUIRE(p->open_seg < 0, "gn_program_begin_segment: segments do not nest");
+  GN_REQUIRE(!p->exec, "gn_program_begin_segment: the program is captured");
+  GN_REQUIRE(p->segs.size() < 64, "gn_program_begin_segment: at most 64 segments per program");
+  p->open_seg = (int64_t)p->ops.size();
+  *seg_id = (int32_t)p->segs.size();
+  return GN_OK;
+}
+int32_t gn_program_end_segment(gn_program* p) {
+  GN_REQUIRE(p && p->open_seg >= 0, "gn_program_end_segment: no open segment");
+  p->segs.push_back(Segment{p->open_seg, (int64_t)p->ops.size()});
+  p->open_seg = -1;
+  return GN_OK;
+}
+int32_t gn_program_set_segment_enabled(gn_program* p, int32_t seg_id, int32_t enabled) {
+  GN_REQUIRE(p && seg_id >= 0 && seg_id < (int32_t)p->segs.size(), "gn_program_set_segment_enabled: no segment %d", seg_id);
+  if (enabled) p->enabled |= 1ull << seg_id;
+  else p->enabled &= ~(1ull << seg_id);
+  return GN_OK;
+}
+int64_t gn_program_last_run_ops(const gn_program* p) { return p ? p->last_run_ops : 0; }
 
 // ---- events ----------------------------------------------------------------------------------------------------------
 int32_t gn_event_create(void** ev) {

@@ -164,6 +164,31 @@ __global__ void argmax_rows_i32_kernel(const int32_t* __restrict__ x, int32_t* _
   out[r] = best;
 }
 
+// did `live` change since the snapshot `seen`?  One workgroup walks both with 16-byte loads (+ a tail of 4-byte words), brings `seen` up to
+// date in the same pass and writes the answer as one int32 (prompt ids are a few KB: one launch, one 4-byte read on the host)
+__global__ __launch_bounds__(256) void bytes_changed_kernel(const uint4* __restrict__ live, uint4* __restrict__ seen, long n16, int tail_words,
+                                                            int32_t* __restrict__ flag) {
+  int diff = 0;
+  for (long i = threadIdx.x; i < n16; i += blockDim.x) {
+    const uint4 a = live[i], b = seen[i];
+    if ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) {
+      diff = 1;
+      seen[i] = a;
+    }
+  }
+  if ((int)threadIdx.x < tail_words) {
+    const uint32_t* lt = reinterpret_cast<const uint32_t*>(live + n16);
+    uint32_t* st = reinterpret_cast<uint32_t*>(seen + n16);
+    const uint32_t a = lt[threadIdx.x];
+    if (a != st[threadIdx.x]) {
+      diff = 1;
+      st[threadIdx.x] = a;
+    }
+  }
+  diff = __syncthreads_or(diff);
+  if (threadIdx.x == 0) *flag = diff ? 1 : 0;
+}
+
 __global__ void image_f16_to_u8_kernel(const f16* __restrict__ in, uint8_t* __restrict__ out, long pixels, int ld) {
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= pixels) return;
@@ -480,6 +505,15 @@ int32_t gn_copy4d(gn_ctx* ctx, const void* in, void* out, const int64_t* sizes, 
 int32_t gn_argmax_rows_i32(gn_ctx* ctx, const int32_t* x, int32_t* out, int32_t rows, int32_t cols) {
   GN_REQUIRE(ctx && x && out && rows > 0 && cols > 0, "gn_argmax_rows_i32: bad arguments");
   hipLaunchKernelGGL(argmax_rows_i32_kernel, dim3(nblk(rows, 64)), dim3(64), 0, ctx->stream, x, out, rows, cols);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int32_t gn_bytes_changed(gn_ctx* ctx, const void* live, void* seen, int64_t bytes, int32_t* flag) {
+  GN_REQUIRE(ctx && live && seen && flag && bytes > 0 && bytes % 4 == 0, "gn_bytes_changed: null argument, or bytes (%ld) not a positive multiple of 4", (long)bytes);
+  GN_REQUIRE((((uintptr_t)live | (uintptr_t)seen) & 15) == 0 && ((uintptr_t)flag & 3) == 0, "gn_bytes_changed: live / seen need 16-byte alignment");
+  hipLaunchKernelGGL(bytes_changed_kernel, dim3(1), dim3(256), 0, ctx->stream, (const uint4*)live, (uint4*)seen, (long)(bytes / 16),
+                     (int)((bytes % 16) / 4), flag);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

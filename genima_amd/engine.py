@@ -94,6 +94,9 @@ class Engine:
         self.lib = _lib.load()
         self.autotune = (record or os.environ.get("GN_AUTOTUNE") == "1") if autotune is None else autotune
         self.hoist_time_shifts = os.environ.get("GN_HOIST_TIME_SHIFTS", "1") != "0"  # pipeline: all steps' time shifts in one pass (A/B switch)
+        # guarded segments (segment() / set_segment()): the pipeline and the ACT wrapper skip prompt-only and record-time-constant work while its
+        # inputs are unchanged; GN_HOIST=0 keeps every segment enabled on every replay (A/B switch)
+        self.hoist = os.environ.get("GN_HOIST", "1") != "0"
         self.up_phases = os.environ.get("GN_UP_PHASES", "1") != "0"  # graphs: upsample + 3x3 conv as four 2x2 phase convs (A/B switch)
         self.up_phases_one_launch = os.environ.get("GN_UP_PHASES_ONE_LAUNCH", "1") != "0"
         self.up_phases_min_rows = int(os.environ.get("GN_UP_PHASES_MIN_ROWS", "1024"))  # source pixels x batch below which the 3x3 launch stays
@@ -140,6 +143,11 @@ class Engine:
         self._scope = []
         self._zpool = None  # eager: [pre-zeroed slab, next free element] while an emitter holds zero_pool()
         self.captured = False
+        self.segments: Dict[str, dict] = {}  # name -> dict(id, first, last, enabled, kernel_ops): the guarded op ranges of a recorded program
+        self._seg_open = None    # name of the segment being recorded
+        self._seg_writes = []    # (lo, hi, segment name) byte ranges written by the ops of closed / open segments
+        self._plain_writes = []  # (lo, hi) byte ranges written by ops outside every segment (kept while the program has segments to check against)
+        self._seen: Dict[str, tuple] = {}  # changed(): key -> (snapshot, flag) device tensors
         self.meta = []  # per recorded op: dict(kind, flops, bytes) -- algorithmic work for the roofline accounting
         # ---- the GroupNorm bridge (csrc/gn_bridge.h; recorded programs): statistics out of the op that writes a tensor, GroupNorm-apply inside
         # the op that reads it.  OFF by default (GN_BRIDGE=1 / Engine(gn_bridge=True) switch it on): measured on MI355X it does not pay inside the
@@ -235,10 +243,112 @@ class Engine:
         self._wrote(t)  # whoever asks for an output buffer is about to write it
         return t
 
+    # ---- guarded segments ---------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def segment(self, name: str):
+        """The ops recorded inside the block form the guarded segment ``name`` (gn_program_begin_segment / end_segment): a full replay skips
+        them while ``set_segment(name, False)`` holds, so whatever they write must survive from one replay to the next -- an op outside the
+        segment that writes into one of its outputs is refused at record time (``_wrote``).  Eager engines run the block as it is."""
+        if not self.record:
+            yield
+            return
+        if name in self.segments or self._seg_open is not None:
+            raise GenimaHipError(f"segment {name!r}: segments are recorded once and do not nest")
+        sid = C.c_int32(-1)
+        check(self.lib.gn_program_begin_segment(self._prog, C.byref(sid)), "gn_program_begin_segment")
+        first = self.num_ops
+        self._seg_open = name
+        try:
+            yield
+        finally:
+            self._seg_open = None
+            check(self.lib.gn_program_end_segment(self._prog), "gn_program_end_segment")
+            last = self.num_ops
+            kernel_ops = sum(1 for m in self.meta[first:last] if m.get("kind") != "stream")
+            self.segments[name] = dict(id=int(sid.value), first=first, last=last, enabled=True, kernel_ops=kernel_ops)
+
+    def set_segment(self, name: str, enabled: bool):
+        """Run (True) or skip (False) the segment on the next full replays (``run()`` / ``launch()``); ``run(first, last)`` ignores it."""
+        seg = self.segments[name]
+        if seg["enabled"] != bool(enabled):
+            check(self.lib.gn_program_set_segment_enabled(self._prog, seg["id"], 1 if enabled else 0), "gn_program_set_segment_enabled")
+            seg["enabled"] = bool(enabled)
+
+    @property
+    def last_run_ops(self) -> int:
+        """Kernel ops the last full replay issued (stream markers not counted)."""
+        return int(self.lib.gn_program_last_run_ops(self._prog)) if self.record else 0
+
+    def changed(self, live: torch.Tensor, key: str, stream: Optional[torch.cuda.Stream] = None) -> bool:
+        """Did the device tensor ``live`` change since the last ``changed(live, key)``?  One compare launch (gn_bytes_changed) on ``stream``
+        (default: the engine's) against a snapshot this engine owns -- brought up to date in the same pass -- and one 4-byte read of its
+        flag.  The first call for a key, and a call after ``forget(key)``, answer True."""
+        nbytes = live.numel() * live.element_size()
+        if not live.is_contiguous() or nbytes % 4 or live.data_ptr() % 16:
+            raise GenimaHipError("Engine.changed: needs a contiguous, 16-byte aligned tensor of a multiple of 4 bytes")
+        st = self._seen.get(key)
+        if st is None or st[0].numel() != nbytes:
+            with torch.cuda.stream(stream if stream is not None else self.stream):
+                snap = live.reshape(-1).view(torch.uint8).clone()
+            self._seen[key] = (snap, torch.zeros(1, dtype=torch.int32, device=self.device))
+            return True
+        snap, flag = st
+        mine = self.stream
+        if stream is not None and stream != mine:
+            self.use_stream(stream)
+        try:
+            check(self.lib.gn_bytes_changed(self._ctx, _ptr(live), _ptr(snap), nbytes, _ptr(flag)), "gn_bytes_changed")
+        finally:
+            if stream is not None and stream != mine:
+                self.use_stream(mine)
+        with torch.cuda.stream(stream if stream is not None else mine):
+            return bool(flag.item())
+
+    def forget(self, key: Optional[str] = None):
+        """Drop the snapshot behind ``changed(.., key)`` (all of them without a key): the next comparison answers True."""
+        if key is None:
+            self._seen.clear()
+        else:
+            self._seen.pop(key, None)
+
+    @staticmethod
+    def _span(t: torch.Tensor):
+        """Byte range [lo, hi) that the (possibly strided) tensor touches."""
+        if t.numel() == 0:
+            return t.data_ptr(), t.data_ptr()
+        last = sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+        return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+    def _check_segment_writes(self, ts):
+        """Liveness of the guarded segments: what a segment writes is read by later replays that skip it, so no op outside the segment may write
+        into the same bytes -- neither after it (the value would be gone at the next replay) nor before it (the earlier op would run again
+        and the segment would not restore it)."""
+        for t in ts:
+            if t is None:
+                continue
+            lo, hi = self._span(t)
+            if hi <= lo:
+                continue
+            own = self._seg_open
+            for a, b, name in self._seg_writes:
+                if name != own and lo < b and a < hi:
+                    where = f"segment {own!r}" if own else "an op outside it"
+                    raise GenimaHipError(f"segment {name!r}: its output at {a:#x} (+{b - a} bytes) is rewritten by {where}; a skipped "
+                                         "segment's outputs must survive to the next replay")
+            if own is None:
+                self._plain_writes.append((lo, hi))
+            else:
+                for a, b in self._plain_writes:
+                    if lo < b and a < hi:
+                        raise GenimaHipError(f"segment {own!r} rewrites {b - a} bytes at {a:#x} that an op outside it writes on every replay")
+                self._seg_writes.append((lo, hi, own))
+
     def _wrote(self, *ts):
         """A recorded op is about to (over)write these tensors: forget who wrote them before -- a GroupNorm recorded later must not fuse into (or take
         statistics from) a producer whose output has been replaced since.  buf() calls it for every buffer it hands out; ops that take an
-        explicit ``out=`` / work in place call it themselves."""
+        explicit ``out=`` / work in place call it themselves.  With guarded segments in the program it is also where their liveness is checked."""
+        if self.record:
+            self._check_segment_writes(ts)
         if self._writer:
             for t in ts:
                 if t is not None:

@@ -725,6 +725,21 @@ int64_t gn_desc_sizeof(int32_t which);
 int32_t gn_program_run(gn_program* p, int64_t first, int64_t last);
 int32_t gn_program_capture(gn_program* p);   /* capture the whole program into a hipGraph on the ctx stream */
 int32_t gn_program_launch(gn_program* p);    /* replay the captured graph */
+/* Guarded segments: work whose inputs stay the same from call to call (the prompt's text tower and K / V projections, the time shifts of a
+ * baked timestep table) is marked at record time and skipped while its inputs are unchanged -- its output buffers persist between replays.
+ *   begin / end    mark the ops recorded in between as one segment (contiguous, not nested, at most 64); every segment starts enabled
+ *   set_enabled    the caller's decision: only the caller knows whether the segment's inputs (and the weights behind it) changed
+ * A FULL replay -- gn_program_run(p, 0, -1) and gn_program_launch -- skips the kernel ops of a disabled segment.  Stream markers (fork /
+ * main / join) inside it still act -- except a fork whose side section has nothing left to run, which is not opened.  A replay of an explicit range (first > 0 or last >= 0) runs exactly the ops it names, whatever the
+ * flags say.  gn_program_launch keeps one captured graph per set of flags it was launched with (captured on first use on the ctx stream);
+ * gn_program_capture drops them all.  gn_program_last_run_ops: kernel ops issued by the last full replay.
+ * gn_bytes_changed: one launch that compares `live` with the snapshot `seen` (16-byte aligned, bytes a multiple of 4), brings `seen` up to
+ * date and writes 1 / 0 to the int32 `flag` in device memory. */
+int32_t gn_program_begin_segment(gn_program* p, int32_t* seg_id);
+int32_t gn_program_end_segment(gn_program* p);
+int32_t gn_program_set_segment_enabled(gn_program* p, int32_t seg_id, int32_t enabled);
+int64_t gn_program_last_run_ops(const gn_program* p);
+int32_t gn_bytes_changed(gn_ctx* ctx, const void* live, void* seen, int64_t bytes, int32_t* flag);
 
 /* ---- timing helper: HIP events on the ctx stream (bench.py's roofline leg) ------------------------------------- */
 int32_t gn_event_create(void** ev);
