@@ -213,6 +213,9 @@ SIGNATURES = {
     "gn_softmax_rows_masked": (_I32, [_P, _P, _I64, _I32, _I32, _F, _I32]),
     "gn_quantize_fp8_rows": (_I32, [_P, _P, _I64, _I64, _I32, _P, _I64, _P]),
     "gn_maxpool3x3s2": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32]),
+    "gn_action_ensemble_state_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "gn_action_ensemble": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
+    "gn_action_ensemble_f16": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_transpose2d": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I64, _I32, _I64, _I64]),
     "gn_transpose2d_zpad": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I64, _I32, _I64, _I64]),
     "gn_transpose2d_multi": (_I32, [_P, _P, _I32, _I32]),
@@ -283,6 +286,7 @@ SIGNATURES = {
     "gn_program_add_embedding": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_program_add_softmax_rows": (_I32, [_P, _P, _I64, _I32, _I32, _F]),
     "gn_program_add_maxpool3x3s2": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32]),
+    "gn_program_add_action_ensemble": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_program_num_ops": (_I64, [_P]),
     "gn_program_get_gemm": (_I32, [_P, _I64, _P]),
     "gn_program_set_gemm_plan": (_I32, [_P, _I64, _I32, _I32, _P]),

@@ -358,6 +358,23 @@ def clip_openai_to_hf(sd: Dict[str, torch.Tensor]) -> "OrderedDict[str, torch.Te
     return out
 
 
+def execution_slots(T: int, execution_horizon: Optional[int], temporal_agg: bool):
+    """-> (h, K): the actions executed per call and the ring slots the ensemble keeps.  ``K = ceil(T / h)`` chunks can cover a step when the
+    environment step advances by h per call; without ``temporal_agg`` one slot (the new chunk alone)."""
+    h = T if execution_horizon is None else execution_horizon
+    if isinstance(h, bool) or int(h) != h or not 1 <= int(h) <= T:
+        raise GenimaHipError(f"execution_horizon must be an integer in 1 .. num_queries = {T}, got {execution_horizon!r}")
+    h = int(h)
+    return h, (-(-T // h) if temporal_agg else 1)
+
+
+def check_ensemble_m(m) -> float:
+    m = float(m)
+    if not (m >= 0.0 and math.isfinite(m)):
+        raise GenimaHipError(f"temporal ensembling: m must be a finite number >= 0, got {m!r}")
+    return m
+
+
 class GenimaACT:
     """Controller plugin (``method._target_: method.genima_act.GenimaACT``, controller/cfgs/method/genima_act.yaml:3-4)."""
 
@@ -379,6 +396,10 @@ class GenimaACT:
         self.training = False
         self.W = self.Wclip = None
         self._progs = {}
+        self.use_graph = False
+        self._exec = None          # (h, K, m) once set_execution() asked for an execution mode; None: act() returns the whole chunk
+        self._exec_epoch = 0       # bumped by set_execution() / reset_execution(): a program whose epoch is older empties every row's ring
+        self._exec_pending = set() # rows reset_execution(rows) marked for the next call
         if self.device.type == "cuda" and torch.cuda.is_available():
             self.to(self.device)
 
@@ -473,11 +494,87 @@ class GenimaACT:
             self._progs = {}
         return missing, unexpected
 
+    # ---- execution mode: the eval configurations' ``execution_horizon`` / ``temporal_agg`` ------------------------------------
+    def set_execution(self, execution_horizon: Optional[int] = None, temporal_agg: bool = False, m: float = 0.01):
+        """Honour ``execution_horizon`` / ``temporal_agg`` (controller/cfgs/eval_genima.yaml:29,33; the reference never reads them): from now
+        on ``act`` / ``act_tiled`` return f32 ``[B, h, A]`` -- the actions of the environment steps ``step .. step + h - 1`` with
+        ``h = execution_horizon`` (None: the whole chunk), so the loop executes h actions and calls again.  With ``temporal_agg`` every
+        chunk that still covers a step takes part in its action: the ACT paper's temporal ensembling with weights ``exp(-m i)``, i = 0 for
+        the oldest prediction, over all action dimensions alike (the gripper's included); without it the result is the first h rows of the
+        new chunk.  The history lives on the device (Engine.action_ensemble, one launch at the end of the recorded program) and starts
+        empty.  ``set_execution()`` with nothing set returns to the default: the whole chunk, no extra op."""
+        T = int(self.config["num_queries"])
+        if execution_horizon is None and not temporal_agg:
+            self._exec = None
+        else:
+            self._exec = (*execution_slots(T, execution_horizon, temporal_agg), check_ensemble_m(m))
+        self._exec_epoch += 1
+        self._exec_pending = set()
+        return self
+
+    @property
+    def execution(self):
+        """The execution mode in force: ``(h, K, m)`` -- actions per call, ring slots, weight decay -- or None (the whole chunk)."""
+        return self._exec
+
+    def reset_execution(self, rows=None):
+        """Forget the chunk history at the next call (a new episode): of every batch row, or of the rows listed."""
+        if rows is None:
+            self._exec_epoch += 1
+            self._exec_pending = set()
+        else:
+            rows = [int(r) for r in rows]
+            if any(r < 0 for r in rows):
+                raise GenimaHipError(f"reset_execution: negative row in {rows}")
+            self._exec_pending.update(rows)
+        return self
+
+    def enable_hip_graph(self, flag: bool = True):
+        """Replay each controller call as one captured hipGraph (as the diffusion pipeline's ``enable_hip_graph``)."""
+        self.use_graph = bool(flag)
+        self._progs = {}
+        return self
+
+    def _fill_execution(self, io, step, B):
+        """Per-call inputs of the ensemble op: the environment step of each row and the rows whose ring is emptied first.  Host values go
+        through a pinned ``steps | reset`` block and ONE asynchronous copy on the current stream: the host does not wait for the work queued in
+        front of it (the diffusion pipeline's, in ``act_tiled``); before the block is written again it waits for that one copy alone."""
+        host = getattr(io, "ens_host", None)
+        if host is None:
+            host = io.ens_host = torch.zeros(5 * B, dtype=torch.uint8, pin_memory=io.ens_ctl.is_cuda)
+            io.ens_host_steps, io.ens_host_reset, io.ens_copied = host[: 4 * B].view(torch.int32), host[4 * B:], None
+        on_device = isinstance(step, torch.Tensor) and step.is_cuda
+        if not on_device:  # checked before anything is taken in
+            st = torch.as_tensor(step).reshape(-1).to(torch.int64)
+            if st.numel() not in (1, B) or bool((st < 0).any()) or bool((st > 2 ** 31 - 1 - int(self.config["num_queries"])).any()):
+                raise GenimaHipError(f"act: step must be an int or an int tensor [{B}] of environment steps >= 0, got {step!r}")
+        if self._exec_pending and max(self._exec_pending) >= B:
+            raise GenimaHipError(f"reset_execution: row {max(self._exec_pending)} of a batch of {B}")
+        if io.ens_copied is not None:
+            io.ens_copied.synchronize()  # the previous call's copy out of the pinned block (long done by now)
+        reset = io.ens_host_reset
+        reset.zero_()
+        if io.ens_epoch != self._exec_epoch:
+            reset.fill_(1)
+            io.ens_epoch = self._exec_epoch
+        if self._exec_pending:
+            reset[sorted(self._exec_pending)] = 1
+            self._exec_pending = set()
+        if on_device:  # the steps stay on the device: no range check is possible without reading them back (see ``act``)
+            io.ens_steps.copy_(step.reshape(-1).expand(B) if step.numel() == 1 else step.reshape(B))
+            io.ens_reset.copy_(reset, non_blocking=True)
+        else:
+            io.ens_host_steps.copy_(st.expand(B))
+            io.ens_ctl.copy_(host, non_blocking=True)  # one copy: steps | reset share a buffer
+        if io.ens_ctl.is_cuda:
+            io.ens_copied = torch.cuda.Event()
+            io.ens_copied.record(torch.cuda.current_stream(io.ens_ctl.device))
+
     # ---- recorded forward programs (one per input shape), replayed from C++ --------------------------------------------------
     def _program(self, B, V, H, Wd, lang: bool):
         if self.W is None:
             raise GenimaHipError("GenimaACT is not on a ROCm device (no CPU fallback)")
-        key = (B, V, H, Wd, lang)
+        key = (B, V, H, Wd, lang) if self._exec is None and not self.use_graph else (B, V, H, Wd, lang, self._exec, self.use_graph)
         io = self._progs.get(key)
         if io is None:
             from types import SimpleNamespace
@@ -491,13 +588,35 @@ class GenimaACT:
             io.qpos = E.buf("in_qpos", (B, sdim), zero=True)
             io.tokens = E.buf("in_tokens", (B, 77), dtype=torch.int32, zero=True) if lang else None
             io.a_hat, io.is_pad, io.task = emit_act_forward(E, self.W, self.Wclip, self.config, self.clip_config, io.img, io.qpos, io.tokens)
+            io.exec = self._exec
+            if io.exec is not None:
+                # the last op, outside every guarded segment: ensembles a_hat (f16, 8-padded rows) with the ring it keeps on the device
+                h, K, m = io.exec
+                T, A = int(self.config["num_queries"]), int(self.config["action_dim"])
+                io.ens_ctl = torch.zeros(5 * B, dtype=torch.uint8, device=self.device)  # int32 steps [B] | uint8 reset [B]
+                io.ens_steps, io.ens_reset = io.ens_ctl[: 4 * B].view(torch.int32), io.ens_ctl[4 * B:]
+                io.ens_state = E.action_ensemble_state(B, T, A, K)
+                io.ens_out = E.action_ensemble(io.a_hat, io.ens_state, io.ens_steps, io.ens_reset, h, K, m, A=A, name="actions")
+                io.ens_epoch = None
             save_tune_table()
             io.text_valid = False  # do the task_text segment's outputs belong to the tokens of the last replay?
             io.tokens_host = None  # the host tokens it last ran with (device tokens are compared by Engine.changed)
+            io.stream = None
+            if self.use_graph:
+                side = torch.cuda.Stream(device=self.device)
+                E.use_stream(side)
+                with torch.cuda.stream(side):
+                    E.run()  # warm-up outside capture (lazy module loads), on the zeroed inputs
+                    side.synchronize()
+                    E.capture()
+                    if io.exec is not None:
+                        io.ens_state.zero_()  # the warm-up put a chunk into every ring
+                    side.synchronize()
+                io.stream = side
             self._progs[key] = io
         return io
 
-    def _run(self, img_u8_nhwc, qpos, tokens):
+    def _run(self, img_u8_nhwc, qpos, tokens, step=0):
         B, V, H, Wd, _ = img_u8_nhwc.shape
         lang = bool(self.config.get("use_lang_cond")) and tokens is not None
         self._clip_used = self._clip_used or lang
@@ -505,7 +624,11 @@ class GenimaACT:
         io.img.copy_(img_u8_nhwc)
         io.qpos[:, : qpos.shape[1]].copy_(qpos.to(torch.float16))
         E = io.engine
-        E.use_stream(torch.cuda.current_stream(self.device))
+        cur = torch.cuda.current_stream(self.device)
+        if io.stream is None:
+            E.use_stream(cur)
+        if io.exec is not None:
+            self._fill_execution(io, step, B)
         guard = lang and E.hoist and "task_text" in E.segments
         run_text = True
         if lang:
@@ -518,14 +641,19 @@ class GenimaACT:
                     E.forget("tokens")
                 else:  # one compare launch + a 4-byte read
                     io.tokens_host = None
-                    changed = E.changed(io.tokens, "tokens")
+                    changed = E.changed(io.tokens, "tokens", cur if io.stream is not None else None)
                 run_text = changed or not io.text_valid
         if guard:
             E.set_segment("task_text", run_text)
             if run_text:
                 io.text_valid = False
         try:
-            E.run()
+            if io.stream is not None:  # the captured graph runs on its own stream, ordered behind the input copies and in front of the readers
+                io.stream.wait_stream(cur)
+                E.launch()
+                cur.wait_stream(io.stream)
+            else:
+                E.run()
         finally:
             if guard:
                 E.set_segment("task_text", True)  # a direct replay of io.engine always runs the whole program
@@ -543,13 +671,17 @@ class GenimaACT:
         pooled = E.gather_rows(x, E.argmax_rows(tks))
         return E.linear(pooled, self.Wclip["text_projection.weight"]).to(torch.float32), x
 
-    def act_tiled(self, tiled_u8: torch.Tensor, low_dim_state: torch.Tensor, lang_tokens: Optional[torch.Tensor]) -> torch.Tensor:
+    def act_tiled(self, tiled_u8: torch.Tensor, low_dim_state: torch.Tensor, lang_tokens: Optional[torch.Tensor], step=0) -> torch.Tensor:
         """Device-resident fast path of eval_genima.py:224-247: the pipeline's uint8 tiled output [B, 2v, 2v, 3] is untiled on
-        the device (crop order of controller/utils/misc.py:25-30 -> camera order of the tile) and fed straight to the policy."""
+        the device (crop order of controller/utils/misc.py:25-30 -> camera order of the tile) and fed straight to the policy.
+        Under ``set_execution``: f32 [B, h, A] for the environment steps ``step .. step + h - 1`` (``step``: an int or an int tensor [B];
+        as in ``act``, host steps are range-checked and a device tensor is the caller's to keep >= 0 -- a negative step gives NaN actions)."""
         B, H2, W2, _ = tiled_u8.shape
         v = H2 // 2
         img = torch.stack([tiled_u8[:, y:y + v, x:x + v] for (x, y) in ((0, 0), (v, 0), (0, v), (v, v))], dim=1)  # layout only
-        io = self._run(img, low_dim_state.to(self.device).flatten(1), lang_tokens)
+        io = self._run(img, low_dim_state.to(self.device).flatten(1), lang_tokens, step)
+        if io.exec is not None:
+            return io.ens_out
         return io.a_hat[..., : self.config["action_dim"]]
 
     def update(self, replay_iter, step: int = 0, replay_buffer=None, **trainer_kw) -> Dict[str, float]:
@@ -591,8 +723,12 @@ class GenimaACT:
         self._dirty = self._stale_host = True
         return metrics
 
-    def act(self, obs: Dict[str, torch.Tensor], step: int = 0, eval_mode: bool = True) -> torch.Tensor:
-        """obs: {'<cam>_rgb': uint8/float [B, fs, 3, H, W], 'low_dim_state': f32 [B, fs, state], 'lang_tokens': int [B, fs, 77]}."""
+    def act(self, obs: Dict[str, torch.Tensor], step=0, eval_mode: bool = True) -> torch.Tensor:
+        """obs: {'<cam>_rgb': uint8/float [B, fs, 3, H, W], 'low_dim_state': f32 [B, fs, state], 'lang_tokens': int [B, fs, 77]}.
+        -> f32 [B, num_queries, A]; under ``set_execution`` f32 [B, h, A], the actions of the environment steps ``step .. step + h - 1``
+        (``step``: an int for all rows or an int tensor [B]; it is not read otherwise).  Host steps are checked (0 <= step, and
+        step + num_queries < 2^31); a device tensor is used as it is, without a read-back, so its range is the caller's to keep: a negative
+        step marks the new chunk's slot as empty and gives NaN actions for that row (no memory is touched out of bounds)."""
         if getattr(self, "_dirty", False):  # weights moved by update(): re-pack once before acting
             self._own_state()
             self.W = pack_act(self._sd, self.device)
@@ -605,5 +741,7 @@ class GenimaACT:
         img_u8 = image.round().clamp(0, 255).to(torch.uint8) if image.dtype != torch.uint8 else image
         img_u8 = img_u8.permute(0, 1, 3, 4, 2).contiguous()
         toks = obs.get("lang_tokens") if self.config.get("use_lang_cond") else None
-        io = self._run(img_u8, qpos, toks)
+        io = self._run(img_u8, qpos, toks, step)
+        if io.exec is not None:
+            return io.ens_out.clone()
         return io.a_hat[..., : self.config["action_dim"]].to(torch.float32)

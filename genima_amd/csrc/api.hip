@@ -21,7 +21,7 @@ namespace {
 enum OpType {
   OP_GEMM = 0, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_TEMB, OP_SCALE_PAD, OP_EULER, OP_F16_TO_U8, OP_U8_TO_F16, OP_ADD,
   OP_ACT, OP_EMBED, OP_SOFTMAX, OP_MAXPOOL, OP_NORMALIZE_U8, OP_GATHER_ROWS, OP_COPY4D, OP_ARGMAX, OP_ADD_NOISE, OP_FILM, OP_SCALE_CAT_PAD,
-  OP_TBLOCK, OP_CONV_GN, OP_ADD_MULTI, OP_MEMSET, OP_TINY_BLOCK,
+  OP_TBLOCK, OP_CONV_GN, OP_ADD_MULTI, OP_MEMSET, OP_TINY_BLOCK, OP_ACTION_ENSEMBLE,
   OP_FORK, OP_MAIN, OP_JOIN  // stream control: ops after FORK go to the program's side stream until MAIN; JOIN makes main wait for it
 };
 
@@ -122,6 +122,9 @@ static int32_t run_op(gn_ctx* ctx, const Op& op) {
       const void* bias[3] = {(const void*)(uintptr_t)g.m[3], (const void*)(uintptr_t)g.m[4], (const void*)(uintptr_t)g.m[5]};
       return gn_tiny_block(ctx, g.p0, w, bias, g.p3, g.i0, g.i1, g.i2, g.i3);
     }
+    case OP_ACTION_ENSEMBLE:  // m[0]: the state blob, m[1]: chunk is f16
+      if (g.m[1]) return gn_action_ensemble_f16(ctx, g.p0, (void*)(uintptr_t)g.m[0], (const int32_t*)g.p1, (const uint8_t*)g.p2, (float*)g.p3, g.i0, g.i1, g.i2, g.i3, (int32_t)g.n0, (int32_t)g.n1, g.f0);
+      return gn_action_ensemble(ctx, (const float*)g.p0, (void*)(uintptr_t)g.m[0], (const int32_t*)g.p1, (const uint8_t*)g.p2, (float*)g.p3, g.i0, g.i1, g.i2, g.i3, (int32_t)g.n0, (int32_t)g.n1, g.f0);
     case OP_ADD_NOISE: return gn_add_noise(ctx, g.p0, g.p1, (const float*)g.p2, (const float*)(uintptr_t)g.m[0], g.p3, g.i0, g.n0);
     default: gn_set_error("gn_program: unknown op type %d", op.type); return GN_ERR_INVALID;
   }
@@ -344,6 +347,16 @@ int32_t gn_program_add_add_noise(gn_program* p, const void* x0, const void* nois
                                  int64_t per_sample) {
   const int32_t rc = push_generic(p, OP_ADD_NOISE, x0, noise, sqrt_ac, out, per_sample, 0, B, 0, 0, 0, 0.f, 0.f);
   if (rc == GN_OK) p->ops.back().g.m[0] = (int64_t)(uintptr_t)sqrt_1mac;
+  return rc;
+}
+int32_t gn_program_add_action_ensemble(gn_program* p, const void* chunk, int32_t chunk_f16, void* state, const int32_t* steps, const uint8_t* reset, float* out,
+                                       int32_t B, int32_t T, int32_t A, int32_t ld, int32_t K, int32_t h, float m) {
+  // the arguments that make the launch refuse are refused here, not at the first replay (possibly in the middle of a hipGraph capture)
+  GN_REQUIRE(chunk && state && steps && reset && out && B > 0 && T > 0 && A > 0 && ld >= A && h >= 1 && h <= T && (K == 1 || K >= (T + h - 1) / h) && m >= 0.f &&
+                 gn_action_ensemble_state_bytes(B, T, A, K) > 0,
+             "gn_program_add_action_ensemble: bad arguments (B %d, T %d, A %d, ld %d, K %d, h %d, m %g)", B, T, A, ld, K, h, (double)m);
+  const int32_t rc = push_generic(p, OP_ACTION_ENSEMBLE, chunk, steps, reset, out, K, h, B, T, A, ld, m, 0.f);
+  if (rc == GN_OK) { p->ops.back().g.m[0] = (int64_t)(uintptr_t)state; p->ops.back().g.m[1] = chunk_f16 ? 1 : 0; }
   return rc;
 }
 int32_t gn_program_add_fork(gn_program* p) { return push_generic(p, OP_FORK, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0.f, 0.f); }

@@ -1446,3 +1446,45 @@ class Engine:
         out = self.buf(name, (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc))
         self._small("maxpool3x3s2", (x, out), _ptr(x), _ptr(out), B, H, W, Cc)
         return out
+
+    # ------------------------------------------------------------------------------------------------ action-chunk ensembling
+    def action_ensemble_state(self, B: int, T: int, A: int, K: int) -> torch.Tensor:
+        """The zeroed state blob of ``action_ensemble`` (gn_action_ensemble_state_bytes): every row's ring empty."""
+        nbytes = int(self.lib.gn_action_ensemble_state_bytes(int(B), int(T), int(A), int(K)))
+        if nbytes <= 0:
+            raise GenimaHipError(f"action_ensemble_state: bad shape (B {B}, T {T}, A {A}, K {K})")
+        return torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def action_ensemble(self, chunk: torch.Tensor, state: torch.Tensor, steps: torch.Tensor, reset: torch.Tensor, h: int, K: int, m: float = 0.01, *,
+                        A: Optional[int] = None, out=None, name=None) -> torch.Tensor:
+        """Temporal ensembling of overlapping action chunks (csrc/ensemble.hip; include/genima_hip.h states the rule): chunk f32 or f16
+        [B, T, ld] of which the first ``A`` columns count, state from ``action_ensemble_state(B, T, A, K)``, steps int32 [B] and reset uint8 [B]
+        on the device -> f32 [B, h, A], the actions of the environment steps ``steps[b] .. steps[b] + h - 1``.  The launch updates ``state``:
+        recorded, it belongs outside every guarded segment (it has to run on every replay), and between replays only the contents of
+        ``steps`` / ``reset`` change."""
+        B, T, ld = chunk.shape
+        A = ld if A is None else int(A)
+        if chunk.dtype not in (torch.float32, F16) or chunk.stride(2) != 1 or chunk.stride(0) != T * chunk.stride(1):
+            raise GenimaHipError("action_ensemble: chunk must be f32 / f16 [B, T, ld] with contiguous rows of one pitch")
+        ld = chunk.stride(1)
+        if self._seg_open is not None:
+            raise GenimaHipError(f"action_ensemble: recorded inside segment {self._seg_open!r}; its state advances on every call, so it cannot be skipped")
+        need = int(self.lib.gn_action_ensemble_state_bytes(B, T, A, int(K)))
+        if (steps.dtype != torch.int32 or reset.dtype != torch.uint8 or steps.numel() != B or reset.numel() != B or state.dtype != torch.uint8
+                or not (steps.is_contiguous() and reset.is_contiguous() and state.is_contiguous()) or need <= 0 or state.numel() < need):
+            raise GenimaHipError(f"action_ensemble: steps int32 [{B}], reset uint8 [{B}], state uint8 [>= {need}] expected (K {K})")
+        if out is None:
+            out = self.buf(name, (B, max(int(h), 1), A), dtype=torch.float32)  # (h < 1 is the library's to refuse)
+        else:
+            self._wrote(out)
+        self._wrote(state)
+        args = (_ptr(state), _ptr(steps), _ptr(reset), _ptr(out), B, T, A, ld, int(K), int(h), float(m))
+        f16 = chunk.dtype == F16
+        if self.record:
+            check(self.lib.gn_program_add_action_ensemble(self._prog, _ptr(chunk), int(f16), *args), "gn_program_add_action_ensemble")
+            self._keepalive(chunk, state, steps, reset, out)
+            self.meta.append(dict(kind="action_ensemble", flops=0.0, bytes=float(4 * B * A * (T + K * h + h) + chunk.element_size() * B * T * A), shape=()))
+        else:
+            fn = self.lib.gn_action_ensemble_f16 if f16 else self.lib.gn_action_ensemble
+            check(fn(self._ctx, _ptr(chunk), *args), "gn_action_ensemble")
+        return out

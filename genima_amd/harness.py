@@ -30,10 +30,17 @@ def make_prompt(goal: str) -> str:
 
 
 def control_step(diffusion_agent, controller_agent, obs: Dict[str, np.ndarray], goal: str, cameras: Sequence[str], num_frames: int,
-                 generator: List[torch.Generator], num_diffusion_steps: int, guidance_scale: float, device, episode_step: int = 0):
+                 generator: List[torch.Generator], num_diffusion_steps: int, guidance_scale: float, device, episode_step: int = 0,
+                 execution_horizon=None, temporal_agg: bool = False):
     """obs: ``{'<cam>_rgb': uint8 [fs, 3, 256, 256], 'low_dim_state': f32 [fs, S], 'lang_tokens': int [fs, 1|.., 77], ...}`` as the
     RoboBase env wrapper hands it over.  Returns ``(actions np.float32 [queries, action_dim], obs_after, tiled_in, tiled_out)``;
-    ``obs_after`` holds the device tensors the controller saw (camera images replaced by the generated joint-target views)."""
+    ``obs_after`` holds the device tensors the controller saw (camera images replaced by the generated joint-target views).
+    ``execution_horizon`` / ``temporal_agg`` (controller/cfgs/eval_genima.yaml:29,33 -- knobs the reference's loop never reads): the
+    controller returns the ``h = execution_horizon`` actions of the environment steps ``episode_step .. episode_step + h - 1``, ensembled over
+    the overlapping chunks of the earlier calls with ``temporal_agg`` (GenimaACT.set_execution); ``actions`` is then ``[h, action_dim]``, the loop
+    executes all of them and calls again with ``episode_step + h``.  ``episode_step == 0`` starts a new history.  The arguments are
+    passed on with ``set_execution`` where the controller's mode (``GenimaACT.execution``) differs from them.  With neither argument given the
+    controller is not touched: it returns what its own mode says (by default the whole chunk, as before)."""
     from PIL import Image
 
     rgbs = [Image.fromarray(np.transpose(obs[f"{cam}_rgb"][t], (1, 2, 0))) for cam in cameras for t in range(num_frames)]
@@ -50,6 +57,14 @@ def control_step(diffusion_agent, controller_agent, obs: Dict[str, np.ndarray], 
         for cam in OVERWRITTEN_CAMERAS:
             obs[f"{cam}_rgb"] = untiled[cam]
         obs_dev = {k: torch.from_numpy(np.asarray(v)).to(device).unsqueeze(0) for k, v in obs.items()}
+        if execution_horizon is not None or temporal_agg:
+            from .act import execution_slots
+
+            if controller_agent.execution is None or controller_agent.execution[:2] != execution_slots(
+                    int(controller_agent.config["num_queries"]), execution_horizon, temporal_agg):
+                controller_agent.set_execution(execution_horizon, temporal_agg)  # (starts with an empty history)
+            elif episode_step == 0:
+                controller_agent.reset_execution()
         actions = controller_agent.act(obs_dev, step=episode_step, eval_mode=True)[0]
     return actions.detach().float().cpu().numpy(), obs_dev, tiled_in, tiled_out
 

@@ -482,6 +482,28 @@ int32_t gn_softmax_rows(gn_ctx* ctx, void* x, int64_t rows, int32_t cols, int32_
 int32_t gn_softmax_rows_masked(gn_ctx* ctx, void* x, int64_t rows, int32_t cols, int32_t ld, float scale, int32_t valid);
 int32_t gn_maxpool3x3s2(gn_ctx* ctx, const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C);
 
+/* ---- temporal ensembling of action chunks (the `execution_horizon` / `temporal_agg` knobs of controller/cfgs/eval_genima.yaml:29,33, which the
+ * reference never reads: controller/eval_genima.py:261-263; the rule is the ACT paper's, generalised from one executed action per call to h) ----
+ * chunk  f32 [B, T, ld] (gn_action_ensemble) or f16 [B, T, ld] (gn_action_ensemble_f16: the controller's a_hat as its head writes it; every f16
+ *        is an f32, so the two agree bit for bit on equal values); ld >= A is the row pitch, only the first A columns are read
+ * state  gn_action_ensemble_state_bytes(B, T, A, K) bytes (-1: bad shape), 16-byte aligned, zeroed ONCE by the caller (a zeroed row is an empty
+ *        one).  Per row: the last K chunks as f32 [K, T, A], the environment step each slot's chunk starts at (int32, -1 = empty), the ring head
+ * steps  int32 [B] on the device: the current environment step t >= 0 of each row
+ * reset  uint8 [B] on the device: non-zero empties that row's ring before the new chunk goes in
+ * out    f32 [B, h, A]: the actions of the environment steps t .. t + h - 1
+ * The new chunk replaces the oldest slot, with start t.  For a target step s every slot with 0 <= s - start < T takes part; those slots in
+ * order of insertion (i = 0: the oldest; the order of their starts as long as steps do not go backwards between resets) get the weights
+ * w_i = exp(-m i), and out[s] = sum_i w_i chunk_i[s - start_i] / sum_i w_i, summed in f32 from the oldest to the newest -- the same bits on every
+ * run.  Every one of the A dimensions is averaged alike, the gripper's included (the reference gives no other rule).  K >= ceil(T / h) holds every
+ * chunk that can still cover a step when t advances by h per call; a smaller K is refused -- except K = 1, the ring of the new chunk alone
+ * (temporal_agg off): out = chunk[:, :h, :A] bit for bit.
+ * One launch, one workgroup per row, plain loads and stores; between replays of a recorded program only the contents of steps / reset change. */
+int64_t gn_action_ensemble_state_bytes(int32_t B, int32_t T, int32_t A, int32_t K);
+int32_t gn_action_ensemble(gn_ctx* ctx, const float* chunk, void* state, const int32_t* steps, const uint8_t* reset, float* out, int32_t B, int32_t T,
+                           int32_t A, int32_t ld, int32_t K, int32_t h, float m);
+int32_t gn_action_ensemble_f16(gn_ctx* ctx, const void* chunk, void* state, const int32_t* steps, const uint8_t* reset, float* out, int32_t B, int32_t T,
+                               int32_t A, int32_t ld, int32_t K, int32_t h, float m);
+
 /* ---- training-side kernels (ControlNet fine-tune step, diffusion/train_controlnet_genima.py:1317-1408) ----------
  * The backward matrix products reuse gn_gemm: dX = dY.W through a transposed weight copy, dW = dY^T.X through transposed
  * activations with GN_OUT_F32 + split-K, conv dgrad = conv with rotated weights, conv wgrad = GEMM over gn_im2col_t's image.
@@ -695,6 +717,8 @@ int32_t gn_program_add_embedding(gn_program* p, const int32_t* ids, const void* 
                                  int32_t B, int32_t L, int32_t D);
 int32_t gn_program_add_softmax_rows(gn_program* p, void* x, int64_t rows, int32_t cols, int32_t ld, float scale);
 int32_t gn_program_add_maxpool3x3s2(gn_program* p, const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C);
+int32_t gn_program_add_action_ensemble(gn_program* p, const void* chunk, int32_t chunk_f16, void* state, const int32_t* steps, const uint8_t* reset,
+                                       float* out, int32_t B, int32_t T, int32_t A, int32_t ld, int32_t K, int32_t h, float m);
 int32_t gn_program_add_image_normalize_u8(gn_program* p, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float m0,
                                           float m1, float m2, float a0, float a1, float a2);
 int32_t gn_program_add_gather_rows(gn_program* p, const void* x, const int32_t* idx, void* out, int32_t B, int32_t L, int32_t D);
