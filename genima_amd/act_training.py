@@ -357,9 +357,11 @@ class ACTTrainer:
         return unpack_state_dict(self.cn.packed_master(), OrderedDict((k, sch[k]) for k in self.names))
 
 
-def elastic_displacement(H: int, W: int, alpha: float = 80.0, sigma: float = 10.0, generator: Optional[torch.Generator] = None) -> torch.Tensor:
-    """torchvision v2.ElasticTransform._get_params: per axis, uniform [-1, 1) noise, Gaussian blur (kernel int(8 sigma + 1) made odd,
-    reflect padding) and a scale of alpha / size -- in the normalised [-1, 1] grid units, converted here to pixels (x (size - 1) / 2).
+def elastic_field(H: int, W: int, alpha: float = 80.0, sigma: float = 10.0, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """torchvision v2.ElasticTransform._get_params: per axis (dx first, then dy), uniform [-1, 1) noise, Gaussian blur (kernel
+    int(8 sigma + 1) made odd, reflect padding) and a scale of alpha / size -> f64 [H, W, 2] = (dx, dy) in the normalised [-1, 1] grid
+    units that torchvision adds to its identity grid.  torchvision scales dx by alpha / size[0] (the height) and dy by alpha / size[1];
+    here dx is scaled by the width and dy by the height -- ACT images are square, so the two never differ.
     Host work on one [H, W] field per call (the transform is called on the whole batch: one field for every image)."""
     import numpy as np
     from numpy.lib.stride_tricks import sliding_window_view
@@ -378,8 +380,16 @@ def elastic_displacement(H: int, W: int, alpha: float = 80.0, sigma: float = 10.
         f = np.pad(f, pad, mode="reflect")
         f = sliding_window_view(f, k, axis=1) @ ker   # along W
         f = sliding_window_view(f, k, axis=0) @ ker   # along H
-        out.append(torch.from_numpy((f * alpha / size) * (size - 1) * 0.5))
-    return torch.stack(out, dim=-1).float().contiguous()  # [H, W, 2] = (dx, dy) in pixels
+        out.append(torch.from_numpy(f * alpha / size))
+    return torch.stack(out, dim=-1).contiguous()
+
+
+def elastic_displacement(H: int, W: int, alpha: float = 80.0, sigma: float = 10.0, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``elastic_field`` in pixels, f32 [H, W, 2] = (dx, dy): what gn_warp_bilinear takes.  torchvision samples with
+    grid_sample(identity + field, align_corners=False) over the identity grid linspace((1 - s) / s, (s - 1) / s, s); that convention maps
+    a grid value g to the pixel ((g + 1) s - 1) / 2, so a normalised displacement d moves the sample by d * s / 2 pixels."""
+    px = torch.tensor([W * 0.5, H * 0.5], dtype=torch.float64)
+    return (elastic_field(H, W, alpha, sigma, generator) * px).float().contiguous()
 
 
 def act_augment(E: Engine, images_u8: torch.Tensor, generator: Optional[torch.Generator] = None, p: float = 0.5, noise_std: float = 5.0):
