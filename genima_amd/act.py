@@ -688,7 +688,8 @@ class GenimaACT:
         """``GenimaACT.update`` (controller/method/genima_act.py:348-422): one behaviour-cloning step on ``next(replay_iter)`` -- a dict
         with ``action`` [B, T, A], ``low_dim_state`` [B, fs, S], the ``*rgb*`` camera tensors [B, fs, 3, H, W] (``tp1`` keys ignored),
         ``lang_tokens`` [B, fs, 77] and ``reward``.  The trainer (act_training.ACTTrainer: CVAE posterior, loss, tape backward, two-group
-        AdamW) is built on first use from this agent's weights; train-time augmentation runs when ``data_augmentation`` is on."""
+        AdamW) is built on first use from this agent's weights; train-time augmentation runs when ``data_augmentation`` is on (config key
+        ``elastic_field``: "host", the default, or "device" -- where the elastic warp's displacement field is blurred)."""
         from .act_training import ACTTrainer, act_augment, act_train_schema
 
         if getattr(self, "_trainer", None) is None:
@@ -714,7 +715,7 @@ class GenimaACT:
         if self.config.get("use_lang_cond"):
             task, _ = self.encode_clip_text(batch["lang_tokens"])
         tr = self._trainer
-        imgs = act_augment(tr.E, img_u8, self._aug_gen) if self.config.get("data_augmentation", True) else img_u8
+        imgs = act_augment(tr.E, img_u8, self._aug_gen, field=self.config.get("elastic_field", "host")) if self.config.get("data_augmentation", True) else img_u8
         metrics = tr.update(imgs, qpos, task, batch["action"].float())
         if "reward" in batch:
             metrics["batch_reward"] = float(batch["reward"].float().mean())

@@ -357,6 +357,16 @@ class ACTTrainer:
         return unpack_state_dict(self.cn.packed_master(), OrderedDict((k, sch[k]) for k in self.names))
 
 
+def elastic_taps(sigma: float) -> torch.Tensor:
+    """The 1-D Gaussian taps of ElasticTransform's blur as torchvision builds them: k = int(8 sigma + 1) made odd, then an f32
+    linspace / exp / normalise -> f32 [k].  The host and the device route of the field both use these."""
+    k = int(8 * sigma + 1)
+    k += (k % 2 == 0)
+    half = (k - 1) * 0.5
+    pdf = torch.exp(-0.5 * (torch.linspace(-half, half, k) / sigma) ** 2)  # (torchvision builds the kernel in f32)
+    return pdf / pdf.sum()
+
+
 def elastic_field(H: int, W: int, alpha: float = 80.0, sigma: float = 10.0, generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """torchvision v2.ElasticTransform._get_params: per axis (dx first, then dy), uniform [-1, 1) noise, Gaussian blur (kernel
     int(8 sigma + 1) made odd, reflect padding) and a scale of alpha / size -> f64 [H, W, 2] = (dx, dy) in the normalised [-1, 1] grid
@@ -366,11 +376,9 @@ def elastic_field(H: int, W: int, alpha: float = 80.0, sigma: float = 10.0, gene
     import numpy as np
     from numpy.lib.stride_tricks import sliding_window_view
 
-    k = int(8 * sigma + 1)
-    k += (k % 2 == 0)
-    half = (k - 1) * 0.5
-    pdf = torch.exp(-0.5 * (torch.linspace(-half, half, k) / sigma) ** 2)  # (torchvision builds the kernel in f32)
-    ker = (pdf / pdf.sum()).double().numpy()
+    ker = elastic_taps(sigma)
+    k = ker.numel()
+    ker = ker.double().numpy()
     out = []
     for size, n in ((W, (H, W)), (H, (H, W))):
         # the draw stays torch's (the generator's stream is part of the recipe); the separable blur of ONE [H, W] field is host arithmetic
@@ -392,19 +400,47 @@ def elastic_displacement(H: int, W: int, alpha: float = 80.0, sigma: float = 10.
     return (elastic_field(H, W, alpha, sigma, generator) * px).float().contiguous()
 
 
-def act_augment(E: Engine, images_u8: torch.Tensor, generator: Optional[torch.Generator] = None, p: float = 0.5, noise_std: float = 5.0):
+def elastic_displacement_device(E: Engine, H: int, W: int, alpha: float = 80.0, sigma: float = 10.0,
+                                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``elastic_displacement`` with the blur on the device (gn_elastic_field): the two noise planes are drawn from the CPU generator by
+    ``elastic_field``'s own calls in its order (dx, then dy), uploaded in one copy and blurred, scaled and interleaved in f32 ->
+    device f32 [H, W, 2] = (dx, dy) in pixels.  The scales are elastic_field's alpha / size times elastic_displacement's size / 2."""
+    import ctypes as C
+
+    from ._lib import check
+
+    taps = elastic_taps(sigma)
+    k = taps.numel()
+    noise = torch.cat([torch.rand([1, 1, H, W], generator=generator) * 2 - 1 for _ in range(2)], dim=1)[0]  # [2, H, W]: dx, dy
+    noise = noise.to(E.device)
+    disp = torch.empty((H, W, 2), dtype=F32, device=E.device)
+    ws = E._workspace(int(E.lib.gn_elastic_field_workspace_bytes(H, W)))
+    check(E.lib.gn_elastic_field(E._ctx, noise.data_ptr(), disp.data_ptr(), ws.data_ptr(), H, W, k, (C.c_float * k)(*taps.tolist()),
+                                 (alpha / W) * (W / 2), (alpha / H) * (H / 2)), "gn_elastic_field")
+    return disp
+
+
+def act_augment(E: Engine, images_u8: torch.Tensor, generator: Optional[torch.Generator] = None, p: float = 0.5, noise_std: float = 5.0,
+                field: str = "host"):
     """``GenimaACTPolicy.aug_transforms`` (controller/method/genima_act.py:150-163) on uint8 [B, V, H, W, 3] device images:
     RandomApply(p)[ElasticTransform(80, 10)], RandomApply(p)[ColorJitter(0.2, 0.2, 0.1, 0.05)], RandomApply(p)[RandomCrop(size, padding
     = 4)] -- each called on the whole batch tensor, so ONE draw per call -- then AddGaussianNoise(0, 5.0) on the 0..255 scale
     (controller/utils/misc.py:50-65).  Returns f16 [B, V, H, W, 8] on the 0..1 scale (the trainer's float-image input).  The random
-    draws use ``generator`` (a CPU generator) in torchvision's order; the pixel work runs in HIP kernels."""
+    draws use ``generator`` (a CPU generator) in torchvision's order; the pixel work runs in HIP kernels.  ``field``: where the elastic
+    displacement field is blurred -- "host" (f64 numpy, ``elastic_displacement``) or "device" (f32, ``elastic_displacement_device``); both
+    consume the generator identically."""
     from . import augment as A
     from ._lib import check
 
+    if field not in ("host", "device"):
+        raise ValueError(f"act_augment: field must be 'host' or 'device', got {field!r}")
     B, V, H, W, _ = images_u8.shape
     x = E.image_u8_to_f16(images_u8.view(B * V, H, W, 3), 8, 1.0, 0.0)
     if float(torch.rand(1, generator=generator)) < p:
-        disp = elastic_displacement(H, W, generator=generator).to(E.device)
+        if field == "device":
+            disp = elastic_displacement_device(E, H, W, generator=generator)
+        else:
+            disp = elastic_displacement(H, W, generator=generator).to(E.device)
         y = torch.empty_like(x)
         check(E.lib.gn_warp_bilinear(E._ctx, x.data_ptr(), y.data_ptr(), disp.data_ptr(), B * V, H, W, 8), "gn_warp_bilinear")
         x = y

@@ -145,6 +145,89 @@ __global__ void warp_bilinear_kernel(const f16* __restrict__ in, f16* __restrict
   *reinterpret_cast<uint4*>(out + i * 8) = *reinterpret_cast<uint4*>(&o);
 }
 
+// ElasticTransform's displacement field (torchvision v2.ElasticTransform._get_params): two [H, W] noise planes, each reflect-padded by
+// R = ksize / 2 and blurred with the separable ksize-tap Gaussian -- along W into a workspace plane, then along H -- scaled and interleaved
+// to [H, W, 2].  Both passes stage their source strip (tile + halo, reflected) in LDS with loads that run along W, so the ksize reads per
+// output are LDS reads; a wave's 64 lanes read 64 consecutive floats of one LDS row (no bank conflict) and every tap is a broadcast read
+// that feeds EL_W_ROWS / EL_H_ROWS FMAs.  f32 FMAs in tap order 0 .. ksize - 1: the same bits on every run.
+constexpr int EL_MAX_K = 129;                     // ksize <= 129 (sigma <= 16)
+constexpr int EL_COLS = 64;                       // tile width of both passes: one wave per LDS row
+constexpr int EL_W_ROWS = 4, EL_W_TILE = 4 * EL_W_ROWS;  // W pass: 256 threads = 64 columns x 4 waves, each wave EL_W_ROWS rows (w, w + 4, ..)
+constexpr int EL_H_ROWS = 8, EL_H_TILE = 4 * EL_H_ROWS;  // H pass: each wave EL_H_ROWS consecutive rows of a 32-row tile; the halo bounds the
+                                                         // strip at EL_H_TILE + 2 R rows whatever H is
+struct ElasticP {
+  float k[EL_MAX_K];  // 1-D taps, k[0 .. ksize - 1]
+};
+// reflect padding's source index for i in [-(n - 1), 2 n - 2] (one reflection)
+__device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+
+// tmp[p, y, x] = sum_t k[t] * noise[p, y, refl(x + t - R)];  grid (ceil(W / 64), ceil(H / 16), 2)
+__global__ __launch_bounds__(256) void elastic_blur_w_kernel(const float* __restrict__ noise, float* __restrict__ tmp, int H, int W, int ksize, ElasticP p) {
+  __shared__ float s[EL_W_TILE * (EL_COLS + EL_MAX_K - 1)];
+  __shared__ float taps[EL_MAX_K];
+  const int R = ksize / 2, SW = EL_COLS + 2 * R;
+  const int x0 = blockIdx.x * EL_COLS, y0 = blockIdx.y * EL_W_TILE;
+  const float* src = noise + (long)blockIdx.z * H * W;
+  for (int i = threadIdx.x; i < ksize; i += 256) taps[i] = p.k[i];
+  for (int i = threadIdx.x; i < EL_W_TILE * SW; i += 256) {
+    const int r = i / SW, c = i - r * SW;
+    const int y = y0 + r, sx = x0 + c - R;  // past the image (a partial tile): 0, read only by outputs that are not stored
+    s[i] = (y < H && sx <= W - 1 + R) ? src[(long)y * W + reflect1(sx, W)] : 0.0f;
+  }
+  __syncthreads();
+  const int c = threadIdx.x % EL_COLS, w = threadIdx.x / EL_COLS;
+  float acc[EL_W_ROWS];
+#pragma unroll
+  for (int j = 0; j < EL_W_ROWS; ++j) acc[j] = 0.0f;
+  for (int t = 0; t < ksize; ++t) {
+    const float k = taps[t];
+#pragma unroll
+    for (int j = 0; j < EL_W_ROWS; ++j) acc[j] = fmaf(k, s[(w + 4 * j) * SW + c + t], acc[j]);
+  }
+  const int x = x0 + c;
+#pragma unroll
+  for (int j = 0; j < EL_W_ROWS; ++j) {
+    const int y = y0 + w + 4 * j;
+    if (x < W && y < H) tmp[((long)blockIdx.z * H + y) * W + x] = acc[j];
+  }
+}
+
+// disp[y, x, p] = scale[p] * sum_t k[t] * tmp[p, refl(y + t - R), x];  grid (ceil(W / 64), ceil(H / 32)); the two planes one after the
+// other through the same LDS strip, so that each lane stores its (dx, dy) pair as one 8-byte word
+__global__ __launch_bounds__(256) void elastic_blur_h_kernel(const float* __restrict__ tmp, float2* __restrict__ disp, int H, int W, int ksize, ElasticP p,
+                                                             float scale_x, float scale_y) {
+  __shared__ float s[(EL_H_TILE + EL_MAX_K - 1) * EL_COLS];
+  __shared__ float taps[EL_MAX_K];
+  const int R = ksize / 2;
+  const int x0 = blockIdx.x * EL_COLS, y0 = blockIdx.y * EL_H_TILE;
+  const int c = threadIdx.x % EL_COLS, w = threadIdx.x / EL_COLS;
+  for (int i = threadIdx.x; i < ksize; i += 256) taps[i] = p.k[i];
+  float acc[2][EL_H_ROWS];
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl) {
+    const float* src = tmp + (long)pl * H * W;
+    if (pl) __syncthreads();  // plane 0's reads are done before the strip is overwritten
+    for (int i = threadIdx.x; i < (EL_H_TILE + 2 * R) * EL_COLS; i += 256) {
+      const int sy = y0 + i / EL_COLS - R, x = x0 + i % EL_COLS;
+      s[i] = (x < W && sy <= H - 1 + R) ? src[(long)reflect1(sy, H) * W + x] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < EL_H_ROWS; ++j) acc[pl][j] = 0.0f;
+    for (int t = 0; t < ksize; ++t) {
+      const float k = taps[t];
+#pragma unroll
+      for (int j = 0; j < EL_H_ROWS; ++j) acc[pl][j] = fmaf(k, s[(w * EL_H_ROWS + j + t) * EL_COLS + c], acc[pl][j]);
+    }
+  }
+  const int x = x0 + c;
+#pragma unroll
+  for (int j = 0; j < EL_H_ROWS; ++j) {
+    const int y = y0 + w * EL_H_ROWS + j;
+    if (x < W && y < H) disp[(long)y * W + x] = make_float2(acc[0][j] * scale_x, acc[1][j] * scale_y);
+  }
+}
+
 // f32 -> f16 add of per-(b, c) sums into a feature gradient  y[i] += a * x[i] is not needed; what IS needed: f32 -> f16 add of per-(b, c) sums into a feature gradient
 __global__ void add_f32_to_f16_kernel(const float* __restrict__ src, long ld_src, f16* __restrict__ dst, long ld_dst, int B, int C) {
   const long i = gtid();
@@ -207,6 +290,30 @@ int32_t gn_warp_bilinear(gn_ctx* ctx, const void* in, void* out, const float* di
   GN_REQUIRE(ctx && in && out && disp && in != out && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "gn_warp_bilinear: bad arguments (C %% 8, no aliasing)");
   const long n = (long)B * H * W * (C / 8);
   hipLaunchKernelGGL(warp_bilinear_kernel, dim3(nblk(n)), dim3(256), 0, ctx->stream, (const f16*)in, (f16*)out, disp, B, H, W, C / 8);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int64_t gn_elastic_field_workspace_bytes(int32_t H, int32_t W) { return H > 0 && W > 0 ? (int64_t)2 * H * W * 4 : 0; }
+
+/* noise f32 [2][H][W] -> disp f32 [H][W][2] = (scale_x * blur(noise[0]), scale_y * blur(noise[1])): reflect padding by ksize / 2, the ksize
+ * host taps along W, then along H.  workspace: gn_elastic_field_workspace_bytes(H, W), the plane between the passes. */
+int32_t gn_elastic_field(gn_ctx* ctx, const float* noise, float* disp, void* workspace, int32_t H, int32_t W, int32_t ksize, const float* taps,
+                         float scale_x, float scale_y) {
+  GN_REQUIRE(ctx && noise && disp && workspace && taps, "gn_elastic_field: null argument");
+  GN_REQUIRE((const void*)noise != (const void*)disp && (const void*)noise != workspace && (const void*)disp != workspace,
+             "gn_elastic_field: noise, disp and workspace must not alias");
+  GN_REQUIRE(((uintptr_t)noise | (uintptr_t)workspace) % 4 == 0 && (uintptr_t)disp % 8 == 0, "gn_elastic_field: disp must be 8-byte aligned");
+  GN_REQUIRE(ksize >= 3 && ksize <= EL_MAX_K && ksize % 2 == 1, "gn_elastic_field: ksize must be odd, 3..129");
+  GN_REQUIRE(H > ksize / 2 && W > ksize / 2, "gn_elastic_field: reflect padding needs H, W > ksize / 2");
+  ElasticP p{};
+  for (int i = 0; i < ksize; ++i) p.k[i] = taps[i];
+  const unsigned gx = (unsigned)((W + EL_COLS - 1) / EL_COLS);
+  hipLaunchKernelGGL(elastic_blur_w_kernel, dim3(gx, (unsigned)((H + EL_W_TILE - 1) / EL_W_TILE), 2), dim3(256), 0, ctx->stream, noise,
+                     (float*)workspace, H, W, ksize, p);
+  GN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(elastic_blur_h_kernel, dim3(gx, (unsigned)((H + EL_H_TILE - 1) / EL_H_TILE)), dim3(256), 0, ctx->stream,
+                     (const float*)workspace, (float2*)disp, H, W, ksize, p, scale_x, scale_y);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

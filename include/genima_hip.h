@@ -794,6 +794,15 @@ int32_t gn_add_f32_to_f16(gn_ctx* ctx, const float* src, int64_t ld_src, void* d
 /* train-time ElasticTransform of the ACT policy (controller/method/genima_act.py:150-163): bilinear warp of NHWC f16 [B, H, W, C] by one
  * displacement field disp f32 [H][W][2] = (dx, dy) in pixels shared by the batch; samples outside the image read 0 */
 int32_t gn_warp_bilinear(gn_ctx* ctx, const void* in, void* out, const float* disp, int32_t B, int32_t H, int32_t W, int32_t C);
+/* the displacement field of that ElasticTransform (torchvision v2.ElasticTransform._get_params): noise f32 [2][H][W] on the device, plane 0
+ * the dx draw and plane 1 the dy draw in [-1, 1) -> disp f32 [H][W][2] = (dx, dy) in pixels, the layout gn_warp_bilinear takes.  Each plane
+ * is reflect-padded by ksize / 2 (one reflection: H, W > ksize / 2), convolved along W and then along H with the ksize host f32 taps
+ * (odd ksize 3..129; f32 FMAs in tap order 0 .. ksize - 1, so two calls on one input give the same bits), and multiplied by scale_x
+ * (plane 0) / scale_y (plane 1).  workspace: gn_elastic_field_workspace_bytes(H, W) of device memory, the plane between the two passes.
+ * noise, disp (8-byte aligned) and workspace must not alias each other.  A refused call launches nothing and leaves disp as it was. */
+int64_t gn_elastic_field_workspace_bytes(int32_t H, int32_t W);
+int32_t gn_elastic_field(gn_ctx* ctx, const float* noise, float* disp, void* workspace, int32_t H, int32_t W, int32_t ksize, const float* taps,
+                         float scale_x, float scale_y);
 
 /* ---- data-parallel gradient exchange (SURVEY.md section 8b "comm"; replaces accelerate's DDP all-reduce under accelerator.backward,
  * diffusion/train_controlnet_genima.py:1216-1218, :1402-1405).  One communicator per (process, GPU); the RCCL unique id (128 bytes) is
