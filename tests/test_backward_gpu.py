@@ -5,6 +5,7 @@ import torch.nn.functional as F
 
 from genima_amd import train_ops as T
 from genima_amd.packing import pack_conv_weight
+from attention_ref import assert_lse2
 from util import assert_close, q16, randn_h, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -187,6 +188,7 @@ def test_flash_attention_backward(engine, N, Nk, fused):
     assert_close(o, o_ref.detach(), what="attention fwd (lse variant)")
     s = torch.einsum("bnhd,bmhd->bhnm", q.view(B, N, heads, D), k[:, :Nk].view(B, Nk, heads, D)) * D ** -0.5
     assert_close(lse, torch.logsumexp(s, -1) * 1.4426950408889634, what="lse (log2 units)")
+    assert_lse2(lse, q, k, heads, Nk, D ** -0.5, what="lse (log2 units), per element")  # tests/attention_ref.py: the bound derived from the kernels
     dq = torch.empty_like(qd)
     # NaN-filled: the kernel itself writes the padding rows [Nk, Nkr) of dk / dv as zeros (no fill launch in front of it)
     dk = dq if fused else torch.full_like(kd, float("nan"))

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attention_ref import assert_lse2
 from util import assert_close, q16, randn_h, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -215,6 +216,7 @@ def test_attention_stream_kernel_fallback(engine, attn_variant, where):
     s = (q.float().view(B, N, heads, D).transpose(1, 2) @ k.float().view(B, N, heads, D).transpose(1, 2).transpose(-1, -2)) * D ** -0.5
     ref_lse = (torch.logsumexp(s, -1) * 1.4426950408889634).cpu()
     assert float((lse.cpu() - ref_lse).abs().max()) < 2e-2, "lse after the fallback"
+    assert_lse2(lse, q, k, heads, N, D ** -0.5, p_sum_f16=True, what=f"lse after the stream kernel's fallback ({where})")  # per element, the derived bound
     o2 = engine.attention(q, k, v, heads, v_rowmajor=True)  # the generic kernel on the same problem
     assert_close(o, o2.float(), rel=1e-3, what=f"stream kernel vs generic kernel ({where})")
 
@@ -244,6 +246,7 @@ def test_attention_pwg_kernel(engine, attn_variant, B, heads, N):
     assert_close(o, o4.float(), rel=1e-3, what="attention_pwg vs attention_stream")
     s = (q.float().cpu().view(B, N, heads, 64).transpose(1, 2) @ k.float().cpu().view(B, N, heads, 64).transpose(1, 2).transpose(-1, -2)) * 0.125
     assert float((lse.cpu() - torch.logsumexp(s, -1) * 1.4426950408889634).abs().max()) < 2e-3, "lse (log2 units)"
+    assert_lse2(lse, q, k, heads, N, 0.125, p_sum_f16=False, what=f"pwg lse {B}x{heads}x{N}")  # per element; this kernel sums the f32 exponentials
     attn_variant(5)
     assert torch.equal(o, engine.attention(q, k, vt, heads)), "a second call is bit-identical"
     if B > 1:  # which rows run in split blocks depends on the head, never on the batch position
@@ -295,6 +298,7 @@ def test_attention_pwg_kernel_fallback(engine, attn_variant, where, N):
     s = (q.float().view(B, N, heads, D).transpose(1, 2) @ k.float().view(B, N, heads, D).transpose(1, 2).transpose(-1, -2)) * D ** -0.5
     ref_lse = (torch.logsumexp(s, -1) * 1.4426950408889634).cpu()
     assert float((lse.cpu() - ref_lse).abs().max()) < 2e-2, "lse after the fallback"
+    assert_lse2(lse, q, k, heads, N, D ** -0.5, p_sum_f16=False, what=f"lse after the pwg kernel's fallback ({where}, {N})")
     o2 = engine.attention(q, k, v, heads, v_rowmajor=True)  # the generic kernel on the same problem
     assert_close(o, o2.float(), rel=1e-3, what=f"pwg kernel vs generic kernel ({where})")
 
@@ -316,6 +320,8 @@ def test_cross_attention_short_key_set(engine, B, heads, Nq, Nk):
     o2 = engine.attention(q, k, v, heads, Nk=Nk, v_rowmajor=True, lse=lse2)
     assert_close(o, o2.float(), rel=1e-3, what="V^T form vs row-major V")
     assert float((lse - lse2).abs().max()) < 2e-3, "lse (log2 units)"
+    assert_lse2(lse, q, k, heads, Nk, 0.125, p_sum_f16=True, what=f"cross lse {B}x{heads}x{Nq}x{Nk}")  # each against f64, per element
+    assert_lse2(lse2, q, k, heads, Nk, 0.125, p_sum_f16=True, what=f"cross lse, row-major V {B}x{heads}x{Nq}x{Nk}")
 
 
 @pytest.mark.parametrize("heads,Nq,Nk,causal", [(5, 512, 512, False), (4, 200, 77, False), (2, 77, 77, True)])
