@@ -959,6 +959,8 @@ int32_t gn_layernorm_bwd(gn_ctx* ctx, const void* x, const void* gamma, const vo
                          int64_t M, int32_t C, float eps, const void* dx_add) {
   GN_REQUIRE(ctx && x && gamma && dy && dx && M > 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * LNB_MAXCH, "gn_layernorm_bwd: C must be a multiple of 8, <= %d", 64 * 8 * LNB_MAXCH);
   GN_REQUIRE((dgamma == nullptr) == (dbeta == nullptr) && (!dgamma || workspace), "gn_layernorm_bwd: dgamma/dbeta come together and need a workspace");
+  // partial rows are [blocks*4][2][C], reduced below as R = blocks*4 rows of 2C columns -> [2C] sums: one destination
+  GN_REQUIRE(!dgamma || dbeta == dgamma + C, "gn_layernorm_bwd: dbeta must follow dgamma contiguously (flat gradient buffer layout)");
   const int rpb = lnb_rows_per_block(M);
   const long blocks = (M + rpb - 1) / rpb;
   float* part = dgamma ? (float*)workspace : nullptr;
@@ -972,8 +974,6 @@ int32_t gn_layernorm_bwd(gn_ctx* ctx, const void* x, const void* gamma, const vo
 #undef GN_LNB
   GN_LAUNCH_CHECK();
   if (dgamma) {
-    // partial rows are [blocks*4][2][C]: view as R = blocks*4 rows of 2C columns -> [2C] sums
-    GN_REQUIRE(dbeta == dgamma + C, "gn_layernorm_bwd: dbeta must follow dgamma contiguously (flat gradient buffer layout)");
     hipLaunchKernelGGL(reduce_rows_f32_kernel, dim3(nblk(2L * C, 64)), dim3(256), 0, ctx->stream, (const float*)workspace, dgamma, 1, (int)(blocks * 4), 2 * C, 1);
     GN_LAUNCH_CHECK();
   }
@@ -984,10 +984,14 @@ int64_t gn_groupnorm_bwd_workspace_bytes(int32_t B, int32_t HW, int32_t C) {
   int chunks = HW / 16; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
   return ((int64_t)B * chunks * 2 * C + (int64_t)B * C * 3 + (int64_t)B * C * 2) * 4;
 }
-/* fwd_ws: the forward's workspace (gn_groupnorm_workspace_bytes) still holding scsh[B][C][2]; stats: [B][G][2] (mean, rstd) */
+/* scsh [B][C][2] and stats [B][G][2] (mean, rstd): what gn_groupnorm_fwd saved (save_scsh / save_stats) */
 int32_t gn_groupnorm_bwd(gn_ctx* ctx, const gn_groupnorm_desc* d, const void* dy, void* dx, void* dx2, const float* scsh, const float* stats,
                          float* dgamma, float* dbeta, void* workspace, const void* dx_add, const void* dx2_add) {
-  GN_REQUIRE(ctx && d && d->x && dy && scsh && stats && workspace && (dx || dx2), "gn_groupnorm_bwd: null pointer");
+  GN_REQUIRE(ctx && d && d->x && d->gamma && dy && scsh && stats && workspace && (dx || dx2), "gn_groupnorm_bwd: null pointer");
+  GN_REQUIRE(d->B > 0 && d->HW > 0 && d->C1 > 0 && d->C2 >= 0 && (d->C2 == 0 || d->x2), "gn_groupnorm_bwd: empty problem, or C2 without x2");
+  GN_REQUIRE(d->groups > 0 && (d->C1 + d->C2) % d->groups == 0 && (d->C1 + d->C2) / d->groups <= 256,
+             "gn_groupnorm_bwd: C=%d must divide into groups=%d of at most 256 channels", d->C1 + d->C2, d->groups);
+  GN_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "gn_groupnorm_bwd: dgamma/dbeta come together");
   GNBParams p;
   p.x = (const f16*)d->x; p.x2 = (const f16*)d->x2; p.dy = (const f16*)dy; p.gamma = (const f16*)d->gamma; p.beta = (const f16*)d->beta;
   p.dx = (f16*)dx; p.dx2 = (f16*)dx2; p.dgamma = dgamma; p.dbeta = dbeta;
@@ -1002,7 +1006,6 @@ int32_t gn_groupnorm_bwd(gn_ctx* ctx, const gn_groupnorm_desc* d, const void* dy
   p.sums = p.coef + (long)p.B * p.C * 3;
   hipLaunchKernelGGL(gnb_partial_kernel, dim3(p.chunks, p.B), dim3(256), 0, ctx->stream, p, scsh);
   GN_LAUNCH_CHECK();
-  GN_REQUIRE(p.cpg <= 256, "gn_groupnorm_bwd: at most 256 channels per group");
   hipLaunchKernelGGL(gnb_finalize_kernel, dim3(p.G, p.B), dim3(256), 0, ctx->stream, p, stats);
   GN_LAUNCH_CHECK();
   if (dgamma) {

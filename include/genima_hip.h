@@ -574,7 +574,9 @@ int64_t gn_layernorm_bwd_workspace_bytes(int64_t M, int32_t C);
 int32_t gn_layernorm_bwd(gn_ctx* ctx, const void* x, const void* gamma, const void* dy, void* dx, float* dgamma, float* dbeta,
                          void* workspace, int64_t M, int32_t C, float eps, const void* dx_add);
 int64_t gn_groupnorm_bwd_workspace_bytes(int32_t B, int32_t HW, int32_t C);
-/* backward of gn_groupnorm_fwd(d) run with save_stats/save_scsh; dx / dx2 follow d->x / d->x2 (either may be NULL) */
+/* backward of gn_groupnorm_fwd(d) run with save_stats/save_scsh; dx / dx2 follow d->x / d->x2 (either may be NULL).
+ * C1 + C2 <= 4096 divisible into d->groups groups of at most 256 channels; dgamma / dbeta (f32 [C], accumulated) come together or not
+ * at all.  Every argument check precedes the first launch: a refused call writes nothing. */
 int32_t gn_groupnorm_bwd(gn_ctx* ctx, const gn_groupnorm_desc* d, const void* dy, void* dx, void* dx2, const float* scsh,
                          const float* stats, float* dgamma, float* dbeta, void* workspace, const void* dx_add, const void* dx2_add);
 int32_t gn_zero_upsample2x(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C); /* stride-2 dgrad */

@@ -1,4 +1,5 @@
-"""-m gpu: backward / optimizer kernels of the ControlNet fine-tune step against torch autograd on CPU (fp32, same f16 inputs)."""
+"""-m gpu: backward / optimizer kernels of the ControlNet fine-tune step against torch autograd on CPU (fp32, same f16 inputs).
+(The LayerNorm / GroupNorm backward per element against f64, on every dispatch route: tests/test_norm_bwd_gpu.py.)"""
 import pytest
 import torch
 import torch.nn.functional as F
