@@ -615,6 +615,7 @@ int32_t gn_embedding(gn_ctx* ctx, const int32_t* ids, const void* tok, const voi
 
 int32_t gn_softmax_rows(gn_ctx* ctx, void* x, int64_t rows, int32_t cols, int32_t ld, float scale) {
   GN_REQUIRE(ctx && x && rows > 0 && cols > 0 && cols % 8 == 0 && cols <= 64 * 8 * SM_MAXCH && ld % 8 == 0 && ld >= cols, "gn_softmax_rows: cols must be a multiple of 8, <= %d", 64 * 8 * SM_MAXCH);
+  GN_REQUIRE(((uintptr_t)x & 15) == 0, "gn_softmax_rows: 16-byte alignment");  // the kernel moves 16-byte chunks
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(nblk(rows, 4)), dim3(256), 0, ctx->stream, (f16*)x, (long)rows, cols, ld, scale, cols);
   GN_LAUNCH_CHECK();
   return GN_OK;
@@ -623,6 +624,7 @@ int32_t gn_softmax_rows(gn_ctx* ctx, void* x, int64_t rows, int32_t cols, int32_
 int32_t gn_softmax_rows_masked(gn_ctx* ctx, void* x, int64_t rows, int32_t cols, int32_t ld, float scale, int32_t valid) {
   GN_REQUIRE(ctx && x && rows > 0 && cols > 0 && cols % 8 == 0 && cols <= 64 * 8 * SM_MAXCH && ld % 8 == 0 && ld >= cols && valid > 0 && valid <= cols,
              "gn_softmax_rows_masked: cols must be a multiple of 8, <= %d, 0 < valid <= cols", 64 * 8 * SM_MAXCH);
+  GN_REQUIRE(((uintptr_t)x & 15) == 0, "gn_softmax_rows_masked: 16-byte alignment");
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(nblk(rows, 4)), dim3(256), 0, ctx->stream, (f16*)x, (long)rows, cols, ld, scale, valid);
   GN_LAUNCH_CHECK();
   return GN_OK;

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import norm_fwd_ref as NR
 from attention_ref import assert_lse2
 from util import assert_close, q16, randn_h, rel_l2
 
@@ -354,6 +355,15 @@ def test_attention_rowmajor_v(engine, heads, Nq, Nk, causal):
 
 
 # ---------------------------------------------------------------------------------------------------- norms
+def assert_groupnorm_per_element(y, x1, x2, gamma, beta, groups, act):
+    """Every element within its bound of tests/norm_fwd_ref.py (half an f16 ulp plus the f32 arithmetic of the statistics and of x a + s)."""
+    B, C1 = x1.shape[0], x1.shape[-1]
+    x1 = x1.reshape(B, -1, C1)
+    x2 = x2.reshape(B, -1, x2.shape[-1]) if x2 is not None else None
+    ref, bound = NR.gn_fwd_bound(x1, x2, gamma, beta, NR.gn_saved_ref(x1, x2, gamma, beta, groups), act)
+    NR.assert_within(y.reshape(ref.shape), ref, bound, f"groupnorm {tuple(ref.shape)} act {act}, per element")
+
+
 @pytest.mark.parametrize("B,H,W,C,act", [(2, 64, 64, 320, 1), (1, 8, 8, 1280, 1), (2, 32, 32, 128, 0), (1, 128, 128, 128, 1),
                                          (1, 16, 16, 2560, 1), (2, 7, 9, 64, 1)])
 def test_groupnorm(engine, B, H, W, C, act):
@@ -364,6 +374,7 @@ def test_groupnorm(engine, B, H, W, C, act):
     ref = F.group_norm(x, 32, gm, bt, 1e-5)
     ref = F.silu(ref) if act else ref
     assert_close(y, nhwc(ref), what=f"groupnorm {C}@{H}x{W}")
+    assert_groupnorm_per_element(y, nhwc(x).half(), None, gm.half(), bt.half(), 32, act)
 
 
 def test_groupnorm_concat(engine):
@@ -373,6 +384,7 @@ def test_groupnorm_concat(engine):
     y = engine.groupnorm(nhwc(x1).half().cuda(), gm.half().cuda(), bt.half().cuda(), 32, 1e-5, act=1, x2=nhwc(x2).half().cuda())
     ref = F.silu(F.group_norm(torch.cat([x1, x2], 1), 32, gm, bt, 1e-5))
     assert_close(y, nhwc(ref), what="groupnorm concat")
+    assert_groupnorm_per_element(y, nhwc(x1).half(), nhwc(x2).half(), gm.half(), bt.half(), 32, 1)
 
 
 @pytest.mark.parametrize("M,C", [(4096, 320), (77, 1024), (1000, 1280), (5, 256), (130, 4096)])
@@ -382,6 +394,8 @@ def test_layernorm(engine, M, C):
     gm, bt = q16(1 + 0.1 * torch.randn(C, generator=g)), q16(0.1 * torch.randn(C, generator=g))
     y = engine.layernorm(x.half().cuda(), gm.half().cuda(), bt.half().cuda(), 1e-5)
     assert_close(y, F.layer_norm(x, (C,), gm, bt, 1e-5), what=f"layernorm {M}x{C}")
+    ref = NR.ln_fwd_ref(x.half(), gm.half(), bt.half())
+    NR.assert_within(y, ref.y, NR.ln_bound(ref), f"layernorm {M}x{C}, per element")
 
 
 # ---------------------------------------------------------------------------------------------------- small ops
@@ -436,8 +450,10 @@ def test_misc_ops(engine):
     assert_close(e, tok.float().cpu()[ids.long()] + pos.float().cpu()[None], what="embedding")
     s = randn_h(37, 4096, seed=5, scale=3.0)
     ref = torch.softmax(s.float().cpu() * 0.25, -1)
+    ref64, t64 = NR.softmax_ref(s.cpu(), 0.25, 4096)
     engine.softmax_rows(s, 0.25)
     assert_close(s, ref, what="softmax rows")
+    NR.assert_within(s, ref64, NR.softmax_bound(ref64, t64), "softmax rows, per element")
     x = randn_h(2, 17, 19, 64, seed=6)
     mp = engine.maxpool3x3s2(x)
     ref = F.max_pool2d(x.float().cpu().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
