@@ -121,6 +121,15 @@ class ConvGnDesc(C.Structure):
     ]
 
 
+class ConvPatchDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("x2", C.c_void_p), ("scsh", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("shift", C.c_void_p),
+        ("residual", C.c_void_p), ("out", C.c_void_p),
+        ("ldr", C.c_int64), ("ldo", C.c_int64), ("ldshift", C.c_int64),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C1", C.c_int32), ("C2", C.c_int32), ("Cout", C.c_int32), ("act", C.c_int32),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("workspace", C.c_void_p),
@@ -175,6 +184,9 @@ SIGNATURES = {
     "gn_conv3x3_gn_supported": (_I32, [_I32, _I32, _I32, _I32, _I32]),
     "gn_conv3x3_gn": (_I32, [_P, C.POINTER(ConvGnDesc)]),
     "gn_program_add_conv3x3_gn": (_I32, [_P, C.POINTER(ConvGnDesc)]),
+    "gn_conv3x3_patch_supported": (_I32, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "gn_conv3x3_patch": (_I32, [_P, C.POINTER(ConvPatchDesc)]),
+    "gn_program_add_conv3x3_patch": (_I32, [_P, C.POINTER(ConvPatchDesc)]),
     "gn_tiny_block_supported": (_I32, [_I32, _I32, _I32]),
     "gn_tiny_block": (_I32, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
     "gn_program_add_tiny_block": (_I32, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
@@ -336,7 +348,7 @@ def load() -> C.CDLL:
             raise GenimaHipError(f"{LIB_PATH} does not export {name} (stale build?)") from e
         fn.restype = res
         fn.argtypes = args
-    for which, cls in enumerate((GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut)):
+    for which, cls in enumerate((GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc)):
         if int(lib.gn_desc_sizeof(which)) != C.sizeof(cls):  # a stale .so against newer Python (or the reverse) would read garbage descriptors
             raise GenimaHipError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(lib.gn_desc_sizeof(which))} in the library, {C.sizeof(cls)} in the "
                                  "binding (stale build? run `python -m genima_amd.build`)")

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, GEMM_DMA, GEMM_PP, GEMM_PPP, GEMM_RING,
                    OUT_BATCH_TRANSPOSED, OUT_ROWMAJOR, TBLOCK_FRONT, TBLOCK_MID,
-                   TBLOCK_TAIL, AttnDesc, ConvGnDesc, GemmDesc, GenimaHipError, GroupNormDesc, NormOut, StatsSink, TBlockDesc, TBlockTapeSrc, check)
+                   TBLOCK_TAIL, AttnDesc, ConvGnDesc, ConvPatchDesc, GemmDesc, GenimaHipError, GroupNormDesc, NormOut, StatsSink, TBlockDesc, TBlockTapeSrc, check)
 
 F16 = torch.float16
 
@@ -86,6 +86,12 @@ class _Writer:
         self.op, self.index, self.numel, self.sunk, self.rdiv, self.gemm = op, index, numel, False, rdiv, gemm  # rdiv: its rows per sample = the tensor's / rdiv
 
 
+# (Cin, Cout) of the ResNet 3x3 convs that take the patch route (csrc/conv_patch.hip): the 64 x 64 x 320 level of the UNet / ControlNet.  The kernel
+# beat the tune table's gn_gemm by 10 - 27 % at all eight raced shapes (tools/bench_conv_gn.py patch, profiles/conv_patch_race.txt, B = 8), but at
+# the 32 x 32 x 640 level the GroupNorm in front of these convs rides inside gn_gemm (norm_in) and comes back as a launch of its own with the
+# patch conv: the call gained nothing there (profiles/conv_patch_modes_ab.txt), so (640, 640), (320, 640), (960 / 1280 / 1920, 640) stay on gn_gemm
+CONV_PATCH_SHAPES = ((320, 320), (640, 320), (960, 320))
+
 class Engine:
     STATS_ARENA_BYTES = 16 << 20  # the GroupNorm bridge's statistics blocks of one recorded program (the used prefix is cleared at the top of every replay)
     STATS_LINE = 16               # int64 words per (replica, sample, group) line: GN_STATS_LINE
@@ -105,6 +111,14 @@ class Engine:
         # 1251 -> 915 us, 512^2 x 256 -> 128 2066 -> 1657 us; a wash at 256^2 x 256 (789 -> 774), a loss below (the SiLU of the 1.4x halo patch is
         # VALU time beside the MFMAs of a 128-wide output tile)
         self.conv_gn_min_hw = int(os.environ.get("GN_CONV_GN_MIN_HW", str(512 * 512)))
+        # graphs: the UNet / ControlNet ResNet convs of CONV_PATCH_SHAPES from an LDS-resident patch (csrc/conv_patch.hip; A/B switch), from
+        # conv_patch_min_rows output pixels x batch: 64 x 64 at B = 8, the size it was raced and the call measured at (91.5 -> 90.1 ms)
+        self.conv_patch = os.environ.get("GN_CONV_PATCH", "1") != "0"
+        self.conv_patch_min_rows = int(os.environ.get("GN_CONV_PATCH_MIN_ROWS", "32768"))
+        self.conv_patch_shapes = set(CONV_PATCH_SHAPES)
+        # statistics-only GroupNorm + normalisation inside the patch (1) or the GroupNorm launch + the plain patch conv (0; A/B switch): equal
+        # as a pair of launches, but the GroupNorm behind a patch conv has no producer statistics and the statistics-only pass is the cheaper one
+        self.conv_patch_fuse_gn = os.environ.get("GN_CONV_PATCH_FUSE_GN", "1") != "0"
         # graphs: ResnetBlock2D's conv_shortcut inside conv2's K loop (gn_gemm_desc.k_append, packing `conv2sc`; A/B switch)
         self.k_append = os.environ.get("GN_K_APPEND", "1") != "0"
         self.k_append_min_rows = int(os.environ.get("GN_K_APPEND_MIN_ROWS", "0"))
@@ -1128,20 +1142,22 @@ class Engine:
         return True
 
     def groupnorm_stats(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, *,
-                        name: Optional[str] = None) -> torch.Tensor:
+                        x2: Optional[torch.Tensor] = None, name: Optional[str] = None) -> torch.Tensor:
         """Statistics-only GroupNorm (gn_groupnorm_fwd with y == NULL): -> f32 [B, C, 2] per-(sample, channel) (scale, shift) such that
         GN(x)[b, .., c] = x * scale + shift; conv2d_gn applies them (and the SiLU) to its input patch in LDS.  One read of x, no write."""
-        B, Cc = x.shape[0], x.shape[-1]
-        HW = x.numel() // (B * Cc)
+        B, C1 = x.shape[0], x.shape[-1]
+        HW = x.numel() // (B * C1)
+        C2 = x2.shape[-1] if x2 is not None else 0  # (x2: the concat partner, as groupnorm's)
+        Cc = C1 + C2
         scsh = self.buf(name, (B, Cc, 2), dtype=torch.float32)
         d = GroupNormDesc()
-        d.x, d.gamma, d.beta, d.y, d.save_scsh = _ptr(x), _ptr(gamma), _ptr(beta), None, _ptr(scsh)
-        d.B, d.HW, d.C1, d.C2, d.groups, d.act, d.eps = B, HW, Cc, 0, groups, ACT_NONE, eps
+        d.x, d.x2, d.gamma, d.beta, d.y, d.save_scsh = _ptr(x), _ptr(x2), _ptr(gamma), _ptr(beta), None, _ptr(scsh)
+        d.B, d.HW, d.C1, d.C2, d.groups, d.act, d.eps = B, HW, C1, C2, groups, ACT_NONE, eps
         ws = self._workspace(int(self.lib.gn_groupnorm_workspace_bytes(C.byref(d))))
         d.workspace = ws.data_ptr()
         if self.record:
             check(self.lib.gn_program_add_groupnorm(self._prog, C.byref(d)), "gn_program_add_groupnorm")
-            self._keepalive(x, gamma, beta, scsh, ws)
+            self._keepalive(x, x2, gamma, beta, scsh, ws)
             self.meta.append(dict(kind="groupnorm", flops=0.0, bytes=2.0 * B * HW * Cc, shape=(B, HW, Cc, 0)))
         else:
             check(self.lib.gn_groupnorm_fwd(self._ctx, C.byref(d)), "gn_groupnorm_fwd")
@@ -1174,6 +1190,73 @@ class Engine:
             self.meta.append(dict(kind="conv3x3", flops=2.0 * M * N * K, bytes=2.0 * (M * Cin + N * K + M * N), shape=(M, N, K), ref_flops=2.0 * M * N * K))
         else:
             check(self.lib.gn_conv3x3_gn(self._ctx, C.byref(d)), "gn_conv3x3_gn")
+        return out
+
+    def conv2d_patch_route(self, x: torch.Tensor, cout: int, x2: Optional[torch.Tensor] = None, groups: int = 32) -> int:
+        """graphs.emit_resnet: which route does GroupNorm -> SiLU -> conv3x3 over x (| x2) take?  0: gn_gemm.  2: statistics-only GroupNorm +
+        normalisation inside the conv's LDS patch.  1: the GroupNorm launch as on the gn_gemm route (bridge statistics / norm_out where they apply),
+        then the plain patch conv -- with GN_CONV_PATCH_FUSE_GN=0, and where x's GroupNorm rides in its producer's split-K reduce (norm_out)."""
+        if not getattr(self, "conv_patch", False) or x.dim() != 4:
+            return 0
+        cin = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
+        if x.shape[0] * x.shape[1] * x.shape[2] < self.conv_patch_min_rows or (cin, cout) not in self.conv_patch_shapes:
+            return 0
+        if not self.lib.gn_conv3x3_patch_supported(x.shape[0], x.shape[1], x.shape[2], cin, 0, cout):
+            return 0
+        if self.conv_patch_fuse_gn and self.conv2d_patch_supported(x, cout, x2) and (x2 is not None or not self._norm_out_applies(x, groups)):
+            return 2
+        return 1
+
+    def _norm_out_applies(self, x: torch.Tensor, groups: int) -> bool:
+        """Would a GroupNorm over x recorded now move into the split-K reduce of the launch that wrote x (_norm_out's conditions, nothing changed)?"""
+        B, Cc = x.shape[0], x.shape[-1]
+        HW = x.numel() // (B * Cc)
+        if not (self.record and self.gn_reduce_fuse) or (B * groups < self.gn_reduce_fuse_min_slabs and HW > self.gn_reduce_fuse_small_hw):
+            return False
+        w = self._writer.get(x.data_ptr())
+        if w is None or not w.gemm or w.sunk or w.rdiv != 1 or w.numel != x.numel() or not x.is_contiguous():
+            return False
+        d = GemmDesc()
+        if self.lib.gn_program_get_gemm(self._prog, w.op, C.byref(d)) != 0 or d.norm_out.y:
+            return False
+        n = d.norm_out  # (a probe: y only has to be non-null and aligned like the tensor the GroupNorm would write)
+        n.y, n.gamma, n.beta, n.eps, n.groups, n.act, n.rows_per_sample = _ptr(x), _ptr(x), _ptr(x), 1e-5, int(groups), ACT_SILU, int(HW)
+        return bool(self.lib.gn_gemm_norm_out_supported(C.byref(d)))
+
+    def conv2d_patch_supported(self, x: torch.Tensor, cout: int, x2: Optional[torch.Tensor] = None) -> bool:
+        B, H, W, C1 = x.shape
+        return bool(self.lib.gn_conv3x3_patch_supported(B, H, W, C1, x2.shape[-1] if x2 is not None else 0, cout))
+
+    def conv2d_patch(self, x: torch.Tensor, scsh: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+                     x2: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None, ldshift: int = 0, act: int = ACT_SILU,
+                     residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, name: Optional[str] = None) -> torch.Tensor:
+        """conv3x3(act(X * scale + shift_gn)) + bias + shift[b] (+ residual), X = x or the virtual concat [x | x2], from an LDS-resident patch in
+        64-channel groups on 128 x 160 output tiles (gn_conv3x3_patch, csrc/conv_patch.hip): the UNet / ControlNet ResNet convs at 320 / 640
+        output channels.  x (x2): RAW NHWC; scsh from groupnorm_stats over x (| x2) (None: plain conv); w packed [Cout, 9 (C1 + C2)];
+        shift: [B, ldshift or Cout] per-sample channel shift."""
+        B, H, W, C1 = x.shape
+        C2 = x2.shape[-1] if x2 is not None else 0
+        N = w.shape[0]
+        assert w.shape[1] == 9 * (C1 + C2), (tuple(w.shape), C1, C2)
+        assert x.is_contiguous() and (x2 is None or (x2.is_contiguous() and tuple(x2.shape[:3]) == (B, H, W)))
+        if out is None:
+            out = self.buf(name, (B, H, W, N))
+        else:
+            self._wrote(out)
+        d = ConvPatchDesc()
+        d.x, d.x2, d.scsh, d.w, d.bias, d.shift, d.residual, d.out = (_ptr(x), _ptr(x2), _ptr(scsh), _ptr(w), _ptr(bias), _ptr(shift),
+                                                                      _ptr(residual), _ptr(out))
+        d.ldr, d.ldo = (residual.stride(-2) if residual is not None else 0), out.stride(-2)
+        d.ldshift = (ldshift or shift.stride(0)) if shift is not None else 0
+        d.B, d.H, d.W, d.C1, d.C2, d.Cout, d.act = B, H, W, C1, C2, N, act
+        if self.record:
+            check(self.lib.gn_program_add_conv3x3_patch(self._prog, C.byref(d)), "gn_program_add_conv3x3_patch")
+            self._keepalive(x, x2, scsh, w, bias, shift, residual, out)
+            M, K = B * H * W, 9 * (C1 + C2)  # (the rows of the conv it replaces: same kind, shape and formulas as conv2d's)
+            self.meta.append(dict(kind="conv3x3", flops=2.0 * M * N * K, bytes=2.0 * (M * (C1 + C2) + N * K + M * N), shape=(M, N, K),
+                                  ref_flops=2.0 * M * N * K, route="patch"))
+        else:
+            check(self.lib.gn_conv3x3_patch(self._ctx, C.byref(d)), "gn_conv3x3_patch")
         return out
 
     def tiny_block_supported(self, x: torch.Tensor) -> bool:

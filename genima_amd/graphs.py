@@ -104,7 +104,15 @@ def emit_resnet(E: Engine, W, p: str, x, x2, shifts, groups: int, eps: float, ep
             sc = x
         sh, ld = _shift_for(W, shifts, p) if (p + ".time_emb_proj.weight") in W else (None, 0)
 
-        if x2 is None and sh is None and fuse(x, c1w.shape[0]):
+        # the 64 x 64 x 320 level at batch: the conv from its LDS-resident patch (csrc/conv_patch.hip), time shift in its epilogue
+        r1 = E.conv2d_patch_route(x, c1w.shape[0], x2, groups)
+        if r1 == 2:  # statistics-only GroupNorm, normalisation inside the patch, the concatenated input as the kernel's two sources
+            st = E.groupnorm_stats(x, W[p + ".norm1.weight"], W[p + ".norm1.bias"], groups, eps if eps_in is None else eps_in, x2=x2, name="n1s")
+            h = E.conv2d_patch(x, st, c1w, W[p + ".conv1.bias"], x2=x2, shift=sh, ldshift=ld, name="c1")
+        elif r1 == 1:  # the GroupNorm launch the gn_gemm route would take (it writes the concatenation), the plain conv on its output
+            n = E.groupnorm(x, W[p + ".norm1.weight"], W[p + ".norm1.bias"], groups, eps if eps_in is None else eps_in, act=ACT_SILU, x2=x2, name="n1")
+            h = E.conv2d_patch(n, None, c1w, W[p + ".conv1.bias"], shift=sh, ldshift=ld, act=ACT_NONE, name="c1")
+        elif x2 is None and sh is None and fuse(x, c1w.shape[0]):
             st = E.groupnorm_stats(x, W[p + ".norm1.weight"], W[p + ".norm1.bias"], groups, eps if eps_in is None else eps_in, name="n1s")
             h = E.conv2d_gn(x, st, c1w, W[p + ".conv1.bias"], name="c1")
         else:
@@ -118,6 +126,15 @@ def emit_resnet(E: Engine, W, p: str, x, x2, shifts, groups: int, eps: float, ep
             if side:
                 E.join()
             return E.conv2d_gn(h, st, c2w, W[p + ".conv2.bias"], residual=sc, name="c2")
+        r2 = 0 if kapp else E.conv2d_patch_route(h, c2w.shape[0], None, groups)
+        if r2:
+            if r2 == 2:
+                st, n = E.groupnorm_stats(h, W[p + ".norm2.weight"], W[p + ".norm2.bias"], groups, eps, name="n2s"), h
+            else:
+                st, n = None, E.groupnorm(h, W[p + ".norm2.weight"], W[p + ".norm2.bias"], groups, eps, act=ACT_SILU, name="n2")
+            if side:
+                E.join()
+            return E.conv2d_patch(n, st, c2w, W[p + ".conv2.bias"], act=ACT_SILU if r2 == 2 else ACT_NONE, residual=sc, name="c2")
         n2 = Norm(W[p + ".norm2.weight"], W[p + ".norm2.bias"], groups, eps, ACT_SILU, "n2")
         if side:
             E.join()

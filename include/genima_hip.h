@@ -390,6 +390,28 @@ typedef struct gn_conv3x3_gn_desc {
 int32_t gn_conv3x3_gn_supported(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
 int32_t gn_conv3x3_gn(gn_ctx* ctx, const gn_conv3x3_gn_desc* d);
 
+/* ---- 3x3 convolution (stride 1, padding 1) from an LDS-resident patch in 64-channel groups, 128 x 160 output tiles (csrc/conv_patch.hip) -----
+ * out = conv3x3(act(X * scale[b, c] + shift_gn[b, c])) + bias + shift[b, :] (+ residual), X = x or the virtual concat [x | x2] along channels:
+ * gn_conv3x3_gn's scheme for the UNet / ControlNet ResNet convs at 320 / 640 output channels (diffusers ResnetBlock2D conv1 with its
+ * time_emb_proj shift and, in the up blocks, its concatenated input; conv2 with its residual).  Same packed weight [Cout][9 * (C1 + C2)] as gn_gemm.
+ * Needs H % 8 == 0, W % 16 == 0, (C1 + C2) % 64 == 0, C1 % 64 == 0 when x2 is given, Cout % 160 == 0 (gn_conv3x3_patch_supported); an
+ * unsupported problem is an error and launches nothing.  Epilogue order: bias, time shift, residual (gn_gemm's), in f32, one rounding. */
+typedef struct gn_conv3x3_patch_desc {
+  const void* x;          /* NHWC f16 [B, H, W, C1]: the RAW tensor the GroupNorm reads */
+  const void* x2;         /* NHWC f16 [B, H, W, C2] or NULL: channels C1 .. C1 + C2 - 1 of the virtual concat */
+  const void* scsh;       /* f32 [B][C1 + C2][2] (scale, shift) by concatenated channel from the statistics-only GroupNorm call, or NULL: plain conv */
+  const void* w;          /* packed conv weight [Cout][9 * (C1 + C2)] f16 (gn_pack_conv_weight) */
+  const void* bias;       /* [Cout] f16 or NULL */
+  const void* shift;      /* [B, ldshift] f16 or NULL: per-sample channel shift (a column slice of the time-shift table) */
+  const void* residual;   /* [B * H * W, ldr] f16 or NULL: added last */
+  void* out;              /* [B * H * W, ldo] f16 */
+  int64_t ldr, ldo, ldshift;
+  int32_t B, H, W, C1, C2, Cout;
+  int32_t act;            /* GN_ACT_NONE / GN_ACT_SILU on the normalised input (with scsh) */
+} gn_conv3x3_patch_desc;
+int32_t gn_conv3x3_patch_supported(int32_t B, int32_t H, int32_t W, int32_t C1, int32_t C2, int32_t Cout);
+int32_t gn_conv3x3_patch(gn_ctx* ctx, const gn_conv3x3_patch_desc* d);
+
 /* ---- diffusers AutoencoderTinyBlock at 64 channels as one launch (csrc/taesd.hip) ----------------------------------------------------
  * out = relu(conv3(relu(conv2(relu(conv1(x))))) + x): 3x3 convs, stride 1, padding 1, NHWC f16 [B, H, W, 64] -- every block of the
  * TAESD / TAESDXL encoder.  w[k]: packed conv weight [64][9 * 64] f16 (gn_pack_conv_weight), bias[k]: [64] f16.  The two intermediate
@@ -684,6 +706,7 @@ int32_t gn_program_add_gemm(gn_program* p, const gn_gemm_desc* d);
 int32_t gn_program_add_attention(gn_program* p, const gn_attn_desc* d);
 int32_t gn_program_add_tblock(gn_program* p, const gn_tblock_desc* d);
 int32_t gn_program_add_conv3x3_gn(gn_program* p, const gn_conv3x3_gn_desc* d);
+int32_t gn_program_add_conv3x3_patch(gn_program* p, const gn_conv3x3_patch_desc* d);
 int32_t gn_program_add_groupnorm(gn_program* p, const gn_groupnorm_desc* d);
 int32_t gn_program_add_tiny_block(gn_program* p, const void* x, const void* const w[3], const void* const bias[3], void* out, int32_t B,
                                  int32_t H, int32_t W, int32_t C);
@@ -745,7 +768,7 @@ int32_t gn_program_add_memset(gn_program* p, void* ptr, int64_t bytes);
 int32_t gn_program_set_memset_bytes(gn_program* p, int64_t op, int64_t bytes); /* shrink a recorded memset to the bytes the program came to use */
 int32_t gn_memset(gn_ctx* ctx, void* ptr, int64_t bytes);
 /* sizeof() of the descriptor structs as the library was compiled (0 gn_gemm_desc, 1 gn_attn_desc, 2 gn_groupnorm_desc, 3 gn_tblock_desc,
- * 4 gn_conv3x3_gn_desc, 5 gn_stats_sink, 6 gn_norm_in, 7 gn_norm_out): a host binding checks its own layout against these before the first call */
+ * 4 gn_conv3x3_gn_desc, 5 gn_stats_sink, 6 gn_norm_in, 7 gn_norm_out, 8 gn_conv3x3_patch_desc): a host binding checks its own layout against these before the first call */
 int64_t gn_desc_sizeof(int32_t which);
 /* first..last (exclusive) op range; last < 0 = to the end */
 int32_t gn_program_run(gn_program* p, int64_t first, int64_t last);
