@@ -6,6 +6,7 @@ The product path has NO fallback: if the HIP library is missing or fails to load
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -84,6 +85,24 @@ class AttnBwdDesc(C.Structure):
                 + [(n + "_bs", C.c_int64) for n in ("q", "k", "v", "o", "do", "qt", "kt", "dot", "dq", "dk", "dv")]
                 + [(n + "_rs", C.c_int32) for n in ("q", "k", "v", "o", "do", "qt", "kt", "dot", "dq", "dk", "dv")]
                 + [(n, C.c_int32) for n in ("B", "heads", "Nq", "Nk", "Nk_rows", "D")] + [("scale", C.c_float)])
+
+
+class AttnDropout(C.Structure):
+    """gn_attn_dropout: the attention-probability dropout mask's parameters (include/genima_hip.h states the formula)."""
+    _fields_ = [("threshold", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("inv_keep", C.c_float)]
+
+
+def attn_dropout_threshold(p: float) -> int:
+    """min(2^32 - 1, floor(p * 2^32)) in f64: an element is kept when its 32-bit hash is >= this (0 keeps everything)."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attention dropout probability must be in [0, 1), got {p!r}")
+    return min(2 ** 32 - 1, int(math.floor(float(p) * 2.0 ** 32)))
+
+
+def attn_dropout_desc(p: float, seed: int) -> AttnDropout:
+    """(p, 64-bit seed) -> gn_attn_dropout."""
+    seed = int(seed) & (2 ** 64 - 1)
+    return AttnDropout(attn_dropout_threshold(p), seed & 0xFFFFFFFF, seed >> 32, 1.0 / (1.0 - float(p)))
 
 
 class GroupNormDesc(C.Structure):
@@ -191,6 +210,9 @@ SIGNATURES = {
     "gn_tiny_block": (_I32, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
     "gn_program_add_tiny_block": (_I32, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
     "gn_attention_bwd": (_I32, [_P, C.POINTER(AttnBwdDesc)]),
+    "gn_attention_dropout_fwd": (_I32, [_P, C.POINTER(AttnDesc), C.POINTER(AttnDropout)]),
+    "gn_attention_dropout_bwd": (_I32, [_P, C.POINTER(AttnBwdDesc), C.POINTER(AttnDropout)]),
+    "gn_attention_dropout_apply": (_I32, [_P, _P, _I32, _I32, _I32, _I64, C.POINTER(AttnDropout), _P]),
     "gn_attention_fp8_quantize": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _F, _P, _P, _P, _I32]),
     "gn_attention_fp8_fwd": (_I32, [_P, C.POINTER(AttnDesc)]),
     "gn_groupnorm_workspace_bytes": (_I64, [C.POINTER(GroupNormDesc)]),

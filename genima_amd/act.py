@@ -689,7 +689,9 @@ class GenimaACT:
         with ``action`` [B, T, A], ``low_dim_state`` [B, fs, S], the ``*rgb*`` camera tensors [B, fs, 3, H, W] (``tp1`` keys ignored),
         ``lang_tokens`` [B, fs, 77] and ``reward``.  The trainer (act_training.ACTTrainer: CVAE posterior, loss, tape backward, two-group
         AdamW) is built on first use from this agent's weights; train-time augmentation runs when ``data_augmentation`` is on (config key
-        ``elastic_field``: "host", the default, or "device" -- where the elastic warp's displacement field is blurred)."""
+        ``elastic_field``: "host", the default, or "device" -- where the elastic warp's displacement field is blurred).  The config key
+        ``attn_dropout`` (default 0.0: off) is the trainer's attention-probability dropout; the reference's value is the ``dropout`` of
+        its DETR layers, 0.1 (``attn_dropout: 0.1`` turns it on; a ``trainer_kw`` of the same name overrides the config)."""
         from .act_training import ACTTrainer, act_augment, act_train_schema
 
         if getattr(self, "_trainer", None) is None:
@@ -701,6 +703,7 @@ class GenimaACT:
             fresh = OrderedDict((k, v) for k, v in sch.items() if k not in sd)
             if fresh:
                 sd.update(weights.synth_state_dict(fresh, 77))  # CVAE encoder: fresh init
+            trainer_kw.setdefault("attn_dropout", float(self.config.get("attn_dropout", 0.0)))
             self._trainer = ACTTrainer(Engine(self.device), self.config, sd, self.clip_config, self.Wclip, **trainer_kw)
             self._aug_gen = torch.Generator().manual_seed(0)
         batch = next(replay_iter)

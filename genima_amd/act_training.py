@@ -12,8 +12,13 @@ generators and everything in the transformer train.  The frozen BatchNorms are a
 weights train un-folded, exactly as in the reference.
 
 Deviations, stated: (1) f16 compute where the reference trains in fp32; (2) of the DETR layers' dropouts the residual / feed-forward
-ones and the state MLP's p = 0.3 are applied, ``nn.MultiheadAttention``'s attention-probability dropout is not (the flash kernel never
-materialises the probabilities); (3) the CVAE encoder's module names are [VERIFY] items (RoboBase is absent).
+ones and the state MLP's p = 0.3 are applied by default; ``nn.MultiheadAttention``'s attention-probability dropout -- the ``dropout`` of
+the reference's DETR layers, 0.1, on every attention: CVAE posterior encoder, encoder self-, decoder self- and cross-attention -- is
+built (``ACTTrainer(attn_dropout=0.1)``, config key ``attn_dropout: 0.1`` under ``GenimaACT.update``) and OFF by default (0.0), so an
+update computes what it computed before unless it is asked for.  Its keep mask is not torch's Philox stream but a hash of (seed,
+batch * heads + head, query, key) that the attention kernels evaluate where they hold the probabilities (include/genima_hip.h,
+gn_attn_dropout): same distribution, other draws; (3) the CVAE encoder's module names are [VERIFY] items
+(RoboBase is absent).
 """
 from __future__ import annotations
 
@@ -74,13 +79,37 @@ def _rup(x, m):
     return (x + m - 1) // m * m
 
 
+_M64 = 2 ** 64 - 1
+
+
+def _splitmix64(x: int) -> int:
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def attn_call_seed(trainer_seed: int, step: int, index: int) -> int:
+    """The 64-bit seed of one attention call's dropout mask: a splitmix64 chain over (trainer seed, optimizer step, index of the attention
+    call within the step).  Host integers only -- nothing is drawn from the trainer's torch generator, so the other dropout masks and
+    the CVAE eps stay the draws they were."""
+    h = _splitmix64(int(trainer_seed) & _M64)
+    h = _splitmix64(h ^ (int(step) & _M64))
+    return _splitmix64(h ^ (int(index) & _M64))
+
+
 class ACTTrainer:
     def __init__(self, E: Engine, cfg, state_dict: Dict[str, torch.Tensor], clip_cfg, clip_W, *, lr: float = 5e-5, lr_backbone: float = 1e-5,
                  weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, loss_scale: float = 1024.0, dropout: float = 0.1,
-                 state_dropout: float = 0.3, seed: int = 0):
+                 state_dropout: float = 0.3, seed: int = 0, attn_dropout: float = 0.0):
+        """attn_dropout: nn.MultiheadAttention's attention-probability dropout on every attention of the update (the reference's DETR
+        layers run it at their ``dropout``, 0.1); 0.0, the default, runs the plain kernels."""
+        if not 0.0 <= float(attn_dropout) < 1.0:
+            raise ValueError(f"ACTTrainer: attn_dropout must be in [0, 1), got {attn_dropout!r}")
         self.E, self.cfg, self.clip_cfg, self.clip_W = E, dict(cfg), clip_cfg, clip_W
         self.lr, self.lr_backbone, self.wd, self.betas, self.eps = lr, lr_backbone, weight_decay, betas, eps
         self.loss_scale, self.p_drop, self.p_state = float(loss_scale), dropout, state_dropout
+        self.p_attn, self.seed, self.last_attn_seeds = float(attn_dropout), int(seed), []
         sch = act_train_schema(cfg)
         sd = {k: state_dict[k].detach().float() for k in sch}
         self.names = trainable_names(sch)
@@ -122,6 +151,14 @@ class ACTTrainer:
                 for alias, (a, b) in (("qk_proj", (0, 2 * d)), ("v_proj", (2 * d, 3 * d)), ("q_proj", (0, d)), ("k_proj", (d, 2 * d))):
                     W[p + alias + ".weight"], G[p + alias + ".weight"] = W[name][a:b], G[name][a:b]
                     W[p + alias + ".bias"], G[p + alias + ".bias"] = W[p + "in_proj_bias"][a:b], G[p + "in_proj_bias"][a:b]
+
+    def _attn_drop(self):
+        """-> the (p, seed) of the next attention call of this step (``opt_step``), or None with attn_dropout off."""
+        if self.p_attn <= 0.0:
+            return None
+        s = attn_call_seed(self.seed, self.opt_step, len(self.last_attn_seeds))
+        self.last_attn_seeds.append(s)
+        return (self.p_attn, s)
 
     # ------------------------------------------------------------------------------------------------------------------ forward pieces
     def _block(self, g: Graph, hv: Var, p: str, c: int, stride: int, film: Optional[Var], bi: int, rows_pf: int) -> Var:
@@ -176,7 +213,7 @@ class ACTTrainer:
         xp = g.add(src, pos)
         qk = g.linear(net, xp, p + ".self_attn.qk_proj.weight", p + ".self_attn.qk_proj.bias")
         v = g.linear(net, src, p + ".self_attn.v_proj.weight", p + ".self_attn.v_proj.bias")
-        a = g.attention(qk, 0, qk, d, v, heads, n_valid)
+        a = g.attention(qk, 0, qk, d, v, heads, n_valid, dropout=self._attn_drop())
         o = g.dropout(g.linear(net, a, p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias"), self.p_drop, self._gen)
         src = g.layernorm(net, g.add(src, o), p + ".norm1.weight", p + ".norm1.bias")
         h = g.dropout(g.act(g.linear(net, src, p + ".linear1.weight", p + ".linear1.bias"), ACT_RELU), self.p_drop, self._gen)
@@ -188,14 +225,14 @@ class ACTTrainer:
         tq = g.add(tgt, qe)
         qk = g.linear(net, tq, p + ".self_attn.qk_proj.weight", p + ".self_attn.qk_proj.bias")
         v = g.linear(net, tgt, p + ".self_attn.v_proj.weight", p + ".self_attn.v_proj.bias")
-        a = g.attention(qk, 0, qk, d, v, heads, nq)
+        a = g.attention(qk, 0, qk, d, v, heads, nq, dropout=self._attn_drop())
         o = g.dropout(g.linear(net, a, p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias"), self.p_drop, self._gen)
         tgt = g.layernorm(net, g.add(tgt, o), p + ".norm1.weight", p + ".norm1.bias")
         m = p + ".multihead_attn"
         cq = g.linear(net, g.add(tgt, qe), m + ".q_proj.weight", m + ".q_proj.bias")
         ck = g.linear(net, mem_pos, m + ".k_proj.weight", m + ".k_proj.bias")
         cv = g.linear(net, memory, m + ".v_proj.weight", m + ".v_proj.bias")
-        a = g.attention(cq, 0, ck, 0, cv, heads, n_mem)
+        a = g.attention(cq, 0, ck, 0, cv, heads, n_mem, dropout=self._attn_drop())
         o = g.dropout(g.linear(net, a, m + ".out_proj.weight", m + ".out_proj.bias"), self.p_drop, self._gen)
         tgt = g.layernorm(net, g.add(tgt, o), p + ".norm2.weight", p + ".norm2.bias")
         h = g.dropout(g.act(g.linear(net, tgt, p + ".linear1.weight", p + ".linear1.bias"), ACT_RELU), self.p_drop, self._gen)
@@ -211,6 +248,7 @@ class ACTTrainer:
         E, cfg, net = self.E, self.cfg, self.cn
         dev = E.device
         g = Graph(E)
+        self.last_attn_seeds = []  # the attention dropout seeds of this step, in call order (empty with attn_dropout off)
         B, V = images.shape[:2]
         d, Tq, L, A = cfg["hidden_dim"], cfg["num_queries"], cfg["latent_dim"], cfg["action_dim"]
         acts = actions[:, :Tq].to(dev, F32).contiguous()

@@ -58,7 +58,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "attention_common.h", "gn_bridge.h", "image_convert.h")] + [os.path.join(HERE, "..", "include", "genima_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "attention_common.h", "attention_dropout.h", "gn_bridge.h", "image_convert.h")] + [os.path.join(HERE, "..", "include", "genima_hip.h")]
     # the objects are only as good as the flags they were built with: a probe build (GN_HIPCC_EXTRA=-DGN_PP_ABLATIONS ..., some of which give wrong
     # results on purpose) must never be reused by the next normal build, nor the other way round -- the flag set is stamped beside the objects
     stamp = os.path.join(objdir, ".flags")

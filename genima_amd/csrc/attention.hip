@@ -32,11 +32,17 @@
 #include <type_traits>
 
 #include "attention_common.h"
+#include "attention_dropout.h"
 
 // waves per SIMD the 4-wave x 32-row D = 64 kernels are held to (register budget 512 / 3 = 170): the V^T kernel fits anyway (167 with
 // -amdgpu-mfma-vgpr-form), the row-major-V one needs the hint (184 -> 168: 222 -> 206-216 us at 8 x 5 x 4096^2)
 #ifndef GN_ATTN_WAVES
 #define GN_ATTN_WAVES 3
+#endif
+
+// the dropout form's mask hashes need registers of their own: held to three waves per SIMD it spills (112 bytes of scratch per lane), at two it fits
+#ifndef GN_ATTN_DROP_WAVES
+#define GN_ATTN_DROP_WAVES 2
 #endif
 
 namespace {
@@ -48,9 +54,17 @@ typedef __fp16 attn_h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) attn_h4* attn_lds_h4_ptr;
 struct AttnH8 { attn_h4 lo, hi; };
 
-template <int D, int NW, int TQ, bool VROW = false>
-__global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4 && TQ == 1 && GN_ATTN_WAVES > 0) ? GN_ATTN_WAVES : 1) void attn_fwd_kernel(const AttnParams p) {
+// the dropout form's arguments ride behind the plain ones, so the plain instantiations keep their kernel arguments as they are
+struct AttnDropParams : AttnParams { AttnDropout dr; };
+
+// DROP (gn_attention_dropout_fwd; non-causal, V^T): O = ((P o keep) / (1 - p)) V with keep from attention_dropout.h.  The row statistics are
+// taken on the undropped P (lse does not depend on dropout); the dropped pairs are zeroed in the packed f16 P after its row sum, right in
+// front of the P.V MFMA, and 1 / (1 - p) is folded into the final 1 / l.
+template <int D, int NW, int TQ, bool VROW = false, bool DROP = false>
+__global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4 && TQ == 1 && GN_ATTN_WAVES > 0) ? (DROP ? GN_ATTN_DROP_WAVES : GN_ATTN_WAVES) : 1) void attn_fwd_kernel(
+    const std::conditional_t<DROP, AttnDropParams, AttnParams> p) {
   static_assert(!VROW || D == 64, "row-major V: the LDS-DMA (D = 64) path only");
+  static_assert(!DROP || !VROW, "dropout: the V^T form only");
   constexpr int NT = NW * 64;
   constexpr int QB = NW * TQ * 32;   // query rows per block
   constexpr int ROWB = D * 2;        // K tile row bytes
@@ -95,6 +109,14 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4 && TQ == 1 && GN_ATTN_
       for (int x = 0; x < 8; ++x) q8[x] = (f16)((float)q8[x] * p.scale_log2);  // exponent units straight out of the MFMA
       qf[tq][ks] = q8;
     }
+
+  // dropout: the per-row part of the mask hash (one mix per query row a lane owns)
+  [[maybe_unused]] unsigned drow[TQ];
+  if constexpr (DROP) {
+    const unsigned dhead = attn_drop_head(p.dr, bh);
+#pragma unroll
+    for (int tq = 0; tq < TQ; ++tq) drow[tq] = attn_drop_row(dhead, qw + 32 * tq);
+  }
 
   f32x16 oacc[TQ][DT], negm[TQ];
   float m_run[TQ], l_run[TQ];
@@ -287,6 +309,11 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4 && TQ == 1 && GN_ATTN_
           pp[0] = (f16)__builtin_amdgcn_exp2f(s[tq][u][r]);
           pp[1] = (f16)__builtin_amdgcn_exp2f(s[tq][u][r + 1]);
           acc = __builtin_amdgcn_fdot2(pp, ones, acc, false);
+          if constexpr (DROP) {  // after the row sum (l is the undropped one), before P.V: both softmax paths pack through here
+            const int key = j0 + 32 * u + 16 * (r >> 3) + 8 * hi + (r & 7);
+            pp[0] = attn_drop_keep(drow[tq], key, p.dr.threshold) ? pp[0] : (f16)0.0f;
+            pp[1] = attn_drop_keep(drow[tq], key + 1, p.dr.threshold) ? pp[1] : (f16)0.0f;
+          }
           pf[tq][u][r >> 3][r & 7] = pp[0];
           pf[tq][u][r >> 3][(r & 7) + 1] = pp[1];
         }
@@ -383,7 +410,8 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4 && TQ == 1 && GN_ATTN_
 #pragma unroll
   for (int tq = 0; tq < TQ; ++tq) {
     const float l_tot = pair_sum(l_run[tq]);
-    const float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
+    float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
+    if constexpr (DROP) inv = l_tot > 0.0f ? p.dr.inv_keep / l_tot : 0.0f;
     const int qrow = qw + 32 * tq;
     if (p.lse && hi == 0 && qrow < p.Nq)
       p.lse[((long)b * p.heads + h) * p.Nq + qrow] = l_tot > 0.0f ? m_run[tq] + __builtin_amdgcn_logf(l_tot) : INFINITY;
@@ -407,6 +435,34 @@ void launch_attn(const AttnParams& p, int B, hipStream_t st) {
   constexpr int QB = NW * TQ * 32;
   dim3 grid(((p.Nq + QB - 1) / QB) * p.heads * B);
   hipLaunchKernelGGL((attn_fwd_kernel<D, NW, TQ, VROW>), grid, dim3(NW * 64), 0, st, p);
+}
+
+template <int D>
+void launch_attn_dropout(const AttnDropParams& p, int B, hipStream_t st) {
+  dim3 grid(((p.Nq + 127) / 128) * p.heads * B);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, 4, 1, false, true>), grid, dim3(256), 0, st, p);
+}
+
+// x[bh][i][j] (f16, row stride ld) <- x o keep(bh, i, j) * inv_keep over i < nq, j < nk; with keep_out, the keep bytes go there instead
+// (same indexing) and x is not touched.  One thread per 8 keys of a row.
+__global__ __launch_bounds__(256) void attn_dropout_apply_kernel(f16* x, unsigned char* keep_out, int bh_n, int nq, int nk, long ld, const AttnDropout dr) {
+  const int chunks = (nk + 7) / 8;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)bh_n * nq * chunks) return;
+  const int c = (int)(idx % chunks);
+  const long row = idx / chunks;
+  const int i = (int)(row % nq), bh = (int)(row / nq);
+  const unsigned drow = attn_drop_row(attn_drop_head(dr, bh), i);
+  const long base = row * ld + c * 8;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int j = c * 8 + e;
+    if (j < nk) {
+      const bool keep = attn_drop_keep(drow, j, dr.threshold);
+      if (keep_out) keep_out[base + e] = keep ? 1 : 0;
+      else x[base + e] = keep ? (f16)((float)x[base + e] * dr.inv_keep) : (f16)0.0f;
+    }
+  }
 }
 
 bool stream_default() {
@@ -449,7 +505,8 @@ extern "C" int32_t gn_attention_set_variant(int32_t variant) {
   return prev;
 }
 
-int32_t gn_launch_attention(gn_ctx* ctx, const gn_attn_desc* d) {
+// the argument checks of the forward entry points and the kernel arguments made from a descriptor
+static int32_t attn_params(const gn_attn_desc* d, AttnParams& p) {
   GN_REQUIRE(d && d->q && d->k && d->vt && d->o, "gn_attention_fwd: null pointer");
   GN_REQUIRE(d->D == 64 || d->D == 32, "gn_attention_fwd: head dim %d unsupported (32 or 64)", d->D);
   GN_REQUIRE(d->B > 0 && d->heads > 0 && d->Nq > 0 && d->Nk > 0, "gn_attention_fwd: empty problem");
@@ -459,13 +516,45 @@ int32_t gn_launch_attention(gn_ctx* ctx, const gn_attn_desc* d) {
   GN_REQUIRE(((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->k & 15) == 0 && ((uintptr_t)d->vt & 15) == 0 && ((uintptr_t)d->o & 7) == 0, "gn_attention_fwd: pointer alignment");
   GN_REQUIRE(d->q_bs % 8 == 0 && d->k_bs % 8 == 0 && d->vt_bs % 8 == 0 && d->o_bs % 4 == 0, "gn_attention_fwd: batch strides alignment");
   GN_REQUIRE(d->scale > 0.0f, "gn_attention_fwd: scale must be positive");
-  AttnParams p;
   p.q = (const f16*)d->q; p.k = (const f16*)d->k; p.vt = (const f16*)d->vt; p.o = (f16*)d->o;
   p.q_bs = d->q_bs; p.k_bs = d->k_bs; p.vt_bs = d->vt_bs; p.o_bs = d->o_bs;
   p.q_rs = d->q_rs; p.k_rs = d->k_rs; p.vt_rs = d->vt_rs; p.o_rs = d->o_rs;
   p.heads = d->heads; p.Nq = d->Nq; p.Nk = d->Nk; p.causal = d->causal;
   p.scale_log2 = d->scale * 1.4426950408889634f;
   p.lse = d->lse;
+  return GN_OK;
+}
+
+extern "C" int32_t gn_attention_dropout_fwd(gn_ctx* ctx, const gn_attn_desc* d, const gn_attn_dropout* dr) {
+  GN_REQUIRE(ctx, "gn_attention_dropout_fwd: null ctx");
+  AttnDropParams p;
+  if (const int32_t rc = attn_params(d, p)) return rc;
+  GN_REQUIRE(!d->causal && !d->v_rowmajor, "gn_attention_dropout_fwd: non-causal attention with V^T only");
+  if (const int32_t rc = attn_dropout_args(dr, p.dr, "gn_attention_dropout_fwd")) return rc;
+  // always this file's 4-wave x 32-row kernel (attention_stream.hip / attention_pwg.hip have no dropout form)
+  if (d->D == 32) launch_attn_dropout<32>(p, d->B, ctx->stream);
+  else launch_attn_dropout<64>(p, d->B, ctx->stream);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+extern "C" int32_t gn_attention_dropout_apply(gn_ctx* ctx, void* x, int32_t bh, int32_t nq, int32_t nk, int64_t ld, const gn_attn_dropout* dr,
+                                              void* keep_out) {
+  GN_REQUIRE(ctx && (x || keep_out), "gn_attention_dropout_apply: null ctx / buffer");
+  GN_REQUIRE(bh > 0 && nq > 0 && nk > 0 && ld >= nk, "gn_attention_dropout_apply: bh %d, nq %d, nk %d must be positive and ld %lld >= nk", bh, nq, nk, (long long)ld);
+  AttnDropout a;
+  if (const int32_t rc = attn_dropout_args(dr, a, "gn_attention_dropout_apply")) return rc;
+  const long n = (long)bh * nq * ((nk + 7) / 8);
+  GN_REQUIRE((n + 255) / 256 <= 0x7fffffffL, "gn_attention_dropout_apply: problem too large");
+  hipLaunchKernelGGL(attn_dropout_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (f16*)x, (unsigned char*)keep_out, bh, nq, nk,
+                     (long)ld, a);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int32_t gn_launch_attention(gn_ctx* ctx, const gn_attn_desc* d) {
+  AttnParams p;
+  if (const int32_t rc = attn_params(d, p)) return rc;
   if (d->D == 32) {
     launch_attn<32, 4, 1>(p, d->B, ctx->stream);
   } else {

@@ -14,6 +14,7 @@
 // gn_transpose2d (96 transposes per step, twice the streamed bytes and LDS).
 #include <type_traits>
 
+#include "attention_dropout.h"
 #include "common.h"
 
 // waves per SIMD passed to __launch_bounds__: with the hint the dK / dV kernel comes out at 166 VGPRs (three waves per SIMD) instead of 206
@@ -41,6 +42,10 @@ struct AttnBwdParams {
   int heads, Nq, Nk, Nk_rows;
   float scale, scale_log2;
 };
+// the dropout form's arguments ride behind the plain ones, so the plain instantiations keep their kernel arguments as they are
+struct AttnBwdDropParams : AttnBwdParams { AttnDropout dr; };
+template <bool DROP>
+using BwdParamsOf = std::conditional_t<DROP, AttnBwdDropParams, AttnBwdParams>;
 
 __device__ __forceinline__ int swap23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
 __device__ __forceinline__ int perm_row(int r) { return (r & 32) | swap23(r & 31); }
@@ -149,7 +154,12 @@ __device__ __forceinline__ f16x8 tr_frag(const unsigned char* tile, const TrOffs
   return __builtin_bit_cast(f16x8, BwdH8{lo, hi});
 }
 
-__global__ __launch_bounds__(256, GN_ATTNB_DQ_WAVES) void attn_bwd_dq_kernel(const AttnBwdParams p) {
+// DROP (gn_attention_dropout_bwd, both kernels): with keep from attention_dropout.h and O the dropped output,
+//     dV = (P o keep / (1 - p))^T dO,   dP = (dO V^T) o keep / (1 - p),   dS = scale P (dP - delta),   delta as before.
+// keep is evaluated for the (query, key) each accumulator holds: here the lane owns the query (one row hash per lane) and the accumulators
+// run over keys; in the dK / dV kernel the lane owns the key and the row hashes of the streamed queries come from LDS, next to lse / delta.
+template <bool DROP>
+__global__ __launch_bounds__(256, GN_ATTNB_DQ_WAVES) void attn_bwd_dq_kernel(const BwdParamsOf<DROP> p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * TILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
@@ -177,6 +187,8 @@ __global__ __launch_bounds__(256, GN_ATTNB_DQ_WAVES) void attn_bwd_dq_kernel(con
   const float L = qlive ? p.lse[sidx] : 0.0f;
   const float dl = qlive ? p.delta[sidx] : 0.0f;
   const float c = p.scale_log2, sc = p.scale;
+  [[maybe_unused]] unsigned drow = 0;
+  if constexpr (DROP) drow = attn_drop_row(attn_drop_head(p.dr, b * p.heads + h), qrow);
 
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   f32x16 acc[2] = {zero16, zero16};
@@ -225,7 +237,9 @@ __global__ __launch_bounds__(256, GN_ATTNB_DQ_WAVES) void attn_bwd_dq_kernel(con
       for (int r = 0; r < 16; ++r) {
         float pv = __builtin_amdgcn_exp2f(fmaf(s[u][r], c, -L));
         if constexpr (LAST) pv = (j0 + 32 * u + 16 * (r >> 3) + 8 * hi + (r & 7) >= p.Nk) ? 0.0f : pv;  // keys past Nk (only the last tile has any)
-        dsf[u][r >> 3][r & 7] = (f16)(pv * (dp[u][r] - dl) * sc);
+        float dpv = dp[u][r];
+        if constexpr (DROP) dpv = attn_drop_keep(drow, j0 + 32 * u + 16 * (r >> 3) + 8 * hi + (r & 7), p.dr.threshold) ? dpv * p.dr.inv_keep : 0.0f;
+        dsf[u][r >> 3][r & 7] = (f16)(pv * (dpv - dl) * sc);
       }
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -260,8 +274,10 @@ __global__ __launch_bounds__(256, GN_ATTNB_DQ_WAVES) void attn_bwd_dq_kernel(con
 // ---- dK, dV ----------------------------------------------------------------------------------------------------------------
 constexpr int KV_BUF = 2 * TILE + 2 * 64 * 4;  // Q, dO tiles + lse + delta of the query tile
 
-__global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(const AttnBwdParams p) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * KV_BUF];
+template <bool DROP>
+__global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(const BwdParamsOf<DROP> p) {
+  constexpr int BUF = KV_BUF + (DROP ? 64 * 4 : 0);  // dropout: + the mask's row hash of the 64 streamed queries
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   int blk, h, b;
@@ -299,8 +315,10 @@ __global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(c
   TileStream sg = make_stream(wv, lane, p.do_rs, true, (long)TS * p.do_rs * 2);
   int jn = 0;  // first query row of the next tile to stage
   float rl = 0.f, rd = 0.f;
+  [[maybe_unused]] unsigned dhead = 0, rh = 0;
+  if constexpr (DROP) dhead = attn_drop_head(p.dr, b * p.heads + h);
   auto dma_tile = [&](int buf) {  // the next tile in sequence; the 2 x 64 row statistics ride along through one register each
-    unsigned char* Qs = smem + buf * KV_BUF;
+    unsigned char* Qs = smem + buf * BUF;
     dma_stream(sq, rs_q, Qs, wv);
     dma_stream(sg, rs_g, Qs + TILE, wv);
     {  // every wave fetches the same 64 values (one wave would do, but "if (tid < 64)" is a branch per tile): clamped index, then a select
@@ -308,13 +326,15 @@ __global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(c
       const float l = lsep[rc], dd = delp[rc];
       rl = row < p.Nq ? l : INFINITY;  // dead query rows: P = exp2(.. - inf) = 0
       rd = row < p.Nq ? dd : 0.0f;
+      if constexpr (DROP) rh = attn_drop_row(dhead, row);
     }
     jn += TS;
   };
   auto store_stats = [&](int buf) {  // (all four waves write the same values)
-    unsigned char* Qs = smem + buf * KV_BUF;
+    unsigned char* Qs = smem + buf * BUF;
     reinterpret_cast<float*>(Qs + 2 * TILE)[lane] = rl;
     reinterpret_cast<float*>(Qs + 2 * TILE + 256)[lane] = rd;
+    if constexpr (DROP) reinterpret_cast<unsigned*>(Qs + 2 * TILE + 512)[lane] = rh;
   };
   if (ntiles > 0) {
     dma_tile(0);
@@ -327,10 +347,11 @@ __global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(c
   auto tile = [&](auto last_c) __attribute__((always_inline)) {  // (one branch per query tile: see the dQ kernel)
     constexpr bool LAST = decltype(last_c)::value;
     if constexpr (!LAST) dma_tile(cur ^ 1);  // buffer cur^1 was last read before the barrier that ended the previous iteration
-    const unsigned char* Qs = smem + cur * KV_BUF;
+    const unsigned char* Qs = smem + cur * BUF;
     const unsigned char* Gs = Qs + TILE;
     const float* Ls = reinterpret_cast<const float*>(Qs + 2 * TILE);
     const float* Ds = Ls + 64;
+    [[maybe_unused]] const unsigned* Hs = reinterpret_cast<const unsigned*>(Ds + 64);
 
     f32x16 s[2], dp[2];
 #pragma unroll
@@ -357,8 +378,14 @@ __global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(c
           const float dq_ = j < 4 ? d0[j & 3] : d1[j & 3];
           const int r = 8 * g + j;
           const float pv = __builtin_amdgcn_exp2f(fmaf(s[u][r], c, -Lq));
-          pf[u][g][j] = (f16)pv;
-          dsf[u][g][j] = (f16)(pv * (dp[u][r] - dq_) * sc);
+          if constexpr (DROP) {  // (the 1 / (1 - p) of dV is applied once, to the accumulators, at the end)
+            const bool keep = attn_drop_keep(Hs[base + j], key, p.dr.threshold);
+            pf[u][g][j] = keep ? (f16)pv : (f16)0.0f;
+            dsf[u][g][j] = (f16)(pv * ((keep ? dp[u][r] * p.dr.inv_keep : 0.0f) - dq_) * sc);
+          } else {
+            pf[u][g][j] = (f16)pv;
+            dsf[u][g][j] = (f16)(pv * (dp[u][r] - dq_) * sc);
+          }
         }
       }
 #pragma unroll
@@ -391,7 +418,8 @@ __global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(c
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           a[i] = klive ? (f16)accK[dt][4 * g + i] : (f16)0.0f;
-          v[i] = klive ? (f16)accV[dt][4 * g + i] : (f16)0.0f;
+          if constexpr (DROP) v[i] = klive ? (f16)(accV[dt][4 * g + i] * p.dr.inv_keep) : (f16)0.0f;
+          else v[i] = klive ? (f16)accV[dt][4 * g + i] : (f16)0.0f;
         }
         *reinterpret_cast<f16x4*>(okp + dt * 32 + 8 * g + 4 * hi) = a;
         *reinterpret_cast<f16x4*>(ovp + dt * 32 + 8 * g + 4 * hi) = v;
@@ -401,7 +429,8 @@ __global__ __launch_bounds__(256, GN_ATTNB_DKV_WAVES) void attn_bwd_dkv_kernel(c
 
 }  // namespace
 
-extern "C" int32_t gn_attention_bwd(gn_ctx* ctx, const gn_attn_bwd_desc* d) {
+// the argument checks of the backward entry points and the kernel arguments made from a descriptor
+static int32_t attn_bwd_params(gn_ctx* ctx, const gn_attn_bwd_desc* d, AttnBwdParams& p) {
   GN_REQUIRE(ctx && d, "gn_attention_bwd: null ctx/desc");
   GN_REQUIRE(d->q && d->k && d->v && d->o && d->d_o && d->lse && d->delta && d->dq && d->dk && d->dv, "gn_attention_bwd: null pointer");
   GN_REQUIRE(d->D == 64, "gn_attention_bwd: head dim %d unsupported (64)", d->D);
@@ -416,7 +445,6 @@ extern "C" int32_t gn_attention_bwd(gn_ctx* ctx, const gn_attn_bwd_desc* d) {
   for (int i = 0; i < 5; ++i) GN_REQUIRE(((uintptr_t)in[i] & 15) == 0, "gn_attention_bwd: inputs must be 16-byte aligned");
   GN_REQUIRE(((uintptr_t)d->dq & 7) == 0 && ((uintptr_t)d->dk & 7) == 0 && ((uintptr_t)d->dv & 7) == 0, "gn_attention_bwd: outputs must be 8-byte aligned");
   GN_REQUIRE(d->scale > 0.0f, "gn_attention_bwd: scale must be positive");
-  AttnBwdParams p;
   p.q = (const f16*)d->q; p.k = (const f16*)d->k; p.v = (const f16*)d->v; p.o = (const f16*)d->o; p.d_o = (const f16*)d->d_o;
   p.qt = (const f16*)d->qt; p.kt = (const f16*)d->kt; p.dot = (const f16*)d->dot;
   p.lse = d->lse; p.delta = d->delta;
@@ -427,12 +455,30 @@ extern "C" int32_t gn_attention_bwd(gn_ctx* ctx, const gn_attn_bwd_desc* d) {
   p.dot_rs = d->dot_rs; p.dq_rs = d->dq_rs; p.dk_rs = d->dk_rs; p.dv_rs = d->dv_rs;
   p.heads = d->heads; p.Nq = d->Nq; p.Nk = d->Nk; p.Nk_rows = d->Nk_rows;
   p.scale = d->scale; p.scale_log2 = d->scale * 1.4426950408889634f;
+  return GN_OK;
+}
+
+template <bool DROP>
+static int32_t attn_bwd_launch(gn_ctx* ctx, const gn_attn_bwd_desc* d, const BwdParamsOf<DROP>& p) {
   const long nd = (long)d->B * d->Nq * d->heads;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, ctx->stream, p, d->B);
+  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, ctx->stream, (AttnBwdParams)p, d->B);
   GN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(((d->Nq + 127) / 128) * d->heads * d->B), dim3(256), 0, ctx->stream, p);
+  hipLaunchKernelGGL(attn_bwd_dq_kernel<DROP>, dim3(((d->Nq + 127) / 128) * d->heads * d->B), dim3(256), 0, ctx->stream, p);
   GN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(((d->Nk + 127) / 128) * d->heads * d->B), dim3(256), 0, ctx->stream, p);
+  hipLaunchKernelGGL(attn_bwd_dkv_kernel<DROP>, dim3(((d->Nk + 127) / 128) * d->heads * d->B), dim3(256), 0, ctx->stream, p);
   GN_LAUNCH_CHECK();
   return GN_OK;
+}
+
+extern "C" int32_t gn_attention_bwd(gn_ctx* ctx, const gn_attn_bwd_desc* d) {
+  AttnBwdParams p;
+  if (const int32_t rc = attn_bwd_params(ctx, d, p)) return rc;
+  return attn_bwd_launch<false>(ctx, d, p);
+}
+
+extern "C" int32_t gn_attention_dropout_bwd(gn_ctx* ctx, const gn_attn_bwd_desc* d, const gn_attn_dropout* dr) {
+  AttnBwdDropParams p;
+  if (const int32_t rc = attn_bwd_params(ctx, d, p)) return rc;
+  if (const int32_t rc = attn_dropout_args(dr, p.dr, "gn_attention_dropout_bwd")) return rc;
+  return attn_bwd_launch<true>(ctx, d, p);
 }

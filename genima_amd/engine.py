@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, GEMM_DMA, GEMM_PP, GEMM_PPP, GEMM_RING,
                    OUT_BATCH_TRANSPOSED, OUT_ROWMAJOR, TBLOCK_FRONT, TBLOCK_MID,
-                   TBLOCK_TAIL, AttnDesc, ConvGnDesc, ConvPatchDesc, GemmDesc, GenimaHipError, GroupNormDesc, NormOut, StatsSink, TBlockDesc, TBlockTapeSrc, check)
+                   TBLOCK_TAIL, AttnDesc, ConvGnDesc, ConvPatchDesc, GemmDesc, GenimaHipError, GroupNormDesc, NormOut, StatsSink, TBlockDesc, TBlockTapeSrc, attn_dropout_desc, check)
 
 F16 = torch.float16
 
@@ -1023,10 +1023,13 @@ class Engine:
     # ------------------------------------------------------------------------------------------------ attention
     def attention(self, q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, *, Nk: Optional[int] = None,
                   causal: bool = False, out: Optional[torch.Tensor] = None, name: Optional[str] = None,
-                  lse: Optional[torch.Tensor] = None, v_rowmajor: bool = False) -> torch.Tensor:
+                  lse: Optional[torch.Tensor] = None, v_rowmajor: bool = False, dropout=None) -> torch.Tensor:
         """q: [B, Nq, heads*D] view (last dim contiguous, may be a column slice), k: [B, Nk, heads*D] view,
         vt: [B, heads*D, Nk_pad] (V transposed) -- or, with v_rowmajor (D = 64), V itself as a [B, Nk, heads*D] view.
-        Returns o [B, Nq, heads*D].  lse: optional f32 [B, heads, Nq] (training)."""
+        Returns o [B, Nq, heads*D].  lse: optional f32 [B, heads, Nq] (training).
+        dropout: None or (p, seed) -- attention-probability dropout inside the kernel (gn_attention_dropout_fwd: non-causal, V^T; the mask
+        is a function of the 64-bit seed, include/genima_hip.h).  p = 0 is the plain call.  Training only: a recorded program would
+        replay one seed for ever, so the recording engine refuses it."""
         B, Nq, Cq = q.shape
         D = Cq // heads
         Nk = k.shape[1] if Nk is None else Nk
@@ -1041,6 +1044,12 @@ class Engine:
         d.B, d.heads, d.Nq, d.Nk, d.D, d.causal, d.scale = B, heads, Nq, Nk, D, int(causal), float(D) ** -0.5
         d.lse = _ptr(lse)
         d.v_rowmajor = int(v_rowmajor)
+        if dropout is not None and float(dropout[0]) > 0.0:
+            if self.record:
+                raise GenimaHipError("Engine.attention: dropout cannot be recorded into a program (the seed changes every step)")
+            dr = attn_dropout_desc(float(dropout[0]), int(dropout[1]))
+            check(self.lib.gn_attention_dropout_fwd(self._ctx, C.byref(d), C.byref(dr)), "gn_attention_dropout_fwd")
+            return out
         if self.record:
             check(self.lib.gn_program_add_attention(self._prog, C.byref(d)), "gn_program_add_attention")
             self._keepalive(q, k, vt, out)

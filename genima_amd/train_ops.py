@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import OUT_F32, OUT_ROWMAJOR, AttnBwdDesc, GemmDesc, GroupNormDesc, WgradDesc, check
+from ._lib import OUT_F32, OUT_ROWMAJOR, AttnBwdDesc, GemmDesc, GroupNormDesc, WgradDesc, attn_dropout_desc, check
 from .engine import Engine, _ptr
 
 F16, F32 = torch.float16, torch.float32
@@ -246,9 +246,20 @@ def softmax_bwd(E: Engine, p: torch.Tensor, dp: torch.Tensor, scale: float):
     return dp
 
 
-def attention_bwd(E: Engine, q, q_off: int, k, k_off: int, v, o, d_o, lse, heads: int, nk_valid: int, dq, dk, dv):
+def attention_dropout_apply(E: Engine, x: torch.Tensor, nk_valid: int, dropout) -> torch.Tensor:
+    """In place on a materialised f16 [B * heads, N, Nkr] tensor (P or dP of the batched-GEMM attention backward):
+    x * keep / (1 - p) over the nk_valid live key columns, with the mask of the flash kernels for the same ``dropout`` = (p, seed)."""
+    BH, N, Nkr = x.shape
+    assert x.is_contiguous() and x.dtype == F16
+    dr = attn_dropout_desc(float(dropout[0]), int(dropout[1]))
+    check(E.lib.gn_attention_dropout_apply(E._ctx, _ptr(x), BH, N, nk_valid, Nkr, C.byref(dr), None), "gn_attention_dropout_apply")
+    return x
+
+
+def attention_bwd(E: Engine, q, q_off: int, k, k_off: int, v, o, d_o, lse, heads: int, nk_valid: int, dq, dk, dv, dropout=None):
     """Flash-attention backward.  q [B, N, ldq] / k [B, Nkr, ldk] (head columns start at q_off / k_off), v / o / d_o [B, *, C];
-    dq / dk are written at the same column offsets of buffers shaped like q / k (they may be one buffer), dv like v."""
+    dq / dk are written at the same column offsets of buffers shaped like q / k (they may be one buffer), dv like v.
+    dropout: None or the (p, seed) the forward ran with (Engine.attention): gn_attention_dropout_bwd when p > 0."""
     B, N, ldq = q.shape
     Nkr, ldk = k.shape[1], k.shape[2]
     Cc = v.shape[-1]
@@ -263,7 +274,11 @@ def attention_bwd(E: Engine, q, q_off: int, k, k_off: int, v, o, d_o, lse, heads
     d.dq_bs, d.dk_bs, d.dv_bs = dq.stride(0), dk.stride(0), dv.stride(0)
     d.dq_rs, d.dk_rs, d.dv_rs = dq.stride(1), dk.stride(1), dv.stride(1)
     d.B, d.heads, d.Nq, d.Nk, d.Nk_rows, d.D, d.scale = B, heads, N, nk_valid, Nkr, D, float(D) ** -0.5
-    check(E.lib.gn_attention_bwd(E._ctx, C.byref(d)), "gn_attention_bwd")
+    if dropout is not None and float(dropout[0]) > 0.0:
+        dr = attn_dropout_desc(float(dropout[0]), int(dropout[1]))
+        check(E.lib.gn_attention_dropout_bwd(E._ctx, C.byref(d), C.byref(dr)), "gn_attention_dropout_bwd")
+    else:
+        check(E.lib.gn_attention_bwd(E._ctx, C.byref(d)), "gn_attention_bwd")
 
 
 def layernorm_bwd(E: Engine, x, gamma, dy, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,

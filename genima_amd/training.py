@@ -520,9 +520,13 @@ class Graph:
         return self._push(out, bw)
 
     # ---- attention: flash forward, materialised batched-GEMM backward (P recomputed from q, k)
-    def attention(self, q: Var, q_off: int, k: Var, k_off: int, v: Var, heads: int, nk_valid: int) -> Var:
+    def attention(self, q: Var, q_off: int, k: Var, k_off: int, v: Var, heads: int, nk_valid: int, dropout=None) -> Var:
         """q.t [B, N, ldq] (queries = columns q_off..q_off+C), k.t [B, Nkr, ldk] (keys = columns k_off..), v.t [B, Nkr, C]; rows
-        >= nk_valid of k / v are zero padding (Nkr % 8 == 0).  q and k may be the same Var (fused self-attention q|k projection)."""
+        >= nk_valid of k / v are zero padding (Nkr % 8 == 0).  q and k may be the same Var (fused self-attention q|k projection).
+        dropout: None or (p, seed): attention-probability dropout (Engine.attention); the forward, the flash backward and the
+        materialised backward evaluate one mask, the function of the seed that include/genima_hip.h states."""
+        if dropout is not None and float(dropout[0]) <= 0.0:
+            dropout = None
         E = self.E
         B, N, ldq = q.t.shape
         Nkr, ldk = k.t.shape[1], k.t.shape[2]
@@ -533,7 +537,7 @@ class Graph:
         vt = T.transpose2d(E, v.t, Nkr, Cc, batch=B, in_bs=Nkr * Cc, pad_to=64).view(B, Cc, -1)
         flash = self.flash_bwd and D == 64
         lse = torch.empty((B, heads, N), dtype=F32, device=E.device) if flash else None
-        o = E.attention(q.t[:, :, q_off:q_off + Cc], k.t[:, :, k_off:k_off + Cc], vt, heads, Nk=nk_valid, lse=lse)
+        o = E.attention(q.t[:, :, q_off:q_off + Cc], k.t[:, :, k_off:k_off + Cc], vt, heads, Nk=nk_valid, lse=lse, dropout=dropout)
         out = Var(o, q.needs or k.needs or v.needs)
         fused = q is k or q.cell is k.cell
 
@@ -543,7 +547,7 @@ class Graph:
             dq = torch.empty_like(q.t)
             dk = dq if fused else zeros(k.t.shape, dtype=F16, device=E.device)
             dv = zeros(v.t.shape, dtype=F16, device=E.device)
-            T.attention_bwd(E, q.t, q_off, k.t, k_off, v.t, o, dO, lse, heads, nk_valid, dq, dk, dv)
+            T.attention_bwd(E, q.t, q_off, k.t, k_off, v.t, o, dO, lse, heads, nk_valid, dq, dk, dv, dropout=dropout)
             self.acc(q, dq)
             if not fused:
                 self.acc(k, dk)
@@ -558,16 +562,21 @@ class Graph:
             T.softmax_rows_masked(E, P, scale, nk_valid)
             dS = torch.empty((BH, N, Nkr), dtype=F16, device=E.device)
             T.gemm(E, dO, v.t, dS, N, Nkr, D, Cc, Cc, Nkr, batch=BH, batch_inner=heads, a_bs=(N * Cc, D), w_bs=(Nkr * Cc, D), out_bs=sbs)
+            Pd = P
+            if dropout is not None:  # dP = (dO V^T) o keep / (1 - p); P stays undropped for the softmax backward, dV takes the masked copy
+                T.attention_dropout_apply(E, dS, nk_valid, dropout)
+                if v.needs:
+                    Pd = T.attention_dropout_apply(E, P.clone(), nk_valid, dropout)
             T.softmax_bwd(E, P, dS, scale)
             tbs = (heads * Nkr * N, Nkr * N)
             if v.needs:
-                PT = T.transpose2d(E, P, N, Nkr, batch=BH, in_bs=N * Nkr)
+                PT = T.transpose2d(E, Pd, N, Nkr, batch=BH, in_bs=N * Nkr)
                 dOT = T.transpose2d(E, dO, N, Cc, batch=B, in_bs=N * Cc)
                 dV = torch.empty((B, Nkr, Cc), dtype=F16, device=E.device)
                 T.gemm(E, PT, dOT, dV, Nkr, D, N, N, N, Cc, batch=BH, batch_inner=heads, a_bs=tbs, w_bs=(Cc * N, D * N), out_bs=(Nkr * Cc, D))
                 self.acc(v, dV)
                 del PT, dOT
-            del P
+            del P, Pd
             dq = torch.empty_like(q.t) if q.needs else None
             dk = dq if fused else (torch.empty_like(k.t) if k.needs else None)
             if dq is not None:

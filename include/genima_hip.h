@@ -345,6 +345,30 @@ typedef struct gn_attn_bwd_desc {
 } gn_attn_bwd_desc;
 int32_t gn_attention_bwd(gn_ctx* ctx, const gn_attn_bwd_desc* d);
 
+/* Attention-probability dropout inside the flash kernels (nn.MultiheadAttention's dropout under the reference ACT's DETR layers,
+ * controller/method/genima_act.py; p = 0.1 there).  The keep mask is a pure function of (seed, bh = b * heads + h, query row i, key j),
+ * evaluated wherever a kernel holds a probability, so nothing is materialised.  All arithmetic is uint32 and wraps:
+ *   mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *   a = mix(seed_lo ^ 0x6A09E667 ^ (bh * 0x9E3779B9))
+ *   r = mix(mix((a ^ seed_hi) + i * 0x85EBCA6B) ^ (j * 0xC2B2AE35))
+ *   keep(i, j) = r >= threshold,   threshold = min(2^32 - 1, floor(p * 2^32)) (made on the host in f64),   inv_keep = 1 / (1 - p)
+ * threshold = 0 keeps every element.  O = ((softmax(S) o keep) * inv_keep) V; the row statistics are those of the undropped P, so lse is the
+ * value gn_attention_fwd writes.  Backward: delta = sum_d dO O (O the dropped output), dV = (P o keep * inv_keep)^T dO,
+ * dP = (dO V^T) o keep * inv_keep, dS = scale P (dP - delta), dQ = dS K, dK = dS^T Q. */
+typedef struct gn_attn_dropout {
+  uint32_t threshold, seed_lo, seed_hi;
+  float inv_keep;
+} gn_attn_dropout;
+/* gn_attention_fwd with dropout: non-causal, V^T given (v_rowmajor = 0), D in {32, 64}; always csrc/attention.hip's 4-wave x 32-row kernel. */
+int32_t gn_attention_dropout_fwd(gn_ctx* ctx, const gn_attn_desc* d, const gn_attn_dropout* dr);
+/* gn_attention_bwd with dropout (D = 64), on the o and lse of gn_attention_dropout_fwd with the same gn_attn_dropout; the padded-row and
+ * zero-fill contract of gn_attention_bwd holds unchanged. */
+int32_t gn_attention_dropout_bwd(gn_ctx* ctx, const gn_attn_bwd_desc* d, const gn_attn_dropout* dr);
+/* The same mask on a materialised f16 tensor x [bh][nq][ld] (the batched-GEMM attention backward: P, dP), in place:
+ * x[b][i][j] = x[b][i][j] * keep(b, i, j) * inv_keep for i < nq, j < nk; columns nk .. ld - 1 are not touched.  With keep_out (uint8, same
+ * indexing) the keep bytes (0 / 1) are written there instead and x is not read or written (x may be NULL): the mask itself, for tests. */
+int32_t gn_attention_dropout_apply(gn_ctx* ctx, void* x, int32_t bh, int32_t nq, int32_t nk, int64_t ld, const gn_attn_dropout* dr, void* keep_out);
+
 /* ---- K2: GroupNorm(+SiLU), NHWC --------------------------------------------------------------------------------
  * y = act(GroupNorm_G(cat(x, x2)) * gamma + beta).  Three launches: coalesced partial statistics over pixel slabs, a finalize
  * that folds (mean, rstd, gamma, beta) into per-(b, c) scale/shift, and a coalesced apply.  Replaces torch
