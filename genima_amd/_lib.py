@@ -149,6 +149,13 @@ class ConvPatchDesc(C.Structure):
     ]
 
 
+class ReplayGatherDesc(C.Structure):
+    """gn_replay_gather_desc: one batch out of the device-resident ACT replay (gn_replay_gather)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("frame_ptr", "qpos", "action", "obs_index", "first_obs", "last_tr", "idx", "images", "images_u8",
+                                           "low_dim_state", "action_out", "lang_tokens", "episode", "tokens_out")]
+                + [("pixels", C.c_int64), ("N_obs", C.c_int64)] + [(n, C.c_int32) for n in ("B", "V", "fs", "T", "S", "A", "N", "N_ep", "L_tok")])
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("workspace", C.c_void_p),
@@ -227,6 +234,7 @@ SIGNATURES = {
     "gn_image_f16_to_u8": (_I32, [_P, _P, _P, _I64, _I32]),
     "gn_image_normalize_u8": (_I32, [_P, _P, _P, _I64, _I32, _F, _F, _F, _F, _F, _F]),
     "gn_gather_u8_to_f16": (_I32, [_P, _P, _P, _I32, _I64, _I32, _F, _F]),
+    "gn_replay_gather": (_I32, [_P, C.POINTER(ReplayGatherDesc)]),
     "gn_gather_rows": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_argmax_rows_i32": (_I32, [_P, _P, _P, _I32, _I32]),
     "gn_copy4d": (_I32, [_P, _P, _P, _P, _P, _P, _I32]),
@@ -370,7 +378,7 @@ def load() -> C.CDLL:
             raise GenimaHipError(f"{LIB_PATH} does not export {name} (stale build?)") from e
         fn.restype = res
         fn.argtypes = args
-    for which, cls in enumerate((GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc)):
+    for which, cls in enumerate((GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc, ReplayGatherDesc)):
         if int(lib.gn_desc_sizeof(which)) != C.sizeof(cls):  # a stale .so against newer Python (or the reverse) would read garbage descriptors
             raise GenimaHipError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(lib.gn_desc_sizeof(which))} in the library, {C.sizeof(cls)} in the "
                                  "binding (stale build? run `python -m genima_amd.build`)")

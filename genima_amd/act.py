@@ -692,7 +692,31 @@ class GenimaACT:
         ``elastic_field``: "host", the default, or "device" -- where the elastic warp's displacement field is blurred).  The config key
         ``attn_dropout`` (default 0.0: off) is the trainer's attention-probability dropout; the reference's value is the ``dropout`` of
         its DETR layers, 0.1 (``attn_dropout: 0.1`` turns it on; a ``trainer_kw`` of the same name overrides the config)."""
-        from .act_training import ACTTrainer, act_augment, act_train_schema
+        self._ensure_trainer(trainer_kw)
+        batch = next(replay_iter)
+        batch = {k: torch.as_tensor(v) for k, v in batch.items()}
+        qpos = batch["low_dim_state"].flatten(1).float()
+        keys = [k for k in batch if re.match(r".*rgb(?!.*?tp1)", k) and "tp1" not in k]
+        image = torch.stack([batch[k] for k in keys], dim=1)  # [B, V, fs, 3, H, W]
+        B = image.shape[0]
+        image = image.reshape(B, -1, 3, image.shape[-2], image.shape[-1]).to(self.device)
+        img_u8 = (image if image.dtype == torch.uint8 else image.round().clamp(0, 255).to(torch.uint8)).permute(0, 1, 3, 4, 2).contiguous()
+        return self._update_converted(img_u8, qpos, batch.get("lang_tokens"), batch["action"].float(), batch.get("reward"))
+
+    def update_device(self, batch, step: int = 0, **trainer_kw) -> Dict[str, float]:
+        """``update`` on a batch that is already on the device in the trainer's layout (``replay.DeviceReplay.sample``): ``images`` f16
+        [B, V * fs, H, W, 8] on the 0..1 scale, ``low_dim_state`` f32 [B, fs, S], ``action`` f32 [B, T, A], ``lang_tokens`` int [B, 1, 77]
+        and ``reward``.  Nothing is stacked, uploaded, rounded or permuted per step; from the batch-conversion boundary on it is ``update``
+        itself -- same trainer, same augmentation draws, same metrics."""
+        self._ensure_trainer(trainer_kw)
+        img = batch["images"]
+        if not (img.is_cuda and img.dtype == torch.float16 and img.dim() == 5 and img.shape[-1] == 8):
+            raise GenimaHipError(f"update_device: images must be a device f16 [B, V, H, W, 8] tensor, got {img.dtype} {tuple(img.shape)}")
+        return self._update_converted(img, batch["low_dim_state"].flatten(1).float(), batch.get("lang_tokens"), batch["action"].float(),
+                                      batch.get("reward"))
+
+    def _ensure_trainer(self, trainer_kw):
+        from .act_training import ACTTrainer, act_train_schema
 
         if getattr(self, "_trainer", None) is None:
             sch = act_train_schema(self.config)
@@ -704,24 +728,26 @@ class GenimaACT:
             if fresh:
                 sd.update(weights.synth_state_dict(fresh, 77))  # CVAE encoder: fresh init
             trainer_kw.setdefault("attn_dropout", float(self.config.get("attn_dropout", 0.0)))
+            for k in ("lr", "lr_backbone", "actor_grad_clip"):  # the method yaml's keys (genima_act.yaml:7-12), where the config carries them
+                if k in self.config:
+                    trainer_kw.setdefault(k, self.config[k])
             self._trainer = ACTTrainer(Engine(self.device), self.config, sd, self.clip_config, self.Wclip, **trainer_kw)
             self._aug_gen = torch.Generator().manual_seed(0)
-        batch = next(replay_iter)
-        batch = {k: torch.as_tensor(v) for k, v in batch.items()}
-        qpos = batch["low_dim_state"].flatten(1).float()
-        keys = [k for k in batch if re.match(r".*rgb(?!.*?tp1)", k) and "tp1" not in k]
-        image = torch.stack([batch[k] for k in keys], dim=1)  # [B, V, fs, 3, H, W]
-        B = image.shape[0]
-        image = image.reshape(B, -1, 3, image.shape[-2], image.shape[-1]).to(self.device)
-        img_u8 = (image if image.dtype == torch.uint8 else image.round().clamp(0, 255).to(torch.uint8)).permute(0, 1, 3, 4, 2).contiguous()
+        return self._trainer
+
+    def _update_converted(self, images, qpos, lang_tokens, action, reward) -> Dict[str, float]:
+        """The shared half of ``update`` / ``update_device``, behind the batch conversion: ``images`` uint8 [B, V, H, W, 3] or f16
+        [B, V, H, W, 8] on the device."""
+        from .act_training import act_augment
+
         task = None
         if self.config.get("use_lang_cond"):
-            task, _ = self.encode_clip_text(batch["lang_tokens"])
+            task, _ = self.encode_clip_text(lang_tokens)
         tr = self._trainer
-        imgs = act_augment(tr.E, img_u8, self._aug_gen, field=self.config.get("elastic_field", "host")) if self.config.get("data_augmentation", True) else img_u8
-        metrics = tr.update(imgs, qpos, task, batch["action"].float())
-        if "reward" in batch:
-            metrics["batch_reward"] = float(batch["reward"].float().mean())
+        imgs = act_augment(tr.E, images, self._aug_gen, field=self.config.get("elastic_field", "host")) if self.config.get("data_augmentation", True) else images
+        metrics = tr.update(imgs, qpos, task, action)
+        if reward is not None:
+            metrics["batch_reward"] = float(reward.float().mean())
         # the eval path reads the packed inference weights and state_dict() the host copies: both are refreshed lazily (act() /
         # _own_state()), not with a device sync + full-state D2H copy per training step
         self._dirty = self._stale_host = True

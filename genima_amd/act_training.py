@@ -101,9 +101,14 @@ def attn_call_seed(trainer_seed: int, step: int, index: int) -> int:
 class ACTTrainer:
     def __init__(self, E: Engine, cfg, state_dict: Dict[str, torch.Tensor], clip_cfg, clip_W, *, lr: float = 5e-5, lr_backbone: float = 1e-5,
                  weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, loss_scale: float = 1024.0, dropout: float = 0.1,
-                 state_dropout: float = 0.3, seed: int = 0, attn_dropout: float = 0.0):
+                 state_dropout: float = 0.3, seed: int = 0, attn_dropout: float = 0.0, actor_grad_clip: Optional[float] = None):
         """attn_dropout: nn.MultiheadAttention's attention-probability dropout on every attention of the update (the reference's DETR
-        layers run it at their ``dropout``, 0.1); 0.0, the default, runs the plain kernels."""
+        layers run it at their ``dropout``, 0.1); 0.0, the default, runs the plain kernels.  actor_grad_clip: the reference's
+        ``actor_grad_clip`` (controller/method/genima_act.py:403-404, ``null`` in its yaml): the max norm of ``clip_grad_norm_`` over all
+        trainable weights; None, the default, does not clip."""
+        if actor_grad_clip is not None and not float(actor_grad_clip) > 0.0:
+            raise ValueError(f"ACTTrainer: actor_grad_clip must be None or > 0, got {actor_grad_clip!r}")
+        self.grad_clip = None if actor_grad_clip is None else float(actor_grad_clip)
         if not 0.0 <= float(attn_dropout) < 1.0:
             raise ValueError(f"ACTTrainer: attn_dropout must be in [0, 1), got {attn_dropout!r}")
         self.E, self.cfg, self.clip_cfg, self.clip_W = E, dict(cfg), clip_cfg, clip_W
@@ -359,12 +364,14 @@ class ACTTrainer:
         return out4
 
     def optimizer_step(self):
-        """AdamW over the two contiguous groups (backbone: lr_backbone; rest: lr), no clipping; a non-finite gradient skips the step and
+        """AdamW over the two contiguous groups (backbone: lr_backbone; rest: lr), the gradient clipped to ``actor_grad_clip`` when that is
+        set; a non-finite gradient skips the step and
         halves the loss scale (the f16 path's GradScaler; the fp32 reference has none)."""
         E, cn = self.E, self.cn
         inv = 1.0 / self.loss_scale
         T.sumsq(E, cn.grad, self._ss)
-        T.clip_coef(E, self._ss, self._clip, 1e30, inv)  # max_norm = inf: coefficient 1, flag = non-finite gradient
+        # without actor_grad_clip max_norm = inf: coefficient 1, flag = non-finite gradient
+        T.clip_coef(E, self._ss, self._clip, 1e30 if self.grad_clip is None else self.grad_clip, inv)
         self.opt_step += 1
         nb, n = self.n_backbone, cn.numel
         for a, b, lr in ((0, nb, self.lr_backbone), (nb, n, self.lr)):
@@ -458,9 +465,10 @@ def elastic_displacement_device(E: Engine, H: int, W: int, alpha: float = 80.0, 
     return disp
 
 
-def act_augment(E: Engine, images_u8: torch.Tensor, generator: Optional[torch.Generator] = None, p: float = 0.5, noise_std: float = 5.0,
+def act_augment(E: Engine, images: torch.Tensor, generator: Optional[torch.Generator] = None, p: float = 0.5, noise_std: float = 5.0,
                 field: str = "host"):
-    """``GenimaACTPolicy.aug_transforms`` (controller/method/genima_act.py:150-163) on uint8 [B, V, H, W, 3] device images:
+    """``GenimaACTPolicy.aug_transforms`` (controller/method/genima_act.py:150-163) on uint8 [B, V, H, W, 3] device images -- or on their
+    f16 [B, V, H, W, 8] conversion to the 0..1 scale (``replay.DeviceReplay.sample``), which skips the first kernel and is not written to:
     RandomApply(p)[ElasticTransform(80, 10)], RandomApply(p)[ColorJitter(0.2, 0.2, 0.1, 0.05)], RandomApply(p)[RandomCrop(size, padding
     = 4)] -- each called on the whole batch tensor, so ONE draw per call -- then AddGaussianNoise(0, 5.0) on the 0..255 scale
     (controller/utils/misc.py:50-65).  Returns f16 [B, V, H, W, 8] on the 0..1 scale (the trainer's float-image input).  The random
@@ -472,8 +480,13 @@ def act_augment(E: Engine, images_u8: torch.Tensor, generator: Optional[torch.Ge
 
     if field not in ("host", "device"):
         raise ValueError(f"act_augment: field must be 'host' or 'device', got {field!r}")
-    B, V, H, W, _ = images_u8.shape
-    x = E.image_u8_to_f16(images_u8.view(B * V, H, W, 3), 8, 1.0, 0.0)
+    B, V, H, W, Cc = images.shape
+    if images.dtype == F16:
+        if Cc != 8 or not images.is_contiguous():
+            raise ValueError(f"act_augment: f16 images must be contiguous [B, V, H, W, 8], got {tuple(images.shape)}")
+        x = images.view(B * V, H, W, 8)
+    else:
+        x = E.image_u8_to_f16(images.view(B * V, H, W, 3), 8, 1.0, 0.0)
     if float(torch.rand(1, generator=generator)) < p:
         if field == "device":
             disp = elastic_displacement_device(E, H, W, generator=generator)

@@ -1392,6 +1392,45 @@ class Engine:
         check(self.lib.gn_gather_u8_to_f16(self._ctx, _ptr(ptrs), _ptr(out), ptrs.numel(), H * W, cpad, float(mul), float(add)), "gn_gather_u8_to_f16")
         return out
 
+    def replay_gather(self, frame_ptr, qpos, action, obs_index, first_obs, last_tr, idx, frame_shape, V: int, fs: int, T: int, *,
+                      want_u8: bool = False, lang_tokens=None, episode=None, out=None):
+        """``gn_replay_gather``: one ACT training batch out of device-resident tables (genima_amd/replay.py), one launch.  ``idx``: the
+        batch's transition indices -- a DEVICE int32 [B] tensor (used as it is; the kernel clamps it into [0, N)), or host integers, which are
+        checked against [0, N) here and uploaded (B x 4 bytes).  -> (images f16 [B, V * fs, H, W, 8] on the 0..1 scale, images_u8
+        [B, V * fs, H, W, 3] or None, low_dim_state f32 [B, fs, S], action f32 [B, T, A], tokens int32 [B, L_tok] or None -- with
+        ``lang_tokens`` int32 [N_ep, L_tok] and ``episode`` int32 [N]); ``out``: the same five to write into.  Eager engines
+        only (a recorded program would replay the indices of one batch)."""
+        if self.record:
+            raise RuntimeError("replay_gather is an eager op: the batch indices change from call to call")
+        N_obs, S = int(qpos.shape[0]), int(qpos.shape[1])
+        N, A = int(action.shape[0]), int(action.shape[1])
+        H, W = int(frame_shape[0]), int(frame_shape[1])
+        for t, dt, shape in ((frame_ptr, torch.int64, (N_obs * V,)), (qpos, torch.float32, (N_obs, S)), (action, torch.float32, (N, A)), (obs_index, torch.int32, (N,)),
+                             (first_obs, torch.int32, (N,)), (last_tr, torch.int32, (N,))):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
+        if not (isinstance(idx, torch.Tensor) and idx.is_cuda):
+            host = torch.as_tensor(idx).reshape(-1).to(torch.int64)
+            if host.numel() == 0 or bool((host < 0).any()) or bool((host >= N).any()):
+                raise GenimaHipError(f"replay_gather: transition indices must lie in [0, {N}), got {host.tolist()}")
+            idx = host.to(torch.int32).to(self.device, non_blocking=True)
+        assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+        B = idx.numel()
+        if out is None:
+            out = (torch.empty((B, V * fs, H, W, 8), dtype=F16, device=self.device),
+                   torch.empty((B, V * fs, H, W, 3), dtype=torch.uint8, device=self.device) if want_u8 else None,
+                   torch.empty((B, fs, S), dtype=torch.float32, device=self.device), torch.empty((B, T, A), dtype=torch.float32, device=self.device),
+                   torch.empty((B, lang_tokens.shape[1]), dtype=torch.int32, device=self.device) if lang_tokens is not None else None)
+        img, img8, low, act, tok = out
+        N_ep, L_tok = (int(lang_tokens.shape[0]), int(lang_tokens.shape[1])) if lang_tokens is not None else (0, 0)
+        for t, dt, shape in ((lang_tokens, torch.int32, (N_ep, L_tok)), (episode, torch.int32, (N,)), (tok, torch.int32, (B, L_tok)), (img, F16, (B, V * fs, H, W, 8)), (img8, torch.uint8, (B, V * fs, H, W, 3)), (low, torch.float32, (B, fs, S)), (act, torch.float32, (B, T, A))):
+            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape), (dt, shape)
+        d = _lib.ReplayGatherDesc(frame_ptr=_ptr(frame_ptr), qpos=_ptr(qpos), action=_ptr(action), obs_index=_ptr(obs_index), first_obs=_ptr(first_obs),
+                                  last_tr=_ptr(last_tr), idx=_ptr(idx), images=_ptr(img), images_u8=_ptr(img8), low_dim_state=_ptr(low), action_out=_ptr(act),
+                                  lang_tokens=_ptr(lang_tokens), episode=_ptr(episode), tokens_out=_ptr(tok), pixels=H * W, N_obs=N_obs, B=B, V=V, fs=fs, T=T,
+                                  S=S, A=A, N=N, N_ep=N_ep, L_tok=L_tok)
+        check(self.lib.gn_replay_gather(self._ctx, C.byref(d)), "gn_replay_gather")
+        return img, img8, low, act, tok
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

@@ -478,6 +478,40 @@ int32_t gn_image_f16_to_u8(gn_ctx* ctx, const void* in, uint8_t* out, int64_t pi
  * out[b, p, :] = frame src[b] pixel p: v / 255 * mul + add in channels 0..2, zeros up to Cpad (as gn_image_u8_to_f16, bit for bit).
  * src: DEVICE array of B device pointers to uint8 [pixels, 3] frames (4-byte aligned; pointers may repeat). */
 int32_t gn_gather_u8_to_f16(gn_ctx* ctx, const uint8_t* const* src, void* out, int32_t B, int64_t pixels, int32_t Cpad, float mul, float add);
+/* One training batch of the ACT controller out of a device-resident demo set (genima_amd/replay.py DeviceReplay; the reference's
+ * controller/utils/dataloader.py _sample), one launch.  Tables, all on the device:
+ *   frame_ptr  int64 [N_obs][V]  addresses of uint8 [pixels, 3] frames (4-byte aligned frames take dword loads, others byte loads)
+ *   qpos       f32 [N_obs][S], action f32 [N][A]: already normalised
+ *   obs_index, first_obs, last_tr  int32 [N]: a transition's own observation, the first observation and the last transition of its episode
+ *   lang_tokens int32 [N_ep][L_tok], episode int32 [N] (a transition's episode): optional, read only when tokens_out is given
+ *   idx        int32 [B]: the batch's transitions, ON THE DEVICE (repeats allowed); a value outside [0, N) is clamped into it
+ * Per sample b, n = idx[b], frame-stack slot k < fs reads observation o(k) = max(obs_index[n] - (fs - 1) + k, first_obs[n]):
+ *   images[b][v * fs + k][p][0..7]   f16 = frame (o(k), v) pixel p: byte / 255 in channels 0..2 (gn_image_u8_to_f16 with mul 1, add 0, bit
+ *                                    for bit), zeros in 3..7; 16-byte aligned
+ *   images_u8[b][v * fs + k][p][0..2]  the same bytes unconverted; optional (NULL: not written)
+ *   low_dim_state[b][k][0..S)        = qpos[o(k)]
+ *   action_out[b][j][0..A)           = action[min(n + j, last_tr[n])], j < T: the chunk repeats the episode's last action
+ *   tokens_out[b][0..L_tok)          = lang_tokens[episode[n]]; optional (NULL: not written)
+ * B <= 65535, V * fs <= 65535.  Every table index is clamped into its table.  Eager only: no gn_program_add_ counterpart. */
+typedef struct gn_replay_gather_desc {
+  const int64_t* frame_ptr;
+  const float* qpos;
+  const float* action;
+  const int32_t* obs_index;
+  const int32_t* first_obs;
+  const int32_t* last_tr;
+  const int32_t* idx;
+  void* images;
+  uint8_t* images_u8;
+  float* low_dim_state;
+  float* action_out;
+  const int32_t* lang_tokens;
+  const int32_t* episode;
+  int32_t* tokens_out;
+  int64_t pixels, N_obs;
+  int32_t B, V, fs, T, S, A, N, N_ep, L_tok;
+} gn_replay_gather_desc;
+int32_t gn_replay_gather(gn_ctx* ctx, const gn_replay_gather_desc* d);
 /* ACT image path (controller/method/genima_act.py:146-148, :188): uint8 [pixels, 3] -> f16 [pixels, Cpad]: v * m_c + a_c
  * (m_c = 1/(255 std_c), a_c = -mean_c/std_c; channels >= 3 zero) */
 int32_t gn_image_normalize_u8(gn_ctx* ctx, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float m0, float m1,
@@ -792,7 +826,7 @@ int32_t gn_program_add_memset(gn_program* p, void* ptr, int64_t bytes);
 int32_t gn_program_set_memset_bytes(gn_program* p, int64_t op, int64_t bytes); /* shrink a recorded memset to the bytes the program came to use */
 int32_t gn_memset(gn_ctx* ctx, void* ptr, int64_t bytes);
 /* sizeof() of the descriptor structs as the library was compiled (0 gn_gemm_desc, 1 gn_attn_desc, 2 gn_groupnorm_desc, 3 gn_tblock_desc,
- * 4 gn_conv3x3_gn_desc, 5 gn_stats_sink, 6 gn_norm_in, 7 gn_norm_out, 8 gn_conv3x3_patch_desc): a host binding checks its own layout against these before the first call */
+ * 4 gn_conv3x3_gn_desc, 5 gn_stats_sink, 6 gn_norm_in, 7 gn_norm_out, 8 gn_conv3x3_patch_desc, 9 gn_replay_gather_desc): a host binding checks its own layout against these before the first call */
 int64_t gn_desc_sizeof(int32_t which);
 /* first..last (exclusive) op range; last < 0 = to the end */
 int32_t gn_program_run(gn_program* p, int64_t first, int64_t last);

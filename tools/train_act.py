@@ -1,0 +1,82 @@
+"""Train the ACT controller from a demo tree: the command line over ``genima_amd.act_train_loop.ControllerTrainLoop``, with the argument
+names of the reference's step 4 (``python train_act.py ... demos=25 action_sequence=20 batch_size=8 num_train_epochs=1000``).
+
+    python tools/train_act.py --dataset_root /data/rlbench_rgb_rendered --tasks take_lid_off_saucepan --demos 25 --work_dir ./exp_local \
+        --clip_text ./clip-vit-base-patch32
+
+Reads ``<dataset_root>/<task>/variation0/episodes/<episode>/{<camera>_rgb/<ts>.png, demo.npz[, description.txt]}`` (the tree
+``tools/render_dataset.py`` writes, plus one ``demo.npz`` per episode: ``genima_amd.replay.save_demo``; an episode that has only RLBench's
+``low_dim_obs.pkl`` is converted first, which needs ``rlbench`` importable for the unpickling) and writes
+``<work_dir>/snapshots/<experiment_name>/{latest.pt, <epoch>.pt, action_stats.json, proprio_stats.json}``.  Nothing from RoboBase or RLBench is
+imported otherwise.  ``--clip_text``: a transformers ``CLIPTextModel`` directory (weights + tokenizer files) for the task-string
+conditioning; without it the text tower keeps its random initialisation, which only makes sense for a dry run."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from genima_amd import replay as P  # noqa: E402
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dataset_root", required=True)
+    ap.add_argument("--tasks", nargs="+", default=["take_lid_off_saucepan"])
+    ap.add_argument("--demos", type=int, default=25)
+    ap.add_argument("--work_dir", default="./exp_local")
+    ap.add_argument("--experiment_name", default="genima_controller")
+    ap.add_argument("--num_train_epochs", type=int, default=1000)
+    ap.add_argument("--checkpoint_every", type=int, default=10)
+    ap.add_argument("--num_checkpoints", type=int, default=3)
+    ap.add_argument("--action_sequence", type=int, default=20)
+    ap.add_argument("--batch_size", type=int, default=8)
+    ap.add_argument("--lr", type=float, default=5e-5)
+    ap.add_argument("--lr_backbone", type=float, default=1e-5)
+    ap.add_argument("--actor_grad_clip", type=float, default=None)
+    ap.add_argument("--cameras", nargs="+", default=list(P.DEFAULT_CAMERAS))
+    ap.add_argument("--image_size", type=int, default=256)
+    ap.add_argument("--clip_text", default=None, help="transformers CLIPTextModel directory (weights and tokenizer)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--log_every", type=int, default=50)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse(argv)
+    import torch
+
+    from genima_amd import configs
+    from genima_amd.act import GenimaACT
+    from genima_amd.act_train_loop import ControllerTrainLoop
+
+    episodes = P.list_episodes(a.dataset_root, a.tasks, a.demos)
+    if not episodes:
+        raise SystemExit(f"train_act: no episodes under {a.dataset_root} for tasks {a.tasks}")
+    for ep in episodes:
+        if not os.path.exists(os.path.join(ep, "demo.npz")):
+            P.save_demo(os.path.join(ep, "demo.npz"), P.demo_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl")))
+    clip_sd = tokenizer = None
+    if a.clip_text:
+        from genima_amd import weights
+        from genima_amd.tokenizer import CLIPTokenizer
+
+        _, clip_sd = weights.load_diffusers_dir(a.clip_text)
+        tokenizer = CLIPTokenizer.from_pretrained(a.clip_text)
+    cfg = dict(configs.ACT_POLICY, num_queries=a.action_sequence, num_views=len(a.cameras), image_size=a.image_size, data_augmentation=True,
+               use_lang_cond=tokenizer is not None, lr=a.lr, lr_backbone=a.lr_backbone, actor_grad_clip=a.actor_grad_clip)
+    torch.manual_seed(a.seed)
+    agent = GenimaACT(cfg, None, configs.ACT_CLIP_TEXT, clip_sd, device="cuda", seed=a.seed)
+    replay = P.DeviceReplay(episodes, a.cameras, device="cuda", action_sequence=a.action_sequence, batch_size=a.batch_size, tokenizer=tokenizer,
+                            image_size=a.image_size)
+    print(f"train_act: {len(episodes)} episodes, {replay.N} transitions, {replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
+
+    def log(metrics, it):
+        if it % a.log_every == 0:
+            print(f"iter {it}: " + " ".join(f"{k}={v:.5f}" for k, v in metrics.items()), flush=True)
+
+    ControllerTrainLoop(agent, replay, a.work_dir, a.experiment_name, a.num_train_epochs, a.checkpoint_every, a.num_checkpoints, log=log,
+                        cfg={k: v for k, v in vars(a).items()}).train()
+
+
+if __name__ == "__main__":
+    main()
