@@ -156,6 +156,14 @@ class ReplayGatherDesc(C.Structure):
                 + [("pixels", C.c_int64), ("N_obs", C.c_int64)] + [(n, C.c_int32) for n in ("B", "V", "fs", "T", "S", "A", "N", "N_ep", "L_tok")])
 
 
+class ReplayRenderDesc(C.Structure):
+    """gn_replay_render_desc: one drawn random-background batch of the ACT replay (gn_replay_render)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("cams", "spheres", "tex_index", "count", "atlas", "bank", "qpos", "action", "obs_index", "first_obs", "last_tr", "idx",
+                                           "images", "images_u8", "bg_layer", "blend_out", "low_dim_state", "action_out", "lang_tokens", "episode", "tokens_out")]
+                + [("N_obs", C.c_int64), ("alpha_blend", C.c_double)] + [(n, C.c_uint32) for n in ("seed_lo", "seed_hi", "draw")]
+                + [(n, C.c_int32) for n in ("B", "V", "fs", "T", "S", "A", "N", "N_ep", "L_tok", "n_spheres", "H", "W", "n_tex", "th", "tw", "samples", "NB")])
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("workspace", C.c_void_p),
@@ -235,6 +243,7 @@ SIGNATURES = {
     "gn_image_normalize_u8": (_I32, [_P, _P, _P, _I64, _I32, _F, _F, _F, _F, _F, _F]),
     "gn_gather_u8_to_f16": (_I32, [_P, _P, _P, _I32, _I64, _I32, _F, _F]),
     "gn_replay_gather": (_I32, [_P, C.POINTER(ReplayGatherDesc)]),
+    "gn_replay_render": (_I32, [_P, C.POINTER(ReplayRenderDesc)]),
     "gn_gather_rows": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_argmax_rows_i32": (_I32, [_P, _P, _P, _I32, _I32]),
     "gn_copy4d": (_I32, [_P, _P, _P, _P, _P, _P, _I32]),
@@ -378,7 +387,7 @@ def load() -> C.CDLL:
             raise GenimaHipError(f"{LIB_PATH} does not export {name} (stale build?)") from e
         fn.restype = res
         fn.argtypes = args
-    for which, cls in enumerate((GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc, ReplayGatherDesc)):
+    for which, cls in enumerate((GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc, ReplayGatherDesc, ReplayRenderDesc)):
         if int(lib.gn_desc_sizeof(which)) != C.sizeof(cls):  # a stale .so against newer Python (or the reverse) would read garbage descriptors
             raise GenimaHipError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(lib.gn_desc_sizeof(which))} in the library, {C.sizeof(cls)} in the "
                                  "binding (stale build? run `python -m genima_amd.build`)")

@@ -46,6 +46,8 @@ class ControllerTrainLoop:
             os.makedirs(self.ckpt_dir)
         elif os.path.isfile(snapshot_path):
             self.load_snapshot(snapshot_path)
+            if hasattr(self.replay, "draw"):  # a render-mode replay: go on with the next backgrounds, not the run's first ones again
+                self.replay.draw = self._num_iters
 
     def load_snapshot(self, path: str):
         ckpt = harness.load_controller_ckpt(self.agent, path)

@@ -456,6 +456,7 @@ int64_t gn_desc_sizeof(int32_t which) {
     case 7: return (int64_t)sizeof(gn_norm_out);
     case 8: return (int64_t)sizeof(gn_conv3x3_patch_desc);
     case 9: return (int64_t)sizeof(gn_replay_gather_desc);
+    case 10: return (int64_t)sizeof(gn_replay_render_desc);
     default: return -1;
   }
 }

@@ -7,6 +7,7 @@
 // for bit.  The blocks of grid row (x = 0, y = 0) also write their sample's low_dim_state, action chunk and token row.  Plain vector loads and stores,
 // no atomics; every table index is clamped into its table, so a wrong index reads a wrong row, never outside the tables.
 #include "image_convert.h"
+#include "replay_common.h"
 
 namespace {
 
@@ -15,39 +16,15 @@ constexpr int RG_THREADS = 256;
 typedef const __attribute__((address_space(1))) uint8_t* rg_gptr8;  // the frames are global memory: global_load, not flat_load
 typedef const __attribute__((address_space(1))) uint32_t* rg_gptr32;
 
-__device__ __forceinline__ int rg_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ void rg_store_pixel(f16* __restrict__ o, uint8_t r, uint8_t g, uint8_t b, float mul, float add) {
   const f16 z = (f16)0.0f;
   *reinterpret_cast<f16x8*>(o) = f16x8{u8_to_f16_value(r, mul, add), u8_to_f16_value(g, mul, add), u8_to_f16_value(b, mul, add), z, z, z, z, z};
 }
 
-// the observation of frame-stack slot k of transition n: the stack ends at the transition's own observation and repeats the episode's first
-__device__ __forceinline__ int rg_obs(const gn_replay_gather_desc& d, int n, int k) {
-  const int o = d.obs_index[n] - (d.fs - 1) + k, first = d.first_obs[n];
-  return rg_clamp(o < first ? first : o, 0, (int)d.N_obs - 1);
-}
-
 __global__ __launch_bounds__(RG_THREADS) void replay_gather_kernel(gn_replay_gather_desc d, float mul, float add) {
   const int b = blockIdx.z, slot = blockIdx.y;
   const int n = rg_clamp(d.idx[b], 0, d.N - 1);
-  if (blockIdx.x == 0 && slot == 0) {  // the sample's low-dimensional values
-    const int nS = d.fs * d.S, nA = d.T * d.A;
-    for (int e = threadIdx.x; e < nS; e += RG_THREADS) {
-      const int k = e / d.S, s = e - k * d.S;
-      d.low_dim_state[(long)b * nS + e] = d.qpos[(long)rg_obs(d, n, k) * d.S + s];
-    }
-    const int last = d.last_tr[n];
-    for (int e = threadIdx.x; e < nA; e += RG_THREADS) {
-      const int j = e / d.A, a = e - j * d.A;
-      const int row = rg_clamp(n + j < last ? n + j : last, 0, d.N - 1);  // the chunk repeats the episode's last action
-      d.action_out[(long)b * nA + e] = d.action[(long)row * d.A + a];
-    }
-    if (d.tokens_out) {  // the episode's task string, tokenised once at load
-      const int ep = rg_clamp(d.episode[n], 0, d.N_ep - 1);
-      for (int e = threadIdx.x; e < d.L_tok; e += RG_THREADS) d.tokens_out[(long)b * d.L_tok + e] = d.lang_tokens[(long)ep * d.L_tok + e];
-    }
-  }
+  if (blockIdx.x == 0 && slot == 0) rg_write_low_dim<RG_THREADS>(d, b, n, threadIdx.x);  // the sample's low-dimensional values
   const long p0 = ((long)blockIdx.x * RG_THREADS + threadIdx.x) * 4;
   if (p0 >= d.pixels) return;
   const int v = slot / d.fs, k = slot - v * d.fs;

@@ -1431,6 +1431,58 @@ class Engine:
         check(self.lib.gn_replay_gather(self._ctx, C.byref(d)), "gn_replay_gather")
         return img, img8, low, act, tok
 
+    def replay_render(self, cams, spheres, tex_index, count, atlas, bank, qpos, action, obs_index, first_obs, last_tr, idx, V: int, fs: int, T: int, *,
+                      samples: int = 4, seed: int = 0, draw: int = 0, alpha_blend: float = 0.7, want_u8: bool = False, want_draws: bool = False,
+                      lang_tokens=None, episode=None, out=None):
+        """``gn_replay_render``: one random-background ACT training batch DRAWN from device-resident view tables and a texture bank
+        (genima_amd/replay.py, render mode), one launch.  ``cams`` f32 [N_obs * V, 18], ``spheres`` f32 [N_obs * V, S, 16], ``tex_index``
+        int32 [N_obs * V, S], ``count`` int32 [N_obs * V] (``render.pack_views`` per observation), ``atlas`` uint8 [T, th, tw, 4], ``bank``
+        uint8 [NB, H, W, 3]; the other tables and ``idx`` as ``replay_gather`` takes them.  ``seed`` (64 bits) and ``draw`` (32 bits) pick
+        the textures and blends.  -> (images f16 [B, V * fs, H, W, 8], images_u8 or None, low_dim_state, action, tokens or None, bg_layer
+        int32 [B, V * fs] or None, blend f64 [B, V * fs] or None -- the last two with ``want_draws``); ``out``: the same seven to write
+        into.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("replay_render is an eager op: the batch indices and the draw change from call to call")
+        N_obs, S = int(qpos.shape[0]), int(qpos.shape[1])
+        N, A = int(action.shape[0]), int(action.shape[1])
+        n_sph = int(spheres.shape[1])
+        NB, H, W = int(bank.shape[0]), int(bank.shape[1]), int(bank.shape[2])
+        for t, dt, shape in ((cams, torch.float32, (N_obs * V, 18)), (spheres, torch.float32, (N_obs * V, n_sph, 16)), (tex_index, torch.int32, (N_obs * V, n_sph)),
+                             (count, torch.int32, (N_obs * V,)), (bank, torch.uint8, (NB, H, W, 3)), (qpos, torch.float32, (N_obs, S)), (action, torch.float32, (N, A)),
+                             (obs_index, torch.int32, (N,)), (first_obs, torch.int32, (N,)), (last_tr, torch.int32, (N,))):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
+        assert atlas.is_cuda and atlas.dtype == torch.uint8 and atlas.is_contiguous() and atlas.dim() == 4 and atlas.shape[3] == 4
+        if not (isinstance(idx, torch.Tensor) and idx.is_cuda):
+            host = torch.as_tensor(idx).reshape(-1).to(torch.int64)
+            if host.numel() == 0 or bool((host < 0).any()) or bool((host >= N).any()):
+                raise GenimaHipError(f"replay_render: transition indices must lie in [0, {N}), got {host.tolist()}")
+            idx = host.to(torch.int32).to(self.device, non_blocking=True)
+        assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+        B = idx.numel()
+        if out is None:
+            out = (torch.empty((B, V * fs, H, W, 8), dtype=F16, device=self.device),
+                   torch.empty((B, V * fs, H, W, 3), dtype=torch.uint8, device=self.device) if want_u8 else None,
+                   torch.empty((B, fs, S), dtype=torch.float32, device=self.device), torch.empty((B, T, A), dtype=torch.float32, device=self.device),
+                   torch.empty((B, lang_tokens.shape[1]), dtype=torch.int32, device=self.device) if lang_tokens is not None else None,
+                   torch.empty((B, V * fs), dtype=torch.int32, device=self.device) if want_draws else None,
+                   torch.empty((B, V * fs), dtype=torch.float64, device=self.device) if want_draws else None)
+        img, img8, low, act, tok, layer, blend = out
+        N_ep, L_tok = (int(lang_tokens.shape[0]), int(lang_tokens.shape[1])) if lang_tokens is not None else (0, 0)
+        for t, dt, shape in ((lang_tokens, torch.int32, (N_ep, L_tok)), (episode, torch.int32, (N,)), (tok, torch.int32, (B, L_tok)), (img, F16, (B, V * fs, H, W, 8)),
+                             (img8, torch.uint8, (B, V * fs, H, W, 3)), (low, torch.float32, (B, fs, S)), (act, torch.float32, (B, T, A)),
+                             (layer, torch.int32, (B, V * fs)), (blend, torch.float64, (B, V * fs))):
+            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape), (dt, shape)
+        seed = int(seed)
+        d = _lib.ReplayRenderDesc(cams=_ptr(cams), spheres=_ptr(spheres), tex_index=_ptr(tex_index), count=_ptr(count), atlas=_ptr(atlas), bank=_ptr(bank),
+                                  qpos=_ptr(qpos), action=_ptr(action), obs_index=_ptr(obs_index), first_obs=_ptr(first_obs), last_tr=_ptr(last_tr), idx=_ptr(idx),
+                                  images=_ptr(img), images_u8=_ptr(img8), bg_layer=_ptr(layer), blend_out=_ptr(blend), low_dim_state=_ptr(low),
+                                  action_out=_ptr(act), lang_tokens=_ptr(lang_tokens), episode=_ptr(episode), tokens_out=_ptr(tok), N_obs=N_obs,
+                                  alpha_blend=float(alpha_blend), seed_lo=seed & 0xFFFFFFFF, seed_hi=(seed >> 32) & 0xFFFFFFFF, draw=int(draw) & 0xFFFFFFFF,
+                                  B=B, V=V, fs=fs, T=T, S=S, A=A, N=N, N_ep=N_ep, L_tok=L_tok, n_spheres=n_sph, H=H, W=W, n_tex=int(atlas.shape[0]),
+                                  th=int(atlas.shape[1]), tw=int(atlas.shape[2]), samples=int(samples), NB=NB)
+        check(self.lib.gn_replay_render(self._ctx, C.byref(d)), "gn_replay_render")
+        return img, img8, low, act, tok, layer, blend
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

@@ -11,6 +11,12 @@ plain-array ``demo.npz`` with ``joint_positions`` f64 [L, J], ``gripper_open`` f
 [L, J + 1]; an optional ``description.txt`` carries the task string in its first line.  A transition t < L - 1 reads observation t, so
 the last observation's frame may be missing (``render_episode`` writes L - 1 frames).
 
+Render mode (``DeviceReplay(..., render=RenderTargets(cfg, textures))``): the controller's own training distribution is the reference's
+``rlbench_data_rnd_bg`` -- the joint-target spheres alpha-blended over a random texture, no scene (``render/render_data.py:296-311``).  Such a
+frame depends on nothing but the trajectory, a texture and a blend factor, so the batch is DRAWN by ``gn_replay_render`` from per-observation
+view tables and a texture bank on the device: an episode is then ``demo.npz`` + ``traj.npz`` (``render.save_traj``), no camera PNG is read,
+and every frame of every batch gets a fresh texture and blend (``draw_backgrounds`` states the picks).
+
 Two things here are NOT pinned to reference text, because ``_compute_action_stats`` and the sequence sampling live in RoboBase: the action
 statistics (taken here as mean / population std / max / min over axis 0 of all transitions' actions) and the end-of-episode rule of the
 action chunk (the chunk repeats the episode's last action and never crosses into the next episode).  Statistics are computed in numpy f64
@@ -20,7 +26,8 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -262,6 +269,104 @@ def list_episodes(dataset_root: str, tasks: Sequence[str], demos: int, variation
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------ render mode
+@dataclass
+class RenderTargets:
+    """What ``DeviceReplay(render=...)`` draws its frames from.  ``cfg``: a ``render.RenderConfig`` (image size, samples, sphere textures,
+    horizon window, per-camera joints); ``textures``: a directory of background images or a uint8 [NB, H, W, 3] array; ``seed``: 64 bits
+    of the background draws; ``alpha_blend``: the lower end of the blend factor (default: ``cfg.alpha_blend``)."""
+    cfg: Any
+    textures: Any
+    seed: int = 0
+    alpha_blend: Optional[float] = None
+
+    def __post_init__(self):
+        if self.alpha_blend is None:
+            self.alpha_blend = float(self.cfg.alpha_blend)
+        if not 0.0 <= float(self.alpha_blend) <= 1.0:
+            raise ValueError(f"RenderTargets: alpha_blend must lie in [0, 1], got {self.alpha_blend}")
+
+
+def load_texture_bank(textures, H: int, W: int) -> np.ndarray:
+    """-> uint8 [NB, H, W, 3].  A directory: every file in natural-sorted order (so a layer index names a file), loaded as the reference
+    does per frame (render_data.py:299-301, and ``render.render_episode``): ``Image.open(f).resize((W, H))``, then ``.convert("RGB")``.
+    An array is checked and taken as it is."""
+    if isinstance(textures, (str, os.PathLike)):
+        from PIL import Image
+
+        d = os.fspath(textures)
+        names = sorted((n for n in os.listdir(d) if os.path.isfile(os.path.join(d, n))), key=_natural_key)
+        if not names:
+            raise ValueError(f"load_texture_bank: no texture files in {d}")
+        return np.ascontiguousarray(np.stack([np.asarray(Image.open(os.path.join(d, n)).resize((W, H)).convert("RGB"), dtype=np.uint8) for n in names]))
+    bank = np.asarray(textures)
+    if bank.dtype != np.uint8 or bank.ndim != 4 or bank.shape[0] < 1 or tuple(bank.shape[1:]) != (H, W, 3):
+        raise ValueError(f"load_texture_bank: a uint8 [NB >= 1, {H}, {W}, 3] array expected, got {bank.dtype} {bank.shape}")
+    return np.ascontiguousarray(bank)
+
+
+def _mix32(x: np.ndarray) -> np.ndarray:
+    x = x.astype(np.uint32)  # a copy
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7FEB352D)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846CA68B)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def draw_backgrounds(seed: int, draw: int, B: int, V: int, fs: int, NB: int, alpha: float):
+    """The texture layer and blend factor of every frame of one ``gn_replay_render`` batch (include/genima_hip.h states the formula), in
+    numpy on the host -> ``(layer int32 [B, V * fs], blend f64 [B, V * fs])``; frame ``[b, v * fs + k]`` is slot ``(b * V + v) * fs + k``.
+    A pure function of its arguments: uint32 arithmetic that wraps, then ``blend = alpha + (1 - alpha) * (u * 2^-24)`` in f64."""
+    seed = int(seed)
+    lo, hi, dr = np.uint32(seed & 0xFFFFFFFF), np.uint32((seed >> 32) & 0xFFFFFFFF), np.uint32(int(draw) & 0xFFFFFFFF)
+    with np.errstate(over="ignore"):
+        base = _mix32(np.array([lo ^ np.uint32(0x6A09E667) ^ (dr * np.uint32(0x9E3779B9))], np.uint32))[0] ^ hi
+        slot = np.arange(B * V * fs, dtype=np.uint32)
+        s = _mix32(base + slot * np.uint32(0x85EBCA6B))
+        layer = (_mix32(s ^ np.uint32(0xC2B2AE35)).astype(np.uint64) * np.uint64(NB)) >> np.uint64(32)
+        u = _mix32(s ^ np.uint32(0x27D4EB2F)) >> np.uint32(8)
+    a = np.float64(alpha)
+    blend = a + (np.float64(1.0) - a) * (u.astype(np.float64) * np.float64(2.0 ** -24))
+    return layer.astype(np.int32).reshape(B, V * fs), blend.reshape(B, V * fs)
+
+
+def _episode_traj(ep, index: int):
+    """-> (demo, description, traj) of a render-mode episode: a directory holding ``demo.npz`` + ``traj.npz`` (camera PNGs are neither
+    needed nor read), or an in-memory ``(demo, traj[, description])`` tuple."""
+    from .render import TRAJ_KEYS, load_traj
+
+    if isinstance(ep, (str, os.PathLike)):
+        ep = os.fspath(ep)
+        p = os.path.join(ep, "traj.npz")
+        if not os.path.exists(p):
+            raise ValueError(f"DeviceReplay: render mode needs a traj.npz (render.save_traj) in every episode; episode {index} ({ep}) has none")
+        demo, desc, traj = load_demo(ep), "", load_traj(p)
+        p = os.path.join(ep, "description.txt")
+        if os.path.exists(p):
+            with open(p) as f:
+                desc = f.readline().rstrip("\n")
+    else:
+        demo, traj, desc = check_demo(ep[0]), ep[1], (ep[2] if len(ep) > 2 else "")
+        if not all(k in traj for k in TRAJ_KEYS):
+            raise ValueError(f"DeviceReplay: render mode takes (demo, traj[, description]) tuples; episode {index} lacks one of {TRAJ_KEYS}")
+    L = demo["joint_positions"].shape[0]
+    if len(traj["gripper_open"]) != L:
+        raise ValueError(f"DeviceReplay: episode {index} has {L} observations in its demo and {len(traj['gripper_open'])} steps in its trajectory")
+    return demo, desc, traj
+
+
+def view_tables(trajs, cfg, cameras: Sequence[str]) -> Dict[str, np.ndarray]:
+    """``gn_replay_render``'s per-observation view tables: for every step ``ts`` of every trajectory, ``render.pack_views(render.pack_step(
+    traj, cfg, ts, cameras))``, concatenated -- row ``obs * V + v``.  A step whose horizon window is empty (``render.window_step``: the last two of a trajectory) has
+    count 0: its frame is the texture alone."""
+    from .render import pack_step, pack_views
+
+    parts = [pack_views(pack_step(traj, cfg, ts, cameras)) for traj in trajs for ts in range(len(traj["gripper_open"]))]
+    return {k: np.ascontiguousarray(np.concatenate([p[k] for p in parts])) for k in ("cams", "spheres", "tex_index", "count")}
+
+
 class DeviceReplay:
     """Every frame of the given episodes and cameras, decoded once into device chunks of at most ``chunk_bytes``, beside persistent device
     tables: ``frame_ptr`` int64 [N_obs * V], ``qpos`` f32 [N_obs, S] and ``action`` f32 [N, A] (both normalised on the host at load, so the
@@ -274,38 +379,69 @@ class DeviceReplay:
     observations needs L or L - 1 frames per camera.  ``image_size``: resize + centre-crop PNGs to it (None: the files' own size).
     ``tokenizer``: a ``tokenizer.CLIPTokenizer`` (its ``tokenize``) or any callable ``[str] -> int [1, 77]``.  ``stats``:
     ``(action_stats, proprio_stats)`` to normalise with; by default they are computed from these episodes.  ``capacity_bytes``: refuse, before
-    anything is allocated, a set whose frames need more device memory than this."""
+    anything is allocated, a set whose frames need more device memory than this.
+
+    ``render``: a ``RenderTargets`` turns on render mode.  Episodes are then directories holding ``demo.npz`` + ``traj.npz`` or
+    ``(demo, traj[, description])`` tuples; instead of frames the device holds the view tables of every observation (``view_tables``), the
+    sphere atlas and the texture bank (``device_bytes`` counts these three), and ``sample`` draws the batch with ONE ``gn_replay_render``
+    launch.  ``H``, ``W``, ``samples`` and the atlas come from ``render.cfg``; the cameras must be among ``render.cfg.cameras``.  The
+    backgrounds of a batch are picked by ``(render.seed, draw)``; ``self.draw`` counts the batches drawn so far."""
 
     def __init__(self, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, engine=None, device="cuda", frame_stack: int = 1,
                  action_sequence: int = 20, batch_size: int = 8, tokenizer=None, image_size: Optional[int] = None, chunk_bytes: int = 256 << 20,
-                 capacity_bytes: Optional[int] = None, shuffle: str = "per_batch", generator: Optional[torch.Generator] = None, stats=None):
+                 capacity_bytes: Optional[int] = None, shuffle: str = "per_batch", generator: Optional[torch.Generator] = None, stats=None,
+                 render: Optional[RenderTargets] = None):
         from .engine import Engine
 
         self.cameras, self.V = tuple(cameras), len(cameras)
         self.fs, self.T, self.batch_size = int(frame_stack), int(action_sequence), int(batch_size)
         if not episodes or self.V == 0 or self.fs < 1 or self.T < 1:
             raise ValueError("DeviceReplay: needs episodes, cameras, frame_stack >= 1 and action_sequence >= 1")
-        eps = [_episode_frames(ep, self.cameras) for ep in episodes]
+        self.render = render
+        if render is not None:
+            cfg = render.cfg
+            missing = [c for c in self.cameras if c not in cfg.cameras]
+            if missing:
+                raise ValueError(f"DeviceReplay: cameras {missing} are not among the render config's {list(cfg.cameras)}")
+            if image_size is not None and (int(image_size) != cfg.image_height or int(image_size) != cfg.image_width):
+                raise ValueError(f"DeviceReplay: image_size = {image_size} contradicts the render config's {cfg.image_height} x {cfg.image_width} frames")
+            eps = [_episode_traj(ep, i) for i, ep in enumerate(episodes)]
+        else:
+            eps = [_episode_frames(ep, self.cameras) for ep in episodes]
         demos = [e[0] for e in eps]
         self.action_stats, self.proprio_stats = stats if stats is not None else (action_stats(demos), proprio_stats(demos))
         # ---- host tables
-        n_obs = []
-        for i, (demo, _, src) in enumerate(eps):
-            L = demo["joint_positions"].shape[0]
-            counts = {len(src[c]) for c in self.cameras}
-            if len(counts) != 1 or min(counts) < L - 1:
-                raise ValueError(f"DeviceReplay: episode {i} has {L} observations and needs {L - 1} or {L} frames per camera, found {sorted(counts)}")
-            n_obs.append(min(L, min(counts)))
-        first = _read_frame(eps[0][2][self.cameras[0]][0], image_size)
-        self.H, self.W = int(first.shape[0]), int(first.shape[1])
-        self.frame_bytes = self.H * self.W * 3
-        self.frame_stride = (self.frame_bytes + 3) // 4 * 4  # frames start on the dword grid: the kernel's three-dword loads
-        n_frames = sum(n_obs) * self.V
-        self.frames_per_chunk = max(1, int(chunk_bytes) // self.frame_stride)
-        self.device_bytes = n_frames * self.frame_stride
-        if capacity_bytes is not None and self.device_bytes > int(capacity_bytes):
-            raise ValueError(f"DeviceReplay: {n_frames} frames of {self.H}x{self.W} need {self.device_bytes} bytes on the device, over "
-                             f"capacity_bytes = {int(capacity_bytes)}")
+        if render is not None:
+            from .render import load_atlas
+
+            n_obs = [e[0]["joint_positions"].shape[0] for e in eps]  # every observation can be drawn: the last one's window is empty
+            self.H, self.W, self.samples = int(render.cfg.image_height), int(render.cfg.image_width), int(render.cfg.samples)
+            self.host_views = view_tables([e[2] for e in eps], render.cfg, self.cameras)
+            self.host_bank = load_texture_bank(render.textures, self.H, self.W)
+            self.host_atlas = load_atlas(render.cfg.texture_dir)
+            self.NB = int(self.host_bank.shape[0])
+            self.device_bytes = sum(int(t.nbytes) for t in self.host_views.values()) + int(self.host_bank.nbytes) + int(self.host_atlas.nbytes)
+            if capacity_bytes is not None and self.device_bytes > int(capacity_bytes):
+                raise ValueError(f"DeviceReplay: the view tables, {self.NB} textures of {self.H}x{self.W} and the sphere atlas need {self.device_bytes} "
+                                 f"bytes on the device, over capacity_bytes = {int(capacity_bytes)}")
+        else:
+            n_obs = []
+            for i, (demo, _, src) in enumerate(eps):
+                L = demo["joint_positions"].shape[0]
+                counts = {len(src[c]) for c in self.cameras}
+                if len(counts) != 1 or min(counts) < L - 1:
+                    raise ValueError(f"DeviceReplay: episode {i} has {L} observations and needs {L - 1} or {L} frames per camera, found {sorted(counts)}")
+                n_obs.append(min(L, min(counts)))
+            first = _read_frame(eps[0][2][self.cameras[0]][0], image_size)
+            self.H, self.W = int(first.shape[0]), int(first.shape[1])
+            self.frame_bytes = self.H * self.W * 3
+            self.frame_stride = (self.frame_bytes + 3) // 4 * 4  # frames start on the dword grid: the kernel's three-dword loads
+            n_frames = sum(n_obs) * self.V
+            self.frames_per_chunk = max(1, int(chunk_bytes) // self.frame_stride)
+            self.device_bytes = n_frames * self.frame_stride
+            if capacity_bytes is not None and self.device_bytes > int(capacity_bytes):
+                raise ValueError(f"DeviceReplay: {n_frames} frames of {self.H}x{self.W} need {self.device_bytes} bytes on the device, over "
+                                 f"capacity_bytes = {int(capacity_bytes)}")
         qpos, action, obs_index, first_obs, last_tr, episode = [], [], [], [], [], []
         o0 = t0 = 0
         for e, (demo, _, _) in enumerate(eps):
@@ -333,25 +469,31 @@ class DeviceReplay:
         # ---- device: frames into chunks, then the tables
         self.E = engine if engine is not None else Engine(device)
         dev = self.E.device
-        self.host_frames = np.empty((self.N_obs * self.V, self.H, self.W, 3), np.uint8)  # host_batch's source (and the tests')
-        i = 0
-        for e, (_, _, src) in enumerate(eps):
-            for t in range(n_obs[e]):
-                for c in self.cameras:
-                    fr = _read_frame(src[c][t], image_size)
-                    if fr.shape != (self.H, self.W, 3):
-                        raise ValueError(f"DeviceReplay: frame {t} of camera {c!r}, episode {e}, is {fr.shape}, expected {(self.H, self.W, 3)}")
-                    self.host_frames[i] = fr
-                    i += 1
-        self.chunks, addr = [], np.empty(n_frames, np.int64)
-        for c0 in range(0, n_frames, self.frames_per_chunk):
-            n = min(self.frames_per_chunk, n_frames - c0)
-            stage = np.zeros((n, self.frame_stride), np.uint8)
-            stage[:, : self.frame_bytes] = self.host_frames[c0: c0 + n].reshape(n, self.frame_bytes)
-            chunk = torch.from_numpy(stage).to(dev)
-            self.chunks.append(chunk)
-            addr[c0: c0 + n] = chunk.data_ptr() + np.arange(n, dtype=np.int64) * self.frame_stride
-        self.frame_ptr = torch.from_numpy(addr).to(dev)
+        if render is not None:
+            self.host_frames, self.chunks, self.frame_ptr = None, [], None
+            self.cams, self.spheres, self.tex_index, self.count = (torch.from_numpy(self.host_views[k]).to(dev) for k in ("cams", "spheres", "tex_index", "count"))
+            self.bank, self.atlas = torch.from_numpy(self.host_bank).to(dev), torch.from_numpy(self.host_atlas).to(dev)
+            self.draw = 0  # the batches drawn so far: the default ``draw`` of the next ``sample``
+        else:
+            self.host_frames = np.empty((self.N_obs * self.V, self.H, self.W, 3), np.uint8)  # host_batch's source (and the tests')
+            i = 0
+            for e, (_, _, src) in enumerate(eps):
+                for t in range(n_obs[e]):
+                    for c in self.cameras:
+                        fr = _read_frame(src[c][t], image_size)
+                        if fr.shape != (self.H, self.W, 3):
+                            raise ValueError(f"DeviceReplay: frame {t} of camera {c!r}, episode {e}, is {fr.shape}, expected {(self.H, self.W, 3)}")
+                        self.host_frames[i] = fr
+                        i += 1
+            self.chunks, addr = [], np.empty(n_frames, np.int64)
+            for c0 in range(0, n_frames, self.frames_per_chunk):
+                n = min(self.frames_per_chunk, n_frames - c0)
+                stage = np.zeros((n, self.frame_stride), np.uint8)
+                stage[:, : self.frame_bytes] = self.host_frames[c0: c0 + n].reshape(n, self.frame_bytes)
+                chunk = torch.from_numpy(stage).to(dev)
+                self.chunks.append(chunk)
+                addr[c0: c0 + n] = chunk.data_ptr() + np.arange(n, dtype=np.int64) * self.frame_stride
+            self.frame_ptr = torch.from_numpy(addr).to(dev)
         for k in ("qpos", "action", "obs_index", "first_obs", "last_tr", "episode", "lang_tokens"):
             setattr(self, k, torch.from_numpy(self.host[k]).to(dev).contiguous() if k in self.host else None)
         self._ones = {}
@@ -361,13 +503,29 @@ class DeviceReplay:
         return self.N
 
     # ---- the two routes to a batch
-    def sample(self, indices, want_u8: bool = False) -> Dict[str, torch.Tensor]:
+    def sample(self, indices, want_u8: bool = False, want_draws: bool = False, draw: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """``indices``: transition indices -- host integers (checked, uploaded) or a device int32 [B] tensor -> ``{"images": f16 [B, V * fs,
         H, W, 8] on the 0..1 scale, "low_dim_state": f32 [B, fs, S], "action": f32 [B, T, A], "lang_tokens": int32 [B, 1, 77] (with a
-        tokenizer), "reward": ones f32 [B]}`` (+ ``"images_u8"`` uint8 [B, V * fs, H, W, 3] with ``want_u8``), all on the device."""
-        img, img8, low, act, tok = self.E.replay_gather(self.frame_ptr, self.qpos, self.action, self.obs_index, self.first_obs, self.last_tr, indices,
-                                                        (self.H, self.W), self.V, self.fs, self.T, want_u8=want_u8, lang_tokens=self.lang_tokens,
-                                                        episode=self.episode if self.lang_tokens is not None else None)
+        tokenizer), "reward": ones f32 [B]}`` (+ ``"images_u8"`` uint8 [B, V * fs, H, W, 3] with ``want_u8``), all on the device.
+
+        Render mode: the images are drawn; ``draw`` (32 bits) picks the batch's backgrounds together with ``render.seed`` and defaults to
+        the counter ``self.draw``, which then advances by one (an explicit ``draw`` leaves the counter alone); ``want_draws`` adds
+        ``"bg_layer"`` int32 and ``"blend"`` f64 [B, V * fs], what ``draw_backgrounds`` states."""
+        layer = blend = None
+        if self.render is not None:
+            if draw is None:
+                draw, self.draw = self.draw, self.draw + 1
+            img, img8, low, act, tok, layer, blend = self.E.replay_render(
+                self.cams, self.spheres, self.tex_index, self.count, self.atlas, self.bank, self.qpos, self.action, self.obs_index, self.first_obs,
+                self.last_tr, indices, self.V, self.fs, self.T, samples=self.samples, seed=self.render.seed, draw=draw,
+                alpha_blend=self.render.alpha_blend, want_u8=want_u8, want_draws=want_draws, lang_tokens=self.lang_tokens,
+                episode=self.episode if self.lang_tokens is not None else None)
+        else:
+            if want_draws or draw is not None:
+                raise ValueError("DeviceReplay.sample: want_draws / draw belong to render mode (render=RenderTargets(...)); this replay gathers stored frames")
+            img, img8, low, act, tok = self.E.replay_gather(self.frame_ptr, self.qpos, self.action, self.obs_index, self.first_obs, self.last_tr, indices,
+                                                            (self.H, self.W), self.V, self.fs, self.T, want_u8=want_u8, lang_tokens=self.lang_tokens,
+                                                            episode=self.episode if self.lang_tokens is not None else None)
         B = img.shape[0]
         if B not in self._ones:
             self._ones[B] = torch.ones(B, dtype=torch.float32, device=self.E.device)
@@ -376,12 +534,16 @@ class DeviceReplay:
             out["lang_tokens"] = tok.view(B, 1, 77)
         if img8 is not None:
             out["images_u8"] = img8
+        if layer is not None:
+            out["bg_layer"], out["blend"] = layer, blend
         return out
 
     def host_batch(self, indices) -> Dict[str, np.ndarray]:
         """The same sample as the numpy dict a RoboBase replay hands to ``GenimaACT.update``: ``<camera>_rgb`` uint8 [B, fs, 3, H, W] in camera
         order, ``low_dim_state`` f32 [B, fs, S], ``action`` f32 [B, T, A], ``lang_tokens`` int32 [B, fs, 77] (with a tokenizer), ``reward``
-        f32 [B].  Assembled on the host, per batch: the route ``sample`` replaces."""
+        f32 [B].  Assembled on the host, per batch: the route ``sample`` replaces.  Not in render mode: there are no stored frames."""
+        if self.render is not None:
+            raise ValueError("DeviceReplay.host_batch: this replay is in render mode -- its frames are drawn on the device by sample(), none are stored")
         idx = np.asarray(torch.as_tensor(indices).cpu()).reshape(-1).astype(np.int64)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= self.N:
             raise ValueError(f"host_batch: transition indices must lie in [0, {self.N}), got {idx.tolist()}")

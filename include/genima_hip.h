@@ -755,6 +755,59 @@ typedef struct gn_render_desc {
 } gn_render_desc;
 int32_t gn_render_spheres(gn_ctx* ctx, const gn_render_desc* d);
 
+/* One random-background training batch of the ACT controller, DRAWN from trajectories instead of gathered from frames (genima_amd/replay.py
+ * DeviceReplay(render=...); the reference's rlbench_data_rnd_bg tree, render/render_data.py:296-311: the joint-target spheres alpha-blended
+ * over a random texture, no scene), one launch.  Tables, all on the device:
+ *   cams f32 [N_obs * V][18], spheres f32 [N_obs * V][n_spheres][16], tex_index int32 [N_obs * V][n_spheres], count int32 [N_obs * V]:
+ *              gn_render_spheres' per-view inputs for every observation and camera, row obs * V + v;  atlas uint8 [n_tex, th, tw, 4]
+ *   bank       uint8 [NB][H][W][3]: the background textures
+ *   qpos, action, obs_index, first_obs, last_tr, lang_tokens, episode, idx: as gn_replay_gather takes them (idx on the device, clamped)
+ * Per sample b, n = idx[b], view v < V and frame-stack slot k < fs, with slot = (b * V + v) * fs + k and o(k) gn_replay_gather's:
+ *   view o(k) * V + v is ray-cast exactly as gn_render_spheres does (samples in {1, 4}) and composited as its rnd output:
+ *   pixel' = white ? bank[layer] : trunc(pixel * blend + bank[layer] * (1 - blend))   (f64, unfused)
+ * layer and blend are a pure function of (seed, draw, slot); mix is gn_attn_dropout's, all integer arithmetic is uint32 and wraps:
+ *   base  = mix(seed_lo ^ 0x6A09E667 ^ (draw * 0x9E3779B9)) ^ seed_hi
+ *   s     = mix(base + slot * 0x85EBCA6B)
+ *   layer = (uint64(mix(s ^ 0xC2B2AE35)) * NB) >> 32
+ *   u     = mix(s ^ 0x27D4EB2F) >> 8                                   24 bits
+ *   blend = alpha_blend + (1.0 - alpha_blend) * (u * 2^-24)           f64, unfused: in [alpha_blend, 1) up to the last rounding
+ * Outputs:
+ *   images[b][v * fs + k][H][W][0..7]  f16 = pixel' / 255 in channels 0..2 (gn_image_u8_to_f16 with mul 1, add 0, bit for bit), zeros in
+ *                                      3..7; 16-byte aligned
+ *   images_u8[b][v * fs + k][H][W][0..2]  pixel'; bg_layer int32 [B][V * fs] = layer; blend_out f64 [B][V * fs] = blend: optional (NULL: not
+ *                                      written)
+ *   low_dim_state, action_out, tokens_out: gn_replay_gather's, bit for bit
+ * B <= 65535, V * fs <= 65535, n_spheres <= 8, NB >= 1, 0 <= alpha_blend <= 1.  Every table index is clamped into its table.  Eager only. */
+typedef struct gn_replay_render_desc {
+  const float* cams;
+  const float* spheres;
+  const int32_t* tex_index;
+  const int32_t* count;
+  const uint8_t* atlas;
+  const uint8_t* bank;
+  const float* qpos;
+  const float* action;
+  const int32_t* obs_index;
+  const int32_t* first_obs;
+  const int32_t* last_tr;
+  const int32_t* idx;
+  void* images;
+  uint8_t* images_u8;
+  int32_t* bg_layer;
+  double* blend_out;
+  float* low_dim_state;
+  float* action_out;
+  const int32_t* lang_tokens;
+  const int32_t* episode;
+  int32_t* tokens_out;
+  int64_t N_obs;
+  double alpha_blend;
+  uint32_t seed_lo, seed_hi, draw;
+  int32_t B, V, fs, T, S, A, N, N_ep, L_tok;              /* gn_replay_gather_desc's */
+  int32_t n_spheres, H, W, n_tex, th, tw, samples, NB;   /* gn_render_desc's S, H, W, T, th, tw, samples; the bank's layers */
+} gn_replay_render_desc;
+int32_t gn_replay_render(gn_ctx* ctx, const gn_replay_render_desc* d);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */
@@ -826,7 +879,7 @@ int32_t gn_program_add_memset(gn_program* p, void* ptr, int64_t bytes);
 int32_t gn_program_set_memset_bytes(gn_program* p, int64_t op, int64_t bytes); /* shrink a recorded memset to the bytes the program came to use */
 int32_t gn_memset(gn_ctx* ctx, void* ptr, int64_t bytes);
 /* sizeof() of the descriptor structs as the library was compiled (0 gn_gemm_desc, 1 gn_attn_desc, 2 gn_groupnorm_desc, 3 gn_tblock_desc,
- * 4 gn_conv3x3_gn_desc, 5 gn_stats_sink, 6 gn_norm_in, 7 gn_norm_out, 8 gn_conv3x3_patch_desc, 9 gn_replay_gather_desc): a host binding checks its own layout against these before the first call */
+ * 4 gn_conv3x3_gn_desc, 5 gn_stats_sink, 6 gn_norm_in, 7 gn_norm_out, 8 gn_conv3x3_patch_desc, 9 gn_replay_gather_desc, 10 gn_replay_render_desc): a host binding checks its own layout against these before the first call */
 int64_t gn_desc_sizeof(int32_t which);
 /* first..last (exclusive) op range; last < 0 = to the end */
 int32_t gn_program_run(gn_program* p, int64_t first, int64_t last);

@@ -1,12 +1,22 @@
 """Train the ACT controller from a demo tree: the command line over ``genima_amd.act_train_loop.ControllerTrainLoop``, with the argument
 names of the reference's step 4 (``python train_act.py ... demos=25 action_sequence=20 batch_size=8 num_train_epochs=1000``).
 
-    python tools/train_act.py --dataset_root /data/rlbench_rgb_rendered --tasks take_lid_off_saucepan --demos 25 --work_dir ./exp_local \
+    python tools/train_act.py --dataset_root /data/rlbench_data_rnd_bg --tasks take_lid_off_saucepan --demos 25 --work_dir ./exp_local \
         --clip_text ./clip-vit-base-patch32
 
-Reads ``<dataset_root>/<task>/variation0/episodes/<episode>/{<camera>_rgb/<ts>.png, demo.npz[, description.txt]}`` (the tree
+Reads ``<dataset_root>/<task>/variation0/episodes/<episode>/{<camera>_rgb/<ts>.png, demo.npz[, description.txt]}`` (a tree
 ``tools/render_dataset.py`` writes, plus one ``demo.npz`` per episode: ``genima_amd.replay.save_demo``; an episode that has only RLBench's
-``low_dim_obs.pkl`` is converted first, which needs ``rlbench`` importable for the unpickling) and writes
+``low_dim_obs.pkl`` is converted first, which needs ``rlbench`` importable for the unpickling).  The controller learns from the
+RANDOM-BACKGROUND tree (the reference's ``rlbench_data_rnd_bg``: spheres blended over a random texture, no scene), not from
+``rgb_rendered``, which is the diffusion agent's.
+
+With ``--rnd_bg_textures DIR`` no PNG tree is needed at all: every batch is drawn on the device from ``<episode>/traj.npz`` (which
+``tools/render_dataset.py`` writes beside the frames; an episode with only ``low_dim_obs.pkl`` is converted too) over a texture of ``DIR``, a
+fresh texture and blend factor for every frame of every batch:
+
+    python tools/train_act.py --dataset_root /data/rlbench_data --rnd_bg_textures ./textures --sphere_textures ./sphere_textures ...
+
+Writes
 ``<work_dir>/snapshots/<experiment_name>/{latest.pt, <epoch>.pt, action_stats.json, proprio_stats.json}``.  Nothing from RoboBase or RLBench is
 imported otherwise.  ``--clip_text``: a transformers ``CLIPTextModel`` directory (weights + tokenizer files) for the task-string
 conditioning; without it the text tower keeps its random initialisation, which only makes sense for a dry run."""
@@ -38,6 +48,11 @@ def parse(argv=None):
     ap.add_argument("--clip_text", default=None, help="transformers CLIPTextModel directory (weights and tokenizer)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log_every", type=int, default=50)
+    ap.add_argument("--rnd_bg_textures", default=None, help="directory of background textures: draw the random-background frames on the device "
+                                                              "from <episode>/traj.npz instead of reading a PNG tree")
+    ap.add_argument("--sphere_textures", default="./sphere_textures/", help="directory of the five sphere_<colour>_stripe_texture.png files")
+    ap.add_argument("--alpha_blend", type=float, default=0.7, help="lower end of the sphere / texture blend factor (render.yaml: 0.7)")
+    ap.add_argument("--render_seed", type=int, default=0, help="seed of the background draws")
     return ap.parse_args(argv)
 
 
@@ -55,6 +70,16 @@ def main(argv=None):
     for ep in episodes:
         if not os.path.exists(os.path.join(ep, "demo.npz")):
             P.save_demo(os.path.join(ep, "demo.npz"), P.demo_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl")))
+    render = None
+    if a.rnd_bg_textures:
+        from genima_amd import render as R
+
+        rcfg = R.RenderConfig(image_width=a.image_size, image_height=a.image_size, alpha_blend=a.alpha_blend,
+                              texture_dir=a.sphere_textures)
+        for ep in episodes:
+            if not os.path.exists(os.path.join(ep, "traj.npz")):
+                R.save_traj(os.path.join(ep, "traj.npz"), R.traj_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl"), rcfg.cameras))
+        render = P.RenderTargets(rcfg, a.rnd_bg_textures, seed=a.render_seed, alpha_blend=a.alpha_blend)
     clip_sd = tokenizer = None
     if a.clip_text:
         from genima_amd import weights
@@ -67,8 +92,9 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     agent = GenimaACT(cfg, None, configs.ACT_CLIP_TEXT, clip_sd, device="cuda", seed=a.seed)
     replay = P.DeviceReplay(episodes, a.cameras, device="cuda", action_sequence=a.action_sequence, batch_size=a.batch_size, tokenizer=tokenizer,
-                            image_size=a.image_size)
-    print(f"train_act: {len(episodes)} episodes, {replay.N} transitions, {replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
+                            image_size=a.image_size, render=render)
+    what = "view tables, textures and sphere atlas" if render is not None else "frames"
+    print(f"train_act: {len(episodes)} episodes, {replay.N} transitions, {replay.device_bytes / 1e6:.0f} MB of {what} on the device", flush=True)
 
     def log(metrics, it):
         if it % a.log_every == 0:
