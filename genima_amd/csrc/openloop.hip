@@ -1,0 +1,167 @@
+// Scores of the open-loop evaluation (genima_amd/openloop.py OpenLoopEval): a generated image against the rendered ground truth under the
+// renderer's `occupied` mask, and a predicted action chunk against the demo's.  include/genima_hip.h states both rules.
+//
+// Image kernel.  Grid: x = blocks of 4-pixel threads over one view (a thread owns pixels x0 .. x0 + 3 of one image row), y = view, z = sample
+// (only the n_valid scored ones are launched).  A thread whose three addresses sit on the dword grid and whose four pixels lie inside the row
+// loads 12 + 12 + 4 bytes as 3 + 3 + 1 dwords; a row tail (W % 4) and a row that starts off the grid (W * 3 % 4 != 0) take byte loads.  Every
+// sum is an integer: a thread's fit 32 bits (<= 4 * 3 * 255^2), a block's too (x 256), so the block folds them with DPP adds and one LDS
+// hand-off between its four waves, and five 64-bit vector atomics per block add them to the view's row, which the entry point zeroed on the
+// same stream.  Integer addition commutes, so the bits do not depend on the order the blocks arrive in.  No thread leaves before the fold.
+//
+// Action kernel.  One thread per (sample, chunk position): the A - 1 joint terms in index order in f32 (this file is compiled without fma
+// contraction, so a term is one subtraction, one multiplication and one addition, each rounded), then the gripper flag.
+#include "common.h"
+
+namespace {
+
+constexpr int OL_THREADS = 256;
+
+typedef const __attribute__((address_space(1))) uint8_t* ol_gptr8;  // global_load, not flat_load
+typedef const __attribute__((address_space(1))) uint32_t* ol_gptr32;
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t ol_dpp(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
+}
+// common.h's wave_sum on unsigned integers: every lane gets the wave's total; all 64 lanes must be active
+__device__ __forceinline__ uint32_t ol_wave_sum(uint32_t v) {
+  v += ol_dpp<0xB1>(v);
+  v += ol_dpp<0x4E>(v);
+  v += ol_dpp<0x141>(v);
+  v += ol_dpp<0x140>(v);
+  const int b = (int)v;
+  return ((uint32_t)__builtin_amdgcn_readlane(b, 0) + (uint32_t)__builtin_amdgcn_readlane(b, 16)) +
+         ((uint32_t)__builtin_amdgcn_readlane(b, 32) + (uint32_t)__builtin_amdgcn_readlane(b, 48));
+}
+
+struct ol_acc {
+  uint32_t v[5];  // se_in, n_in, se_out, n_out, wrap_sq
+};
+
+__device__ __forceinline__ void ol_pixel(ol_acc& a, const uint8_t* g, const uint8_t* t, uint8_t occ) {
+  uint32_t se = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int d = (int)g[c] - (int)t[c];
+    se += (uint32_t)(d * d);
+    const uint32_t w = (uint32_t)d & 255u;
+    a.v[4] += (w * w) & 255u;
+  }
+  if (occ) {
+    a.v[0] += se;
+    a.v[1] += 1;
+  } else {
+    a.v[2] += se;
+    a.v[3] += 1;
+  }
+}
+
+__global__ __launch_bounds__(OL_THREADS) void openloop_image_kernel(const uint8_t* __restrict__ gen, const uint8_t* __restrict__ gt,
+                                                                    const uint8_t* __restrict__ occupied, unsigned long long* __restrict__ out, int V,
+                                                                    int H, int W, int tiled, int row0) {
+  __shared__ uint32_t part[OL_THREADS / 64][5];
+  const int b = blockIdx.z, v = blockIdx.y;
+  const int G = (W + 3) >> 2;  // 4-pixel groups per image row
+  const long t = (long)blockIdx.x * OL_THREADS + threadIdx.x;
+  const int y = (int)(t / G), x0 = (int)(t - (long)y * G) * 4;
+  ol_acc a = {{0, 0, 0, 0, 0}};
+  if (y < H) {
+    const long view = (long)b * V + v;
+    const long po = (view * H + y) * W + x0;  // pixel offset in gt / occupied
+    const long pg = tiled ? (((long)b * 2 * H + (long)(v >> 1) * H + y) * (2L * W) + (long)(v & 1) * W + x0) : po;
+    const ol_gptr8 g8 = (ol_gptr8)(gen + pg * 3), t8 = (ol_gptr8)(gt + po * 3), o8 = (ol_gptr8)(occupied + po);
+    uint8_t gb[12], tb[12], ob[4];
+    int cnt = W - x0 < 4 ? W - x0 : 4;
+    if (cnt == 4 && (((uintptr_t)g8 | (uintptr_t)t8 | (uintptr_t)o8) & 3) == 0) {
+      const ol_gptr32 gw = (ol_gptr32)g8, tw = (ol_gptr32)t8;
+      const uint32_t gq[3] = {gw[0], gw[1], gw[2]}, tq[3] = {tw[0], tw[1], tw[2]}, oq = *(ol_gptr32)o8;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) {
+        gb[i] = (uint8_t)(gq[i >> 2] >> ((i & 3) * 8));
+        tb[i] = (uint8_t)(tq[i >> 2] >> ((i & 3) * 8));
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ob[j] = (uint8_t)(oq >> (j * 8));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ol_pixel(a, gb + j * 3, tb + j * 3, ob[j]);
+    } else {
+      for (int j = 0; j < cnt; ++j) {
+        const uint8_t gp[3] = {g8[j * 3], g8[j * 3 + 1], g8[j * 3 + 2]}, tp[3] = {t8[j * 3], t8[j * 3 + 1], t8[j * 3 + 2]};
+        ol_pixel(a, gp, tp, o8[j]);
+      }
+    }
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const uint32_t s = ol_wave_sum(a.v[i]);
+    if ((threadIdx.x & 63) == 0) part[wave][i] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    uint32_t s = 0;
+#pragma unroll
+    for (int w = 0; w < OL_THREADS / 64; ++w) s += part[w][threadIdx.x];
+    if (s) atomicAdd(out + ((long)(row0 + b) * V + v) * 5 + threadIdx.x, (unsigned long long)s);
+  }
+}
+
+__global__ __launch_bounds__(OL_THREADS) void openloop_action_kernel(const f16* __restrict__ a_hat, long ld_hat, long bs_hat, const float* __restrict__ actions,
+                                                                     const float* __restrict__ joint_scale, float* __restrict__ out, int T, int A, int row0,
+                                                                     int n) {
+  const int i = blockIdx.x * OL_THREADS + threadIdx.x;  // (sample, chunk position)
+  if (i >= n) return;
+  const int b = i / T, t = i - b * T;
+  const f16* h = a_hat + (long)b * bs_hat + (long)t * ld_hat;
+  const float* a = actions + (long)i * A;
+  float sum = 0.0f;
+  for (int j = 0; j < A - 1; ++j) {
+    const float d = fabsf((float)h[j] - a[j]);
+    sum += joint_scale ? joint_scale[j] * d : d;
+  }
+  float* o = out + ((long)(row0 + b) * T + t) * 2;
+  o[0] = sum;
+  o[1] = (((float)h[A - 1] > 0.0f) == (a[A - 1] > 0.5f)) ? 1.0f : 0.0f;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t gn_openloop_image_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_t* gt, const uint8_t* occupied, uint64_t* img_out, int32_t B, int32_t V,
+                                  int32_t H, int32_t W, int32_t tiled, int32_t row0, int32_t n_valid, int32_t rows) {
+  GN_REQUIRE(ctx && gen && gt && occupied && img_out, "gn_openloop_image_metrics: null argument");
+  GN_REQUIRE(B > 0 && B <= 65535 && V > 0 && V <= 65535 && H > 0 && W > 0 && (int64_t)H * W * 3 <= INT32_MAX,
+             "gn_openloop_image_metrics: B (%d), V (%d), H (%d), W (%d) out of range", B, V, H, W);
+  GN_REQUIRE(!tiled || V == 4, "gn_openloop_image_metrics: the tiled layout holds 4 views, got V = %d", V);
+  GN_REQUIRE(n_valid >= 0 && n_valid <= B && row0 >= 0 && (int64_t)row0 + n_valid <= rows,
+             "gn_openloop_image_metrics: n_valid (%d) must lie in [0, B = %d] and rows row0 (%d) .. row0 + n_valid inside the table's %d", n_valid, B, row0, rows);
+  GN_REQUIRE(((uintptr_t)img_out & 7) == 0, "gn_openloop_image_metrics: img_out must be 8-byte aligned");
+  if (n_valid == 0) return GN_OK;
+  GN_HIP(hipMemsetAsync(img_out + (int64_t)row0 * V * 5, 0, (size_t)n_valid * V * 5 * sizeof(uint64_t), ctx->stream));
+  const int64_t threads = (int64_t)H * ((W + 3) / 4);
+  hipLaunchKernelGGL(openloop_image_kernel, dim3((unsigned)cdiv64(threads, OL_THREADS), (unsigned)V, (unsigned)n_valid), dim3(OL_THREADS), 0, ctx->stream, gen,
+                     gt, occupied, (unsigned long long*)img_out, V, H, W, tiled ? 1 : 0, row0);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int32_t gn_openloop_action_metrics(gn_ctx* ctx, const void* a_hat, int64_t ld_hat, int64_t bs_hat, const float* actions, const float* joint_scale,
+                                   float* act_out, int32_t B, int32_t T, int32_t A, int32_t row0, int32_t n_valid, int32_t rows) {
+  GN_REQUIRE(ctx && a_hat && actions && act_out, "gn_openloop_action_metrics: null argument");
+  GN_REQUIRE(B > 0 && T > 0 && A >= 2 && (int64_t)B * T <= (1 << 24), "gn_openloop_action_metrics: B (%d), T (%d), A (%d) out of range", B, T, A);
+  GN_REQUIRE(ld_hat >= A && bs_hat >= (int64_t)(T - 1) * ld_hat + A, "gn_openloop_action_metrics: a_hat pitch %ld / sample stride %ld too small for T = %d, A = %d",
+             (long)ld_hat, (long)bs_hat, T, A);
+  GN_REQUIRE(n_valid >= 0 && n_valid <= B && row0 >= 0 && (int64_t)row0 + n_valid <= rows,
+             "gn_openloop_action_metrics: n_valid (%d) must lie in [0, B = %d] and rows row0 (%d) .. row0 + n_valid inside the table's %d", n_valid, B, row0, rows);
+  GN_REQUIRE((((uintptr_t)a_hat) & 1) == 0 && (((uintptr_t)actions | (uintptr_t)joint_scale | (uintptr_t)act_out) & 3) == 0,
+             "gn_openloop_action_metrics: misaligned argument");
+  if (n_valid == 0) return GN_OK;
+  const int n = n_valid * T;
+  hipLaunchKernelGGL(openloop_action_kernel, dim3((unsigned)cdiv64(n, OL_THREADS)), dim3(OL_THREADS), 0, ctx->stream, (const f16*)a_hat, (long)ld_hat,
+                     (long)bs_hat, actions, joint_scale, act_out, T, A, row0, n);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+}  // extern "C"

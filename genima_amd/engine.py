@@ -1483,6 +1483,42 @@ class Engine:
         check(self.lib.gn_replay_render(self._ctx, C.byref(d)), "gn_replay_render")
         return img, img8, low, act, tok, layer, blend
 
+    def openloop_image_metrics(self, gen, gt, occupied, out, *, row0: int = 0, n_valid: Optional[int] = None):
+        """``gn_openloop_image_metrics``: ``gen`` uint8 -- the pipeline's tiled [B, 2H, 2W, 3] output (V = 4) or per-view [B, V, H, W, 3] --
+        against ``gt`` uint8 [B * V, H, W, 3] under ``occupied`` uint8 [B * V, H, W] (``render_spheres``' ``full`` / ``occupied``) -> rows
+        ``row0 .. row0 + n_valid - 1`` of ``out`` int64 [rows, V, 5] = (se_in, n_in, se_out, n_out, wrap_sq), zeroed and summed by the
+        call; samples ``b >= n_valid`` (default B) write nothing.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("openloop_image_metrics is an eager op: the result rows change from batch to batch")
+        H, W = int(gt.shape[1]), int(gt.shape[2])
+        tiled = gen.dim() == 4
+        B = int(gen.shape[0])
+        V = 4 if tiled else int(gen.shape[1])
+        rows = int(out.shape[0])
+        for t, dt, shape in ((gen, torch.uint8, (B, 2 * H, 2 * W, 3) if tiled else (B, V, H, W, 3)), (gt, torch.uint8, (B * V, H, W, 3)),
+                             (occupied, torch.uint8, (B * V, H, W)), (out, torch.int64, (rows, V, 5))):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
+        check(self.lib.gn_openloop_image_metrics(self._ctx, _ptr(gen), _ptr(gt), _ptr(occupied), _ptr(out), B, V, H, W, int(tiled), int(row0),
+                                                 B if n_valid is None else int(n_valid), rows), "gn_openloop_image_metrics")
+        return out
+
+    def openloop_action_metrics(self, a_hat, actions, out, *, joint_scale=None, row0: int = 0, n_valid: Optional[int] = None):
+        """``gn_openloop_action_metrics``: ``a_hat`` f16 [B, T, >= A] (any row pitch and sample stride: ``act_tiled``'s view of the padded
+        chunk is taken as it is) against ``actions`` f32 [B, T, A] -> rows ``row0 .. row0 + n_valid - 1`` of ``out`` f32 [rows, T, 2] =
+        (sum_j joint_scale[j] |a_hat[j] - actions[j]| over the A - 1 joints, gripper flag).  ``joint_scale``: f32 [A - 1] or None (= 1).
+        Eager engines only."""
+        if self.record:
+            raise RuntimeError("openloop_action_metrics is an eager op: the result rows change from batch to batch")
+        B, T, A = (int(s) for s in actions.shape)
+        rows = int(out.shape[0])
+        assert a_hat.is_cuda and a_hat.dtype == F16 and a_hat.dim() == 3 and a_hat.shape[0] == B and a_hat.shape[1] >= T and a_hat.shape[2] >= A
+        assert a_hat.stride(2) == 1 or a_hat.shape[2] == 1
+        for t, shape in ((actions, (B, T, A)), (joint_scale, (A - 1,)), (out, (rows, T, 2))):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape), shape
+        check(self.lib.gn_openloop_action_metrics(self._ctx, _ptr(a_hat), a_hat.stride(1), a_hat.stride(0), _ptr(actions), _ptr(joint_scale), _ptr(out),
+                                                  B, T, A, int(row0), B if n_valid is None else int(n_valid), rows), "gn_openloop_action_metrics")
+        return out
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

@@ -1,0 +1,301 @@
+"""Open-loop evaluation: score a diffusion checkpoint and a controller snapshot on held-out demos without a simulator.
+
+The reference answers "is this checkpoint good" with RLBench / CoppeliaSim success rates (controller/eval_genima.py), which are out of scope
+here.  What a demo tree does give is, for every transition, the observation, the ground-truth joint target
+(``gn_render_spheres`` over the observation's frames: what ``render.render_episode`` writes as ``rgb_rendered``) and the demo's action chunk.
+``OpenLoopEval`` runs the body of the eval loop on every transition -- diffusion, then the controller, the device route of
+``harness.control_step`` -- and scores
+
+* the generated target against the rendered one, per camera, inside and outside the renderer's ``occupied`` mask, plus the reference's own
+  wrapped-uint8 ``mse`` (``validation.normalized_error``) -- ``gn_openloop_image_metrics``;
+* the predicted action chunk against the demo's, joint L1 and gripper agreement per chunk position -- ``gn_openloop_action_metrics``;
+* a second controller pass on the GROUND-TRUTH target, the "oracle" row: what the controller does when the diffusion model is perfect, so the
+  difference between the two rows is the diffusion model's share of the error.
+
+Frames, scores and the per-transition tables stay on the device; ``run()`` ends with one device-to-host copy of the tables.
+
+What this is NOT: a success rate.  Every chunk is predicted from a demo state, so errors never compound and nothing is executed.
+"""
+from __future__ import annotations
+
+import json
+import os
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import harness
+from .replay import DEFAULT_CAMERAS, DeviceReplay
+
+IMAGE_COLUMNS = ("se_in", "n_in", "se_out", "n_out", "wrap_sq")  # gn_openloop_image_metrics' five values per (transition, camera)
+
+
+def _mean(x) -> Optional[float]:
+    x = np.asarray(x, np.float64)
+    x = x[~np.isnan(x)]
+    return float(x.mean()) if x.size else None
+
+
+class OpenLoopResult:
+    """The per-transition tables of one evaluation, on the host.  ``image`` int64 [N, V, 5] (``IMAGE_COLUMNS``; None for a controller-only
+    run); ``actions``: ``{"generated" | "oracle": {"norm" | "rad": f32 [N, T, 2]}}`` -- ``[.., 0]`` the joint L1 SUM over the ``joints`` arm
+    joints, normalised or in radians, ``[.., 1]`` the gripper flag; ``episode`` / ``step`` / ``task`` int32 [N] (``task`` indexes ``tasks``)."""
+
+    def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int):
+        self.image, self.actions = image, actions
+        self.episode, self.step, self.task = np.asarray(episode, np.int32), np.asarray(step, np.int32), np.asarray(task, np.int32)
+        self.tasks, self.cameras, self.joints, self.H, self.W = list(tasks), list(cameras), int(joints), int(H), int(W)
+
+    def __len__(self):
+        return len(self.episode)
+
+    def sphere_rmse(self) -> np.ndarray:
+        """f64 [N, V]: ``sqrt(se_in / (3 n_in))``, NaN where ``n_in`` is 0 (no sphere drawn: the last two steps of a trajectory)."""
+        se, n = self.image[..., 0].astype(np.float64), self.image[..., 1].astype(np.float64)
+        return np.sqrt(np.divide(se, 3.0 * n, out=np.full(se.shape, np.nan), where=n > 0))
+
+    def background_rmse(self) -> np.ndarray:
+        se, n = self.image[..., 2].astype(np.float64), self.image[..., 3].astype(np.float64)
+        return np.sqrt(np.divide(se, 3.0 * n, out=np.full(se.shape, np.nan), where=n > 0))
+
+    def wrapped_mse(self) -> np.ndarray:
+        """f64 [N]: the reference's validation ``mse`` (numpy's wrapping uint8 arithmetic) of the whole tiled image."""
+        return self.image[..., 4].astype(np.float64).sum(axis=1) / float(len(self.cameras) * self.H * self.W * 3)
+
+    def _summary(self, rows: np.ndarray) -> Dict:
+        out: Dict = {"n": int(rows.sum())}
+        for name, tabs in self.actions.items():
+            norm, rad = tabs["norm"][rows].astype(np.float64), tabs["rad"][rows].astype(np.float64)
+            out[name] = {"joint_l1_norm": _mean(norm[..., 0] / self.joints), "joint_l1_rad": _mean(rad[..., 0] / self.joints),
+                         "gripper_acc": _mean(norm[..., 1]),
+                         "per_t": {"joint_l1_norm": (norm[..., 0] / self.joints).mean(axis=0).tolist() if len(norm) else [],
+                                   "joint_l1_rad": (rad[..., 0] / self.joints).mean(axis=0).tolist() if len(rad) else [],
+                                   "gripper_acc": norm[..., 1].mean(axis=0).tolist() if len(norm) else []}}
+        if self.image is not None:
+            sph, bg = self.sphere_rmse()[rows], self.background_rmse()[rows]
+            out["image"] = {"sphere_rmse": {c: _mean(sph[:, v]) for v, c in enumerate(self.cameras)},  # None: no transition drew a sphere there
+                            "sphere_missing": {c: int(np.isnan(sph[:, v]).sum()) for v, c in enumerate(self.cameras)},
+                            "background_rmse": {c: _mean(bg[:, v]) for v, c in enumerate(self.cameras)},
+                            "wrapped_mse": _mean(self.wrapped_mse()[rows])}
+        return out
+
+    def summary(self) -> Dict:
+        """Means over all transitions, in numpy f64: per row (``generated``, ``oracle``) the joint L1 per joint -- normalised and in radians --
+        and the gripper accuracy, overall and per chunk position; per camera the sphere-region RMSE over the transitions that drew a sphere
+        there (None where none did; ``sphere_missing`` counts the others), the background RMSE and the wrapped ``mse``; ``per_task`` the same
+        for each task when there is more than one."""
+        out = self._summary(np.ones(len(self), bool))
+        out["cameras"], out["tasks"] = self.cameras, self.tasks
+        if len(self.tasks) > 1:
+            out["per_task"] = {t: self._summary(self.task == i) for i, t in enumerate(self.tasks)}
+        return out
+
+    def to_json(self, path: str) -> Dict:
+        s = self.summary()
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(s, f, indent=1)
+        return s
+
+
+def _task_of(ep, description: str) -> str:
+    """``<root>/<task>/variation<k>/episodes/<episode>`` -> ``<task>``; anything else is named by its description."""
+    if isinstance(ep, (str, os.PathLike)):
+        parts = os.path.normpath(os.fspath(ep)).split(os.sep)
+        if len(parts) >= 4 and parts[-2] == "episodes" and parts[-3].startswith("variation"):
+            return parts[-4]
+    return description
+
+
+class OpenLoopEval:
+    """``OpenLoopEval(diffusion_agent, controller, episodes, ...).run() -> OpenLoopResult``.
+
+    ``diffusion_agent``: any agent of ``agent.py`` (its ``pipe`` is called as ``SDControlNetAgent.infer`` calls it, with ``output_type="pt"``),
+    or None: the controller alone on the ground-truth targets (``controller_validator``).  ``controller``: a ``GenimaACT`` with no execution
+    mode set (whole chunks are compared) and ``frame_stack`` 1.  ``episodes``: directories holding ``demo.npz``, ``traj.npz``, the camera PNGs
+    and optionally ``description.txt``, or ``(demo, frames, traj[, description])`` tuples.  ``render_cfg``: the ``render.RenderConfig`` the
+    targets are drawn with (the one the diffusion model's training targets were rendered with).  ``stats``: the TRAINING run's ``(action_stats,
+    proprio_stats)`` (``replay.load_stats`` of the snapshot directory) -- a held-out set must not be normalised with its own statistics.
+    ``tokenizer``: the controller's task-token source, as ``DeviceReplay`` takes it.
+
+    Per batch, on the device: ``DeviceReplay.sample`` (the frames, proprioception, normalised action chunk, task tokens) -> ``gn_render_spheres``
+    over the frames (``full``, ``occupied``) -> the four views on the 2x2 canvas -> the pipeline (``harness.make_prompt`` ids, one generator
+    seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image and action scores -> the controller again on ``full`` -> its action
+    scores.  The transitions are walked in order; the last batch is padded by repeating its last index and scores only its first rows, so one
+    recorded program per network serves the whole run."""
+
+    def __init__(self, diffusion_agent, controller, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None,
+                 batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None):
+        from .render import load_atlas, load_traj
+
+        if controller.execution is not None:
+            raise ValueError(f"OpenLoopEval: the controller has an execution mode set ({controller.execution}); open-loop scoring compares whole "
+                             "chunks -- call set_execution() with nothing set first")
+        if int(controller.config.get("frame_stack", 1)) > 1:
+            raise NotImplementedError("OpenLoopEval: frame-stacked controllers (frame_stack > 1) are not scored")
+        if stats is None:
+            raise ValueError("OpenLoopEval: stats = (action_stats, proprio_stats) of the TRAINING run is required (replay.load_stats)")
+        self.agent, self.controller, self.cameras, self.V = diffusion_agent, controller, tuple(cameras), len(cameras)
+        if diffusion_agent is not None and self.V != 4:
+            raise ValueError(f"OpenLoopEval: the 2x2 canvas takes exactly four cameras, got {self.V}")
+        self.cfg, self.batch_size = render_cfg, int(batch_size)
+        self.num_inference_steps, self.guidance_scale, self.seed = int(num_inference_steps), float(guidance_scale), int(seed)
+        H, W = int(render_cfg.image_height), int(render_cfg.image_width)
+        eps, trajs = [], []
+        for ep in episodes:
+            if isinstance(ep, (str, os.PathLike)):
+                eps.append(os.fspath(ep))
+                trajs.append(load_traj(os.path.join(os.fspath(ep), "traj.npz")))
+            else:
+                eps.append((ep[0], ep[1]) + tuple(ep[3:4]))
+                trajs.append(ep[2])
+        self.replay = DeviceReplay(eps, self.cameras, engine=engine, device=controller.device, frame_stack=1,
+                                   action_sequence=int(controller.config["num_queries"]), batch_size=self.batch_size, tokenizer=tokenizer,
+                                   image_size=H if H == W and isinstance(eps[0], str) else None, stats=stats)
+        rp = self.replay
+        if (rp.H, rp.W) != (H, W):
+            raise ValueError(f"OpenLoopEval: the frames are {rp.H} x {rp.W}, the render config draws {H} x {W}")
+        if rp.A != int(controller.config["action_dim"]):
+            raise ValueError(f"OpenLoopEval: the demos' actions have {rp.A} elements, the controller's {controller.config['action_dim']}")
+        self.E, self.N, self.H, self.W, self.T, self.A = rp.E, rp.N, H, W, rp.T, rp.A
+        dev = self.E.device
+        # ---- per-transition view tables: transition n of episode e, step t, reads observation t of trajectory e
+        from .replay import view_tables
+
+        vt = view_tables(trajs, render_cfg, self.cameras)  # row obs * V + v over EVERY step of every trajectory
+        starts = np.concatenate([[0], np.cumsum([len(t["gripper_open"]) for t in trajs])])
+        ep_of = rp.host["episode"]
+        counts = np.bincount(ep_of, minlength=rp.N_ep)  # transitions per episode
+        step = (np.arange(rp.N) - np.concatenate([[0], np.cumsum(counts)[:-1]])[ep_of]).astype(np.int32)
+        for e, t in enumerate(trajs):
+            if len(t["gripper_open"]) != int(counts[e]) + 1:
+                raise ValueError(f"OpenLoopEval: episode {e} has {int(counts[e]) + 1} observations in its demo and {len(t['gripper_open'])} steps in its trajectory")
+        rows = ((starts[ep_of] + step)[:, None] * self.V + np.arange(self.V)[None]).reshape(-1)
+        self.views = {k: torch.from_numpy(np.ascontiguousarray(vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:]))).to(dev) for k in vt}
+        self.atlas = torch.from_numpy(load_atlas(render_cfg.texture_dir)).to(dev)
+        self.samples = int(render_cfg.samples)
+        self.step_index, self.episode_index = step, ep_of.copy()
+        names = [_task_of(ep, d) for ep, d in zip(episodes, rp.descriptions)]
+        self.tasks = sorted(set(names))
+        self.task_index = np.asarray([self.tasks.index(names[e]) for e in ep_of], np.int32)
+        # ---- scales, prompt ids
+        std = torch.from_numpy(np.asarray(stats[0]["std"], np.float64)[: self.A - 1].astype(np.float32)).to(dev)
+        self.joint_std = std.contiguous()
+        self.prompts = [harness.make_prompt(d) for d in rp.descriptions]
+        self.prompt_ids = torch.cat([diffusion_agent.pipe.encode_ids([p]) for p in self.prompts]) if diffusion_agent is not None else None
+        self._n_index = torch.arange(rp.N, dtype=torch.int64, device=dev)
+
+    # ---- the steps of one batch (the tests recompute a batch from these inputs)
+    def batch_indices(self, start: int) -> np.ndarray:
+        """Transitions ``start .. start + batch_size - 1``; past the end the last index repeats (the padding of the last batch)."""
+        return np.minimum(np.arange(start, start + self.batch_size), self.N - 1).astype(np.int64)
+
+    def targets(self, idx: np.ndarray) -> Dict[str, torch.Tensor]:
+        """Steps 1 - 3: the sampled batch, the ground-truth render over its frames and the tiled canvas, all on the device."""
+        E, B, V, H, W = self.E, len(idx), self.V, self.H, self.W
+        batch = self.replay.sample(idx, want_u8=True)
+        sel = torch.from_numpy(np.asarray(idx, np.int64)).to(E.device, non_blocking=True)
+        v = {k: t.index_select(0, sel).reshape((B * V,) + tuple(t.shape[2:])).contiguous() for k, t in self.views.items()}
+        frames = batch["images_u8"].view(B * V, H, W, 3)
+        full = torch.empty((B * V, H, W, 3), dtype=torch.uint8, device=E.device)
+        occupied = torch.empty((B * V, H, W), dtype=torch.uint8, device=E.device)
+        E.render_spheres(v["cams"], v["spheres"], v["tex_index"], v["count"], self.atlas, H, W, self.samples, bg=frames, full=full, occupied=occupied)
+        batch["full"], batch["occupied"] = full, occupied
+        if V == 4:  # view v -> the tile at row v / 2, column v % 2 (tiling.CROP_ORDER): layout only
+            batch["tiled"] = frames.view(B, 2, 2, H, W, 3).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * H, 2 * W, 3)
+        return batch
+
+    def generate(self, batch, idx: np.ndarray, generator) -> torch.Tensor:
+        """Step 4: the agent's pipeline on the tiled frames -> the generated tiled targets, uint8 [B, 2H, 2W, 3] on the device."""
+        ep = self.episode_index[np.asarray(idx)]
+        with torch.inference_mode():
+            return self.agent.pipe(prompt=[self.prompts[e] for e in ep], prompt_ids=self.prompt_ids[torch.from_numpy(ep.astype(np.int64))],
+                                   image=batch["tiled"], num_inference_steps=self.num_inference_steps, guidance_scale=self.guidance_scale,
+                                   generator=generator, output_type="pt").images
+
+    def _fresh_controller(self):
+        c = self.controller
+        if getattr(c, "_dirty", False):  # weights moved by update(): re-pack once before acting, as ``act`` does
+            from .act import pack_act
+
+            c._own_state()
+            c.W = pack_act(c._sd, c.device)
+            c._progs, c._dirty = {}, False
+
+    def _chunk(self, img_bvhw3: torch.Tensor, batch) -> torch.Tensor:
+        """The controller on per-view frames uint8 [B, V, H, W, 3] -> its f16 chunk, a view of the program's padded output buffer."""
+        io = self.controller._run(img_bvhw3, batch["low_dim_state"].flatten(1), batch.get("lang_tokens"))
+        return io.a_hat[..., : self.A]
+
+    def _score_actions(self, a_hat, batch, tabs, row0: int, n_valid: int):
+        self.E.openloop_action_metrics(a_hat, batch["action"], tabs["norm"], row0=row0, n_valid=n_valid)
+        self.E.openloop_action_metrics(a_hat, batch["action"], tabs["rad"], joint_scale=self.joint_std, row0=row0, n_valid=n_valid)
+
+    def _tables(self):
+        dev, N, T = self.E.device, self.N, self.T
+
+        def act():
+            return {unit: torch.zeros((N, T, 2), dtype=torch.float32, device=dev) for unit in ("norm", "rad")}
+
+        tabs = {"oracle": act()}
+        if self.agent is not None:
+            tabs["generated"] = act()
+            tabs["image"] = torch.zeros((N, self.V, 5), dtype=torch.int64, device=dev)
+        return tabs
+
+    def run_batch(self, start: int, tabs, generator) -> None:
+        """One evaluator batch: steps 1 - 7 for transitions ``start ..``, everything on the device, nothing read back."""
+        self._fresh_controller()
+        idx = self.batch_indices(start)
+        n_valid = min(self.batch_size, self.N - start)
+        with torch.inference_mode():  # as harness.control_step runs the same two programs
+            batch = self.targets(idx)
+            B = len(idx)
+            if self.agent is not None:
+                gen = self.generate(batch, idx, generator)
+                a_hat = self.controller.act_tiled(gen, batch["low_dim_state"], batch.get("lang_tokens"))
+                self.E.openloop_image_metrics(gen, batch["full"], batch["occupied"], tabs["image"], row0=start, n_valid=n_valid)
+                self._score_actions(a_hat, batch, tabs["generated"], start, n_valid)  # before the oracle pass overwrites the program's chunk
+            a_hat = self._chunk(batch["full"].view(B, self.V, self.H, self.W, 3), batch)
+            self._score_actions(a_hat, batch, tabs["oracle"], start, n_valid)
+
+    def run(self) -> OpenLoopResult:
+        tabs = self._tables()
+        generator = torch.Generator(device=self.E.device).manual_seed(self.seed) if self.agent is not None else None
+        for start in range(0, self.N, self.batch_size):
+            self.run_batch(start, tabs, generator)
+        # the one device-to-host copy: every table as bytes of one buffer
+        flat = [tabs[k][m] for k in ("generated", "oracle") if k in tabs for m in ("norm", "rad")] + ([tabs["image"]] if "image" in tabs else [])
+        host = torch.cat([t.reshape(-1).view(torch.uint8) for t in flat]).cpu().numpy()
+        out, o = [], 0
+        for t in flat:
+            n = t.numel() * t.element_size()
+            out.append(host[o: o + n].view(np.int64 if t.dtype == torch.int64 else np.float32).reshape(tuple(t.shape)).copy())
+            o += n
+        actions, k = {}, 0
+        for name in ("generated", "oracle"):
+            if name in tabs:
+                actions[name] = {"norm": out[k], "rad": out[k + 1]}
+                k += 2
+        image = out[k] if "image" in tabs else None
+        return OpenLoopResult(image, actions, self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1, self.H, self.W)
+
+
+def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None):
+    """-> a ``validate`` callable for ``ControllerTrainLoop``: ``(agent, epochs_done) -> {"select", "joint_l1_norm", "joint_l1_rad",
+    "gripper_acc", "n"}``.  It scores the controller ALONE on held-out demos with the ground-truth targets (the oracle row: sample, render,
+    controller; no diffusion agent), reads the agent's current weights and changes none; ``select`` is the normalised joint L1, so
+    ``best.pt`` follows its minimum.  The demo set is loaded onto the device at the first call and kept."""
+    state: Dict = {}
+
+    def validate(agent, epochs_done: int) -> Dict[str, float]:
+        ev = state.get("ev")
+        if ev is None or ev.controller is not agent:
+            ev = state["ev"] = OpenLoopEval(None, agent, episodes, cameras, render_cfg=render_cfg, stats=stats, tokenizer=tokenizer,
+                                            batch_size=batch_size, engine=engine)
+        s = ev.run().summary()["oracle"]
+        return {"select": s["joint_l1_norm"], "joint_l1_norm": s["joint_l1_norm"], "joint_l1_rad": s["joint_l1_rad"],
+                "gripper_acc": s["gripper_acc"], "n": float(len(ev.replay))}
+
+    return validate

@@ -808,6 +808,37 @@ typedef struct gn_replay_render_desc {
 } gn_replay_render_desc;
 int32_t gn_replay_render(gn_ctx* ctx, const gn_replay_render_desc* d);
 
+/* Open-loop evaluation scores (genima_amd/openloop.py OpenLoopEval): a generated image against the rendered ground truth, and a predicted action
+ * chunk against the demo's.  Both write rows row0 .. row0 + n_valid - 1 of a result table of `rows` rows: sample b < n_valid writes row
+ * row0 + b, samples b >= n_valid (the padding of a last batch) write nothing.  Eager only.  A refused call (NULL required pointer, B, V, H, W,
+ * T <= 0, A < 2, n_valid outside [0, B], row0 < 0 or row0 + n_valid > rows, tiled with V != 4) launches nothing and leaves the outputs as they
+ * were; n_valid == 0 is accepted and does nothing.
+ *
+ * gn_openloop_image_metrics, per (sample b, view v), in integer arithmetic:
+ *   gen       uint8: tiled = 1 (V = 4): the pipeline's [B][2H][2W][3] output, view v = the tile at row v / 2, column v % 2 (the order
+ *             GenimaACT.act_tiled untiles in);  tiled = 0: [B * V][H][W][3]
+ *   gt        uint8 [B * V][H][W][3], occupied uint8 [B * V][H][W]: gn_render_spheres' `full` and `occupied`
+ *   img_out   uint64 [rows][V][5], 8-byte aligned = (se_in, n_in, se_out, n_out, wrap_sq):
+ *     se_in   = sum over the pixels with occupied != 0 and the 3 channels of (gen - gt)^2, as plain integers;  n_in = the number of those pixels
+ *     se_out, n_out: the same over the pixels with occupied == 0
+ *     wrap_sq = sum over ALL pixels and channels of ((d * d) & 255) with d = (gen - gt) & 255: numpy's uint8 arithmetic, so wrap_sq / (H W 3) is
+ *               the `mse` of the reference's validation score (diffusion/train_controlnet_genima.py:642-650) for one view
+ *   The entry point zeroes the rows it owns (on the ctx stream), then per-block partial sums are added with 64-bit vector atomics: integer
+ *   addition is order-independent, so every run gives the same bits.  H * W * 3 < 2^31; B, V <= 65535.
+ *
+ * gn_openloop_action_metrics, per (sample b, chunk position t), one thread each:
+ *   a_hat     f16, element (b, t, j) at a_hat[b * bs_hat + t * ld_hat + j] (gn_act_loss's addressing; ld_hat >= A);  actions f32 [B][T][A]
+ *   joint_scale  f32 [A - 1] or NULL (= 1): the action std gives radians
+ *   act_out   f32 [rows][T][2]:
+ *     [0] = sum over j < A - 1 of joint_scale[j] * |a_hat[j] - actions[j]|: each term one f32 subtraction of the exactly converted half, one
+ *           f32 multiplication, added in f32 in index order j = 0 .. A - 2 (no fused multiply-add), so the bits repeat
+ *     [1] = 1.0 where (a_hat[A - 1] > 0) == (actions[A - 1] > 0.5), else 0.0: the gripper output is a logit (calculate_loss uses
+ *           BCE-with-logits); a logit of exactly 0 counts as closed */
+int32_t gn_openloop_image_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_t* gt, const uint8_t* occupied, uint64_t* img_out, int32_t B, int32_t V,
+                                  int32_t H, int32_t W, int32_t tiled, int32_t row0, int32_t n_valid, int32_t rows);
+int32_t gn_openloop_action_metrics(gn_ctx* ctx, const void* a_hat, int64_t ld_hat, int64_t bs_hat, const float* actions, const float* joint_scale,
+                                   float* act_out, int32_t B, int32_t T, int32_t A, int32_t row0, int32_t n_valid, int32_t rows);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */

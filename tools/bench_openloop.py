@@ -1,0 +1,150 @@
+"""What one batch of the open-loop evaluation costs against the bare joint call it wraps: full-size networks with synthetic weights (SD-Turbo +
+ControlNet, the full ACT config), B = 8, V = 4, 256^2 views, synthetic episodes, one process, two routes on the same batch that alternate
+inside every repetition:
+
+  (a) the bare joint call: the pipeline (``output_type="pt"``) -> ``GenimaACT.act_tiled``
+  (b) one evaluator batch (``OpenLoopEval.run_batch``): sample -> ``gn_render_spheres`` -> tile -> pipeline -> ``act_tiled`` -> image and
+      action scores -> the oracle controller pass on the rendered target -> its action scores
+
+Each figure is the median (with min / max) of ``--reps`` individually synchronised repetitions after ``--warmup``, a host clock around work
+that ends in a stream synchronise.  The oracle controller pass alone is timed the same way, and the three launches -- the two metric kernels
+and ``gn_render_spheres`` -- by device events (5 x 100 launches).  The claim checked: (b) costs no more than (a) plus the run's own min-max
+spread of (a).
+
+Prints one JSON line; needs an MI355X.
+
+    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12]
+        [--sphere_textures tests/golden/sphere_textures] [--out profiles/openloop_b8.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+import types
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, HERE)
+
+
+def stats(ms):
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--episodes", type=int, default=2)
+    ap.add_argument("--length", type=int, default=12)
+    ap.add_argument("--family", default="sd-turbo")
+    ap.add_argument("--sphere_textures", default=os.path.join(HERE, "tests", "golden", "sphere_textures"))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+
+    from genima_amd import configs
+    from genima_amd import render as R
+    from genima_amd import replay as P
+    from genima_amd.act import GenimaACT
+    from genima_amd.agent import SDControlNetAgent
+    from genima_amd.engine import Engine
+    from genima_amd.openloop import OpenLoopEval
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_openloop: no ROCm device (this tool measures on the GPU only)")
+    B, S, cams = args.batch, 256, P.DEFAULT_CAMERAS
+    tiny = args.family == "tiny"
+    ccfg = configs.TINY_ACT_CLIP_TEXT if tiny else configs.ACT_CLIP_TEXT
+    E = Engine(torch.device("cuda", 0))
+
+    def tokens(texts):  # a fixed 5-token prompt, the end-of-text id last (the highest id marks the pooled position)
+        t = np.zeros((1, 77), np.int32)
+        t[0, :5] = [ccfg["vocab_size"] - 2, 3, 4, 5, ccfg["vocab_size"] - 1]
+        return t
+
+    eps, demos, rcfg = [], [], None
+    for e in range(args.episodes):
+        demo, frames = P.synthetic_demo(args.length, seed=e, size=S, cameras=cams)
+        rcfg, traj, _ = R.synthetic_episode(args.length, seed=7 + e, texture_dir=args.sphere_textures, action_horizon=4)
+        eps.append((demo, frames, traj, "open the box"))
+        demos.append(demo)
+    ns = types.SimpleNamespace(diffusion_ckpt="", sd_ckpt=f"synthetic:{args.family}", device="cuda", image_resolution=2 * S, vae_slicing=False,
+                               upcast_vae=False, fused_projections=True, enable_xformers_memory_efficient_attention=True,
+                               show_diffusion_progress=False, torch_compile=False, autoencoder="")
+    dagent = SDControlNetAgent(ns)
+    controller = GenimaACT(dict(configs.TINY_ACT_POLICY if tiny else configs.ACT_POLICY, image_size=S), None, ccfg, None, device="cuda", seed=4)
+    ev = OpenLoopEval(dagent, controller, eps, cams, render_cfg=rcfg, stats=(P.action_stats(demos), P.proprio_stats(demos)), tokenizer=tokens,
+                      batch_size=B, engine=E)
+    tabs = ev._tables()
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    idx = ev.batch_indices(0)
+    with torch.inference_mode():
+        batch = ev.targets(idx)
+    ids = ev.prompt_ids[torch.from_numpy(ev.episode_index[idx].astype(np.int64))]
+
+    def bare():
+        with torch.inference_mode():
+            out = dagent.pipe(prompt_ids=ids, image=batch["tiled"], num_inference_steps=ev.num_inference_steps, guidance_scale=ev.guidance_scale,
+                              generator=gen, output_type="pt").images
+            return out, controller.act_tiled(out, batch["low_dim_state"], batch["lang_tokens"])
+
+    def oracle():
+        with torch.inference_mode():
+            return ev._chunk(batch["full"].view(B, ev.V, S, S, 3), batch)
+
+    routes = {"bare_joint_call": bare, "evaluator_batch": lambda: ev.run_batch(0, tabs, gen), "oracle_controller_pass": oracle}
+    ms = {k: [] for k in routes}
+    for i in range(args.warmup + args.reps):
+        for k, fn in routes.items():
+            E.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t) * 1e3)
+    res = {"tool": "bench_openloop", "device": torch.cuda.get_device_name(0), "family": args.family, "batch": B, "views": ev.V, "size": S,
+           "transitions": ev.N, "num_inference_steps": ev.num_inference_steps, "reps": args.reps, "warmup": args.warmup}
+    for k in routes:
+        res[k] = stats(ms[k])
+    a, b = res["bare_joint_call"], res["evaluator_batch"]
+    res["evaluator_minus_bare_ms"] = round(b["median_ms"] - a["median_ms"], 4)
+    res["bare_spread_ms"] = round(a["max_ms"] - a["min_ms"], 4)
+    res["evaluator_within_bare_spread"] = bool(res["evaluator_minus_bare_ms"] <= res["bare_spread_ms"])
+    # the three launches alone
+    out_img, a_hat = bare()
+    sel = torch.from_numpy(idx).cuda()
+    v = {k: t.index_select(0, sel).reshape((B * ev.V,) + tuple(t.shape[2:])).contiguous() for k, t in ev.views.items()}
+    frames = batch["images_u8"].view(B * ev.V, S, S, 3)
+    launches = {"image_metrics_us": lambda: E.openloop_image_metrics(out_img, batch["full"], batch["occupied"], tabs["image"]),
+                "action_metrics_us": lambda: E.openloop_action_metrics(a_hat, batch["action"], tabs["generated"]["rad"], joint_scale=ev.joint_std),
+                "render_spheres_us": lambda: E.render_spheres(v["cams"], v["spheres"], v["tex_index"], v["count"], ev.atlas, S, S, ev.samples, bg=frames,
+                                                              full=batch["full"], occupied=batch["occupied"])}
+    for name, launch in launches.items():
+        us = []
+        for _ in range(5):
+            for _ in range(10):
+                launch()
+            s, e = E.event(), E.event()
+            E.event_record(s)
+            for _ in range(100):
+                launch()
+            E.event_record(e)
+            E.synchronize()
+            us.append(E.event_elapsed_ms(s, e) / 100 * 1e3)
+        res[name] = {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
+    res["image_metrics_bytes"] = int(out_img.numel() + batch["full"].numel() + batch["occupied"].numel())
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,89 @@
+"""Score a diffusion checkpoint and a controller snapshot on held-out demos, open loop (``genima_amd.openloop.OpenLoopEval``): for every
+transition of the demo tree, diffusion then the controller as the eval loop's body runs them, the generated target against the rendered
+ground truth, the predicted action chunk against the demo's, and the controller again on the ground-truth target (the oracle row).
+
+    python tools/eval_openloop.py --dataset_root /data/rlbench_data_val --tasks take_lid_off_saucepan --demos 5 \
+        --sd_ckpt ./sd-turbo --diffusion_ckpt ./controlnet_out --controller_snapshot ./exp_local/snapshots/genima_controller/best.pt \
+        --stats_dir ./exp_local/snapshots/genima_controller --clip_text ./clip-vit-base-patch32 --sphere_textures ./sphere_textures \
+        --out openloop.json
+
+Reads ``<dataset_root>/<task>/variation0/episodes/<episode>/{<camera>_rgb/<ts>.png, demo.npz, traj.npz[, description.txt]}`` (the camera frames
+are the SCENE frames the diffusion agent sees at run time; ``tools/render_dataset.py`` writes ``traj.npz``, ``genima_amd.replay.save_demo``
+``demo.npz``).  ``--stats_dir`` holds the TRAINING run's ``action_stats.json`` / ``proprio_stats.json``: the held-out demos are normalised with
+those, never with their own.  Prints the summary and writes it as JSON.  Open-loop error is not a success rate: every chunk is predicted from
+a demo state, nothing is executed and no error compounds."""
+import argparse
+import json
+import os
+import sys
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from genima_amd import replay as P  # noqa: E402
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dataset_root", required=True)
+    ap.add_argument("--tasks", nargs="+", default=["take_lid_off_saucepan"])
+    ap.add_argument("--demos", type=int, default=5)
+    ap.add_argument("--sd_ckpt", required=True, help="diffusers directory of the base model, or synthetic:<family>")
+    ap.add_argument("--diffusion_ckpt", default="", help="the fine-tune's output directory (checkpoint-N/controlnet) or a ControlNet directory")
+    ap.add_argument("--agent", default="SDControlNetAgent", choices=["SDControlNetAgent", "SDXLControlNetAgent", "SDPix2PixAgent"])
+    ap.add_argument("--autoencoder", default="")
+    ap.add_argument("--controller_snapshot", required=True, help="latest.pt / best.pt / <epoch>.pt of tools/train_act.py")
+    ap.add_argument("--stats_dir", required=True, help="directory of the training run's action_stats.json and proprio_stats.json")
+    ap.add_argument("--clip_text", default=None, help="transformers CLIPTextModel directory (weights and tokenizer) of the controller")
+    ap.add_argument("--cameras", nargs="+", default=list(P.DEFAULT_CAMERAS))
+    ap.add_argument("--image_size", type=int, default=256)
+    ap.add_argument("--action_sequence", type=int, default=20)
+    ap.add_argument("--action_horizon", type=int, default=20, help="render.yaml's horizon of the drawn joint target")
+    ap.add_argument("--sphere_textures", default="./sphere_textures/")
+    ap.add_argument("--batch_size", type=int, default=8)
+    ap.add_argument("--num_inference_steps", type=int, default=5)
+    ap.add_argument("--guidance_scale", type=float, default=0.0)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default="openloop.json")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse(argv)
+    from genima_amd import agent as A
+    from genima_amd import configs, harness
+    from genima_amd import render as R
+    from genima_amd.act import GenimaACT
+    from genima_amd.openloop import OpenLoopEval
+
+    episodes = P.list_episodes(a.dataset_root, a.tasks, a.demos)
+    if not episodes:
+        raise SystemExit(f"eval_openloop: no episodes under {a.dataset_root} for tasks {a.tasks}")
+    rcfg = R.RenderConfig(image_width=a.image_size, image_height=a.image_size, action_horizon=a.action_horizon, texture_dir=a.sphere_textures)
+    for ep in episodes:
+        if not os.path.exists(os.path.join(ep, "demo.npz")):
+            P.save_demo(os.path.join(ep, "demo.npz"), P.demo_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl")))
+        if not os.path.exists(os.path.join(ep, "traj.npz")):
+            R.save_traj(os.path.join(ep, "traj.npz"), R.traj_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl"), rcfg.cameras))
+    clip_sd = tokenizer = None
+    if a.clip_text:
+        from genima_amd import weights
+        from genima_amd.tokenizer import CLIPTokenizer
+
+        _, clip_sd = weights.load_diffusers_dir(a.clip_text)
+        tokenizer = CLIPTokenizer.from_pretrained(a.clip_text)
+    ns = types.SimpleNamespace(diffusion_ckpt=a.diffusion_ckpt, sd_ckpt=a.sd_ckpt, device="cuda", image_resolution=2 * a.image_size, vae_slicing=False,
+                               upcast_vae=False, fused_projections=True, enable_xformers_memory_efficient_attention=True,
+                               show_diffusion_progress=False, torch_compile=False, autoencoder=a.autoencoder)
+    dagent = getattr(A, a.agent)(ns)
+    cfg = dict(configs.ACT_POLICY, num_queries=a.action_sequence, num_views=len(a.cameras), image_size=a.image_size, use_lang_cond=tokenizer is not None)
+    controller = GenimaACT(cfg, None, configs.ACT_CLIP_TEXT, clip_sd, device="cuda", seed=a.seed)
+    harness.load_controller_ckpt(controller, a.controller_snapshot)
+    ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=P.load_stats(a.stats_dir), tokenizer=tokenizer,
+                      batch_size=a.batch_size, num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed)
+    print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
+    summary = ev.run().to_json(a.out)
+    print(json.dumps(summary, indent=1))
+
+
+if __name__ == "__main__":
+    main()

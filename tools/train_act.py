@@ -16,6 +16,11 @@ fresh texture and blend factor for every frame of every batch:
 
     python tools/train_act.py --dataset_root /data/rlbench_data --rnd_bg_textures ./textures --sphere_textures ./sphere_textures ...
 
+With ``--val_root DIR`` (a second tree of the same layout whose episodes hold the scene frames, ``demo.npz`` and ``traj.npz``) every snapshot
+is scored on the first ``--val_demos`` held-out demos of each task -- the controller alone on the rendered ground-truth targets
+(``genima_amd.openloop.controller_validator``) -- into ``validation.jsonl``, and the snapshot with the lowest normalised joint L1 is kept as
+``best.pt``.
+
 Writes
 ``<work_dir>/snapshots/<experiment_name>/{latest.pt, <epoch>.pt, action_stats.json, proprio_stats.json}``.  Nothing from RoboBase or RLBench is
 imported otherwise.  ``--clip_text``: a transformers ``CLIPTextModel`` directory (weights + tokenizer files) for the task-string
@@ -53,6 +58,9 @@ def parse(argv=None):
     ap.add_argument("--sphere_textures", default="./sphere_textures/", help="directory of the five sphere_<colour>_stripe_texture.png files")
     ap.add_argument("--alpha_blend", type=float, default=0.7, help="lower end of the sphere / texture blend factor (render.yaml: 0.7)")
     ap.add_argument("--render_seed", type=int, default=0, help="seed of the background draws")
+    ap.add_argument("--val_root", default=None, help="held-out demo tree: score every snapshot on it (validation.jsonl) and keep the best as best.pt")
+    ap.add_argument("--val_demos", type=int, default=5, help="held-out demos per task")
+    ap.add_argument("--val_action_horizon", type=int, default=20, help="render.yaml's horizon of the joint targets drawn for validation")
     return ap.parse_args(argv)
 
 
@@ -100,8 +108,22 @@ def main(argv=None):
         if it % a.log_every == 0:
             print(f"iter {it}: " + " ".join(f"{k}={v:.5f}" for k, v in metrics.items()), flush=True)
 
+    validate = None
+    if a.val_root:
+        from genima_amd import render as R
+        from genima_amd.openloop import controller_validator
+
+        vcfg = R.RenderConfig(image_width=a.image_size, image_height=a.image_size, action_horizon=a.val_action_horizon, texture_dir=a.sphere_textures)
+        val_eps = P.list_episodes(a.val_root, a.tasks, a.val_demos)
+        for ep in val_eps:
+            if not os.path.exists(os.path.join(ep, "demo.npz")):
+                P.save_demo(os.path.join(ep, "demo.npz"), P.demo_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl")))
+            if not os.path.exists(os.path.join(ep, "traj.npz")):
+                R.save_traj(os.path.join(ep, "traj.npz"), R.traj_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl"), vcfg.cameras))
+        validate = controller_validator(val_eps, a.cameras, render_cfg=vcfg, stats=(replay.action_stats, replay.proprio_stats), tokenizer=tokenizer,
+                                        batch_size=a.batch_size, engine=replay.E)
     ControllerTrainLoop(agent, replay, a.work_dir, a.experiment_name, a.num_train_epochs, a.checkpoint_every, a.num_checkpoints, log=log,
-                        cfg={k: v for k, v in vars(a).items()}).train()
+                        cfg={k: v for k, v in vars(a).items()}, validate=validate).train()
 
 
 if __name__ == "__main__":
