@@ -182,6 +182,9 @@ class RenderDesc(C.Structure):
                 + [(n, C.c_float) for n in ("full_mul", "full_add", "rnd_mul", "rnd_add")])
 
 
+# the structs gn_desc_sizeof(which) reports, in its order: load() refuses a library whose sizes differ (tests/test_abi.py checks the same list)
+DESC_CLASSES = (GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc, ReplayGatherDesc, ReplayRenderDesc)
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/genima_hip.h declares (tests/test_abi.py checks the two agree)
@@ -389,7 +392,7 @@ def load() -> C.CDLL:
             raise GenimaHipError(f"{LIB_PATH} does not export {name} (stale build?)") from e
         fn.restype = res
         fn.argtypes = args
-    for which, cls in enumerate((GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc, ReplayGatherDesc, ReplayRenderDesc)):
+    for which, cls in enumerate(DESC_CLASSES):
         if int(lib.gn_desc_sizeof(which)) != C.sizeof(cls):  # a stale .so against newer Python (or the reverse) would read garbage descriptors
             raise GenimaHipError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(lib.gn_desc_sizeof(which))} in the library, {C.sizeof(cls)} in the "
                                  "binding (stale build? run `python -m genima_amd.build`)")

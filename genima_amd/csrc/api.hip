@@ -2,7 +2,10 @@
 #include <stdarg.h>
 #include <string.h>
 
+#include <functional>
 #include <map>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -18,40 +21,45 @@ void gn_set_error(const char* fmt, ...) {
 
 namespace {
 
-enum OpType {
-  OP_GEMM = 0, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM, OP_TEMB, OP_SCALE_PAD, OP_EULER, OP_F16_TO_U8, OP_U8_TO_F16, OP_ADD,
-  OP_ACT, OP_EMBED, OP_SOFTMAX, OP_MAXPOOL, OP_NORMALIZE_U8, OP_GATHER_ROWS, OP_COPY4D, OP_ARGMAX, OP_ADD_NOISE, OP_FILM, OP_SCALE_CAT_PAD,
-  OP_TBLOCK, OP_CONV_GN, OP_CONV_PATCH, OP_ADD_MULTI, OP_MEMSET, OP_TINY_BLOCK, OP_ACTION_ENSEMBLE,
-  OP_FORK, OP_MAIN, OP_JOIN  // stream control: ops after FORK go to the program's side stream until MAIN; JOIN makes main wait for it
-};
-
-struct GenericArgs {  // argument block of the small ops
-  const void* p0; const void* p1; const void* p2; void* p3;
-  int64_t n0, n1;
-  int32_t i0, i1, i2, i3;
-  float f0, f1;
-  int64_t m[12];  // copy4d: sizes[4], in_strides[4], out_strides[4]; tiny block: w[3], bias[3]
-  float g[6];     // normalize: mul[3], add[3]
-};
+// A recorded op is the eager entry point bound to its arguments (Kernel).  The three ops that gn_program_get_gemm / set_* read and rewrite after
+// recording keep a typed payload in the Op instead and are dispatched by kind: a closure must not point into gn_program::ops (the vector
+// reallocates).  Stream control: ops after Fork go to the program's side stream until Main; Join makes main wait for it.
+enum class Kind { Kernel, Gemm, AddMulti, Memset, Fork, Main, Join };
 
 struct AddMultiOp {
   const void* a[GN_ADD_MULTI_MAX]; const void* b[GN_ADD_MULTI_MAX]; void* out[GN_ADD_MULTI_MAX]; int64_t n[GN_ADD_MULTI_MAX]; int32_t count;
   int32_t C[GN_ADD_MULTI_MAX]; gn_stats_sink sink[GN_ADD_MULTI_MAX]; int32_t has_sink;  // GroupNorm bridge (gn_program_set_sink)
 };
 
+struct MemsetOp { void* ptr; int64_t bytes; };
+
 struct Op {
-  int type;
-  union {
-    AddMultiOp addm;
-    gn_gemm_desc gemm;
-    gn_attn_desc attn;
-    gn_groupnorm_desc gnorm;
-    gn_tblock_desc tblock;
-    gn_conv3x3_gn_desc convgn;
-    gn_conv3x3_patch_desc convpatch;
-    GenericArgs g;
-  };
+  Kind kind;
+  const char* name;                         // the gn_ entry point a replay calls (error text)
+  std::function<int32_t(gn_ctx*)> launch;   // Kernel
+  union { AddMultiOp addm; gn_gemm_desc gemm; MemsetOp ms; };  // AddMulti / Gemm / Memset (the largest first: Op{} zeroes all of it)
 };
+
+static Op make_op(Kind kind, const char* name) {
+  static_assert(sizeof(AddMultiOp) >= sizeof(gn_gemm_desc) && sizeof(AddMultiOp) >= sizeof(MemsetOp), "the union's first member covers the others");
+  Op op{};
+  op.kind = kind;
+  op.name = name;
+  return op;
+}
+
+// An array argument, copied into the closure and handed to the entry point as a pointer to the copy: the caller's arrays are temporaries
+// (ctypes arrays that die when gn_program_add_* returns).
+template <class T, size_t N>
+struct Arr {
+  T v[N];
+  explicit Arr(const T* s) { for (size_t i = 0; i < N; ++i) v[i] = s[i]; }
+  operator const T*() const { return v; }
+};
+
+// an argument binds to a parameter of exactly its own type (no conversion on the way into the closure or out of it); an Arr to a pointer to its elements
+template <class A, class P> constexpr bool binds = std::is_same<A, P>::value;
+template <class T, size_t N, class P> constexpr bool binds<Arr<T, N>, P> = std::is_same<const T*, P>::value;
 
 }  // namespace
 
@@ -90,60 +98,43 @@ static bool op_skipped(const gn_program* p, int64_t i) {
 }
 
 static int32_t run_op(gn_ctx* ctx, const Op& op) {
-  const GenericArgs& g = op.g;
-  switch (op.type) {
-    case OP_GEMM: return gn_launch_gemm(ctx, &op.gemm);
-    case OP_ATTN: return gn_launch_attention(ctx, &op.attn);
-    case OP_GROUPNORM: return gn_launch_groupnorm(ctx, &op.gnorm);
-    case OP_TBLOCK: return gn_launch_tblock(ctx, &op.tblock);
-    case OP_CONV_GN: return gn_conv3x3_gn(ctx, &op.convgn);
-    case OP_CONV_PATCH: return gn_conv3x3_patch(ctx, &op.convpatch);
-    case OP_LAYERNORM: return gn_layernorm_fwd(ctx, g.p0, g.p1, g.p2, g.p3, g.n0, g.i0, g.f0);
-    case OP_TEMB: return gn_timestep_embedding(ctx, (const float*)g.p0, g.p3, g.i0, g.i1, g.i2, g.f0);
-    case OP_SCALE_PAD: return gn_scale_pad(ctx, g.p0, g.p3, g.n0, g.i0, g.i1, g.f0);
-    case OP_SCALE_CAT_PAD: return gn_scale_cat_pad(ctx, g.p0, g.p1, g.p3, g.n0, g.i0, (int32_t)g.n1, g.i1, g.i2, g.i3, g.f0, g.f1);
-    case OP_EULER: return gn_euler_step(ctx, g.p3, g.p0, g.n0, g.i0, g.i1, g.f0, g.f1);
-    case OP_F16_TO_U8: return gn_image_f16_to_u8(ctx, g.p0, (uint8_t*)g.p3, g.n0, g.i0);
-    case OP_U8_TO_F16: return gn_image_u8_to_f16(ctx, (const uint8_t*)g.p0, g.p3, g.n0, g.i0, g.f0, g.f1);
-    case OP_ADD: return gn_add(ctx, g.p0, g.p1, g.p3, g.n0);
-    case OP_ADD_MULTI:
+  switch (op.kind) {
+    case Kind::Kernel: return op.launch(ctx);
+    case Kind::Gemm: return gn_launch_gemm(ctx, &op.gemm);
+    case Kind::AddMulti:
       if (op.addm.has_sink) return gn_add_multi_stats(ctx, op.addm.a, op.addm.b, op.addm.out, op.addm.n, op.addm.C, op.addm.sink, op.addm.count);
       return gn_add_multi(ctx, op.addm.a, op.addm.b, op.addm.out, op.addm.n, op.addm.count);
-    case OP_MEMSET: return gn_memset(ctx, g.p3, g.n0);
-    case OP_ACT: return gn_act(ctx, g.p0, g.p3, g.n0, g.i0);
-    case OP_FILM: return gn_film(ctx, g.p0, g.p3, g.p1, g.p2, g.m[0], g.m[1], g.n0, g.i0, g.i1);
-    case OP_EMBED: return gn_embedding(ctx, (const int32_t*)g.p0, g.p1, g.p2, g.p3, g.i0, g.i1, g.i2);
-    case OP_SOFTMAX: return gn_softmax_rows(ctx, g.p3, g.n0, g.i0, g.i1, g.f0);
-    case OP_MAXPOOL: return gn_maxpool3x3s2(ctx, g.p0, g.p3, g.i0, g.i1, g.i2, g.i3);
-    case OP_NORMALIZE_U8: return gn_image_normalize_u8(ctx, (const uint8_t*)g.p0, g.p3, g.n0, g.i0, g.g[0], g.g[1], g.g[2], g.g[3], g.g[4], g.g[5]);
-    case OP_GATHER_ROWS: return gn_gather_rows(ctx, g.p0, (const int32_t*)g.p1, g.p3, g.i0, g.i1, g.i2);
-    case OP_COPY4D: return gn_copy4d(ctx, g.p0, g.p3, g.m, g.m + 4, g.m + 8, g.i0);
-    case OP_ARGMAX: return gn_argmax_rows_i32(ctx, (const int32_t*)g.p0, (int32_t*)g.p3, g.i0, g.i1);
-    case OP_TINY_BLOCK: {
-      const void* w[3] = {(const void*)(uintptr_t)g.m[0], (const void*)(uintptr_t)g.m[1], (const void*)(uintptr_t)g.m[2]};
-      const void* bias[3] = {(const void*)(uintptr_t)g.m[3], (const void*)(uintptr_t)g.m[4], (const void*)(uintptr_t)g.m[5]};
-      return gn_tiny_block(ctx, g.p0, w, bias, g.p3, g.i0, g.i1, g.i2, g.i3);
-    }
-    case OP_ACTION_ENSEMBLE:  // m[0]: the state blob, m[1]: chunk is f16
-      if (g.m[1]) return gn_action_ensemble_f16(ctx, g.p0, (void*)(uintptr_t)g.m[0], (const int32_t*)g.p1, (const uint8_t*)g.p2, (float*)g.p3, g.i0, g.i1, g.i2, g.i3, (int32_t)g.n0, (int32_t)g.n1, g.f0);
-      return gn_action_ensemble(ctx, (const float*)g.p0, (void*)(uintptr_t)g.m[0], (const int32_t*)g.p1, (const uint8_t*)g.p2, (float*)g.p3, g.i0, g.i1, g.i2, g.i3, (int32_t)g.n0, (int32_t)g.n1, g.f0);
-    case OP_ADD_NOISE: return gn_add_noise(ctx, g.p0, g.p1, (const float*)g.p2, (const float*)(uintptr_t)g.m[0], g.p3, g.i0, g.n0);
-    default: gn_set_error("gn_program: unknown op type %d", op.type); return GN_ERR_INVALID;
+    case Kind::Memset: return gn_memset(ctx, op.ms.ptr, op.ms.bytes);
+    default: gn_set_error("gn_program: %s is not a kernel op", op.name); return GN_ERR_INVALID;
   }
 }
 
-static int32_t push_generic(gn_program* p, int type, const void* p0, const void* p1, const void* p2, void* p3, int64_t n0,
-                            int64_t n1, int32_t i0, int32_t i1, int32_t i2, int32_t i3, float f0, float f1) {
-  GN_REQUIRE(p, "gn_program_add_*: null program");
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = type;
-  op.g.p0 = p0; op.g.p1 = p1; op.g.p2 = p2; op.g.p3 = p3;
-  op.g.n0 = n0; op.g.n1 = n1;
-  op.g.i0 = i0; op.g.i1 = i1; op.g.i2 = i2; op.g.i3 = i3;
-  op.g.f0 = f0; op.g.f1 = f1;
-  p->ops.push_back(op);
+// every gn_program_add_* ends here: exactly one op appended (stream markers included -- the callers index the list), none when refused
+static int32_t push(gn_program* p, const char* who, Op op) {
+  GN_REQUIRE(p, "%s: null program", who);
+  p->ops.push_back(std::move(op));
   return GN_OK;
+}
+
+// record `fn(ctx, args...)`: the arguments are captured by value and checked against fn's own declaration
+template <class... P, class... A>
+static int32_t record(gn_program* p, const char* who, const char* name, int32_t (*fn)(gn_ctx*, P...), A... args) {
+  static_assert(sizeof...(P) == sizeof...(A), "argument count differs from the entry point's");
+  static_assert((binds<A, P> && ...), "an argument's type differs from the entry point's parameter");
+  Op op = make_op(Kind::Kernel, name);
+  op.launch = [fn, args...](gn_ctx* ctx) { return fn(ctx, args...); };
+  return push(p, who, std::move(op));
+}
+// RECORD(gn_X, args...) inside gn_program_add_X(gn_program* p, ...)
+#define RECORD(fn, ...) record(p, __func__, #fn, fn, __VA_ARGS__)
+
+// the descriptor ops that nothing patches after recording: the closure owns a copy of *d
+template <class D>
+static int32_t record_desc(gn_program* p, const char* who, const char* name, int32_t (*fn)(gn_ctx*, const D*), const D* d) {
+  GN_REQUIRE(p && d, "%s: null argument", who);
+  Op op = make_op(Kind::Kernel, name);
+  op.launch = [fn, desc = *d](gn_ctx* ctx) { return fn(ctx, &desc); };
+  return push(p, who, std::move(op));
 }
 
 extern "C" {
@@ -211,154 +202,86 @@ int32_t gn_program_destroy(gn_program* p) {
 }
 int32_t gn_program_add_gemm(gn_program* p, const gn_gemm_desc* d) {
   GN_REQUIRE(p && d, "gn_program_add_gemm: null argument");
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = OP_GEMM;
+  Op op = make_op(Kind::Gemm, "gn_gemm");
   op.gemm = *d;
-  p->ops.push_back(op);
-  return GN_OK;
+  return push(p, __func__, std::move(op));
 }
-int32_t gn_program_add_attention(gn_program* p, const gn_attn_desc* d) {
-  GN_REQUIRE(p && d, "gn_program_add_attention: null argument");
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = OP_ATTN;
-  op.attn = *d;
-  p->ops.push_back(op);
-  return GN_OK;
-}
-int32_t gn_program_add_tblock(gn_program* p, const gn_tblock_desc* d) {
-  GN_REQUIRE(p && d, "gn_program_add_tblock: null argument");
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = OP_TBLOCK;
-  op.tblock = *d;
-  p->ops.push_back(op);
-  return GN_OK;
-}
-int32_t gn_program_add_conv3x3_gn(gn_program* p, const gn_conv3x3_gn_desc* d) {
-  GN_REQUIRE(p && d, "gn_program_add_conv3x3_gn: null argument");
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = OP_CONV_GN;
-  op.convgn = *d;
-  p->ops.push_back(op);
-  return GN_OK;
-}
+int32_t gn_program_add_attention(gn_program* p, const gn_attn_desc* d) { return record_desc(p, __func__, "gn_attention_fwd", gn_launch_attention, d); }
+int32_t gn_program_add_tblock(gn_program* p, const gn_tblock_desc* d) { return record_desc(p, __func__, "gn_tblock", gn_launch_tblock, d); }
+int32_t gn_program_add_conv3x3_gn(gn_program* p, const gn_conv3x3_gn_desc* d) { return record_desc(p, __func__, "gn_conv3x3_gn", gn_conv3x3_gn, d); }
 int32_t gn_program_add_conv3x3_patch(gn_program* p, const gn_conv3x3_patch_desc* d) {
-  GN_REQUIRE(p && d, "gn_program_add_conv3x3_patch: null argument");
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = OP_CONV_PATCH;
-  op.convpatch = *d;
-  p->ops.push_back(op);
-  return GN_OK;
+  return record_desc(p, __func__, "gn_conv3x3_patch", gn_conv3x3_patch, d);
 }
-int32_t gn_program_add_groupnorm(gn_program* p, const gn_groupnorm_desc* d) {
-  GN_REQUIRE(p && d, "gn_program_add_groupnorm: null argument");
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = OP_GROUPNORM;
-  op.gnorm = *d;
-  p->ops.push_back(op);
-  return GN_OK;
-}
+int32_t gn_program_add_groupnorm(gn_program* p, const gn_groupnorm_desc* d) { return record_desc(p, __func__, "gn_groupnorm_fwd", gn_launch_groupnorm, d); }
 int32_t gn_program_add_tiny_block(gn_program* p, const void* x, const void* const w[3], const void* const bias[3], void* out, int32_t B,
                                  int32_t H, int32_t W, int32_t C) {
   GN_REQUIRE(w && bias, "gn_program_add_tiny_block: null weight / bias array");
   GN_REQUIRE(x && out && B > 0 && gn_tiny_block_supported(C, H, W), "gn_program_add_tiny_block: null x / out or unsupported shape (B %d, %dx%d, C %d)", B, H,
              W, C);
-  const int32_t rc = push_generic(p, OP_TINY_BLOCK, x, nullptr, nullptr, out, 0, 0, B, H, W, C, 0.f, 0.f);
-  if (rc == GN_OK)
-    for (int k = 0; k < 3; ++k) {
-      p->ops.back().g.m[k] = (int64_t)(uintptr_t)w[k];
-      p->ops.back().g.m[3 + k] = (int64_t)(uintptr_t)bias[k];
-    }
-  return rc;
+  return RECORD(gn_tiny_block, x, Arr<const void*, 3>(w), Arr<const void*, 3>(bias), out, B, H, W, C);
 }
 int32_t gn_program_add_layernorm(gn_program* p, const void* x, const void* gamma, const void* beta, void* y, int64_t M, int32_t C, float eps) {
-  return push_generic(p, OP_LAYERNORM, x, gamma, beta, y, M, 0, C, 0, 0, 0, eps, 0.f);
+  return RECORD(gn_layernorm_fwd, x, gamma, beta, y, M, C, eps);
 }
 int32_t gn_program_add_timestep_embedding(gn_program* p, const float* t, void* out, int32_t B, int32_t dim, int32_t flip, float freq_shift) {
-  return push_generic(p, OP_TEMB, t, nullptr, nullptr, out, 0, 0, B, dim, flip, 0, freq_shift, 0.f);
+  return RECORD(gn_timestep_embedding, t, out, B, dim, flip, freq_shift);
 }
 int32_t gn_program_add_scale_pad(gn_program* p, const void* x, void* out, int64_t pixels, int32_t C, int32_t Cpad, float scale) {
-  return push_generic(p, OP_SCALE_PAD, x, nullptr, nullptr, out, pixels, 0, C, Cpad, 0, 0, scale, 0.f);
+  return RECORD(gn_scale_pad, x, out, pixels, C, Cpad, scale);
 }
 int32_t gn_program_add_scale_cat_pad(gn_program* p, const void* x, const void* x2, void* out, int64_t pixels, int32_t C, int32_t ld1,
                                      int32_t C2, int32_t ld2, int32_t Cpad, float scale, float scale2) {
-  return push_generic(p, OP_SCALE_CAT_PAD, x, x2, nullptr, out, pixels, ld1, C, C2, ld2, Cpad, scale, scale2);
+  return RECORD(gn_scale_cat_pad, x, x2, out, pixels, C, ld1, C2, ld2, Cpad, scale, scale2);
 }
 int32_t gn_program_add_euler_step(gn_program* p, void* x, const void* eps, int64_t pixels, int32_t C, int32_t ld_eps, float sigma, float sigma_next) {
-  return push_generic(p, OP_EULER, eps, nullptr, nullptr, x, pixels, 0, C, ld_eps, 0, 0, sigma, sigma_next);
+  return RECORD(gn_euler_step, x, eps, pixels, C, ld_eps, sigma, sigma_next);
 }
 int32_t gn_program_add_image_f16_to_u8(gn_program* p, const void* in, uint8_t* out, int64_t pixels, int32_t ld) {
-  return push_generic(p, OP_F16_TO_U8, in, nullptr, nullptr, out, pixels, 0, ld, 0, 0, 0, 0.f, 0.f);
+  return RECORD(gn_image_f16_to_u8, in, out, pixels, ld);
 }
 int32_t gn_program_add_image_u8_to_f16(gn_program* p, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float mul, float add) {
-  return push_generic(p, OP_U8_TO_F16, in, nullptr, nullptr, out, pixels, 0, Cpad, 0, 0, 0, mul, add);
+  return RECORD(gn_image_u8_to_f16, in, out, pixels, Cpad, mul, add);
 }
-int32_t gn_program_add_add(gn_program* p, const void* a, const void* b, void* out, int64_t n) {
-  return push_generic(p, OP_ADD, a, b, nullptr, out, n, 0, 0, 0, 0, 0, 0.f, 0.f);
-}
+int32_t gn_program_add_add(gn_program* p, const void* a, const void* b, void* out, int64_t n) { return RECORD(gn_add, a, b, out, n); }
 int32_t gn_program_add_add_multi(gn_program* p, const void* const* a, const void* const* b, void* const* out, const int64_t* n, int32_t count) {
   GN_REQUIRE(p && a && b && out && n && count >= 1 && count <= GN_ADD_MULTI_MAX, "gn_program_add_add_multi: 1 .. %d tensors", GN_ADD_MULTI_MAX);
-  Op op;
-  memset(&op, 0, sizeof(op));
-  op.type = OP_ADD_MULTI;
+  Op op = make_op(Kind::AddMulti, "gn_add_multi");
   for (int i = 0; i < count; ++i) { op.addm.a[i] = a[i]; op.addm.b[i] = b[i]; op.addm.out[i] = out[i]; op.addm.n[i] = n[i]; }
   op.addm.count = count;
-  p->ops.push_back(op);
-  return GN_OK;
+  return push(p, __func__, std::move(op));
 }
 int32_t gn_program_add_film(gn_program* p, const void* x, void* out, const void* gamma, const void* beta, int64_t ld_film,
                             int64_t rows_per_film, int64_t rows, int32_t C, int32_t act) {
-  const int32_t rc = push_generic(p, OP_FILM, x, gamma, beta, out, rows, 0, C, act, 0, 0, 0.f, 0.f);
-  if (rc == GN_OK) { p->ops.back().g.m[0] = ld_film; p->ops.back().g.m[1] = rows_per_film; }
-  return rc;
+  return RECORD(gn_film, x, out, gamma, beta, ld_film, rows_per_film, rows, C, act);
 }
-int32_t gn_program_add_act(gn_program* p, const void* x, void* out, int64_t n, int32_t act) {
-  return push_generic(p, OP_ACT, x, nullptr, nullptr, out, n, 0, act, 0, 0, 0, 0.f, 0.f);
-}
+int32_t gn_program_add_act(gn_program* p, const void* x, void* out, int64_t n, int32_t act) { return RECORD(gn_act, x, out, n, act); }
 int32_t gn_program_add_embedding(gn_program* p, const int32_t* ids, const void* tok, const void* pos, void* out, int32_t B, int32_t L, int32_t D) {
-  return push_generic(p, OP_EMBED, ids, tok, pos, out, 0, 0, B, L, D, 0, 0.f, 0.f);
+  return RECORD(gn_embedding, ids, tok, pos, out, B, L, D);
 }
 int32_t gn_program_add_softmax_rows(gn_program* p, void* x, int64_t rows, int32_t cols, int32_t ld, float scale) {
-  return push_generic(p, OP_SOFTMAX, nullptr, nullptr, nullptr, x, rows, 0, cols, ld, 0, 0, scale, 0.f);
+  return RECORD(gn_softmax_rows, x, rows, cols, ld, scale);
 }
 int32_t gn_program_add_maxpool3x3s2(gn_program* p, const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C) {
-  return push_generic(p, OP_MAXPOOL, x, nullptr, nullptr, y, 0, 0, B, H, W, C, 0.f, 0.f);
+  return RECORD(gn_maxpool3x3s2, x, y, B, H, W, C);
 }
 int32_t gn_program_add_image_normalize_u8(gn_program* p, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float m0,
                                           float m1, float m2, float a0, float a1, float a2) {
-  int32_t rc = push_generic(p, OP_NORMALIZE_U8, in, nullptr, nullptr, out, pixels, 0, Cpad, 0, 0, 0, 0.f, 0.f);
-  if (rc == GN_OK) {
-    float* g = p->ops.back().g.g;
-    g[0] = m0; g[1] = m1; g[2] = m2; g[3] = a0; g[4] = a1; g[5] = a2;
-  }
-  return rc;
+  return RECORD(gn_image_normalize_u8, in, out, pixels, Cpad, m0, m1, m2, a0, a1, a2);
 }
 int32_t gn_program_add_gather_rows(gn_program* p, const void* x, const int32_t* idx, void* out, int32_t B, int32_t L, int32_t D) {
-  return push_generic(p, OP_GATHER_ROWS, x, idx, nullptr, out, 0, 0, B, L, D, 0, 0.f, 0.f);
+  return RECORD(gn_gather_rows, x, idx, out, B, L, D);
 }
 int32_t gn_program_add_copy4d(gn_program* p, const void* in, void* out, const int64_t* sizes, const int64_t* in_strides,
                               const int64_t* out_strides, int32_t L) {
   GN_REQUIRE(sizes && in_strides && out_strides, "gn_program_add_copy4d: null argument");
-  int32_t rc = push_generic(p, OP_COPY4D, in, nullptr, nullptr, out, 0, 0, L, 0, 0, 0, 0.f, 0.f);
-  if (rc == GN_OK) {
-    int64_t* m = p->ops.back().g.m;
-    for (int i = 0; i < 4; ++i) { m[i] = sizes[i]; m[4 + i] = in_strides[i]; m[8 + i] = out_strides[i]; }
-  }
-  return rc;
+  return RECORD(gn_copy4d, in, out, Arr<int64_t, 4>(sizes), Arr<int64_t, 4>(in_strides), Arr<int64_t, 4>(out_strides), L);
 }
 int32_t gn_program_add_argmax_rows_i32(gn_program* p, const int32_t* x, int32_t* out, int32_t rows, int32_t cols) {
-  return push_generic(p, OP_ARGMAX, x, nullptr, nullptr, out, 0, 0, rows, cols, 0, 0, 0.f, 0.f);
+  return RECORD(gn_argmax_rows_i32, x, out, rows, cols);
 }
 int32_t gn_program_add_add_noise(gn_program* p, const void* x0, const void* noise, const float* sqrt_ac, const float* sqrt_1mac, void* out, int32_t B,
                                  int64_t per_sample) {
-  const int32_t rc = push_generic(p, OP_ADD_NOISE, x0, noise, sqrt_ac, out, per_sample, 0, B, 0, 0, 0, 0.f, 0.f);
-  if (rc == GN_OK) p->ops.back().g.m[0] = (int64_t)(uintptr_t)sqrt_1mac;
-  return rc;
+  return RECORD(gn_add_noise, x0, noise, sqrt_ac, sqrt_1mac, out, B, per_sample);
 }
 int32_t gn_program_add_action_ensemble(gn_program* p, const void* chunk, int32_t chunk_f16, void* state, const int32_t* steps, const uint8_t* reset, float* out,
                                        int32_t B, int32_t T, int32_t A, int32_t ld, int32_t K, int32_t h, float m) {
@@ -366,25 +289,24 @@ int32_t gn_program_add_action_ensemble(gn_program* p, const void* chunk, int32_t
   GN_REQUIRE(chunk && state && steps && reset && out && B > 0 && T > 0 && A > 0 && ld >= A && h >= 1 && h <= T && (K == 1 || K >= (T + h - 1) / h) && m >= 0.f &&
                  gn_action_ensemble_state_bytes(B, T, A, K) > 0,
              "gn_program_add_action_ensemble: bad arguments (B %d, T %d, A %d, ld %d, K %d, h %d, m %g)", B, T, A, ld, K, h, (double)m);
-  const int32_t rc = push_generic(p, OP_ACTION_ENSEMBLE, chunk, steps, reset, out, K, h, B, T, A, ld, m, 0.f);
-  if (rc == GN_OK) { p->ops.back().g.m[0] = (int64_t)(uintptr_t)state; p->ops.back().g.m[1] = chunk_f16 ? 1 : 0; }
-  return rc;
+  if (chunk_f16) return RECORD(gn_action_ensemble_f16, chunk, state, steps, reset, out, B, T, A, ld, K, h, m);
+  return RECORD(gn_action_ensemble, (const float*)chunk, state, steps, reset, out, B, T, A, ld, K, h, m);
 }
-int32_t gn_program_add_fork(gn_program* p) { return push_generic(p, OP_FORK, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0.f, 0.f); }
-int32_t gn_program_add_main(gn_program* p) { return push_generic(p, OP_MAIN, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0.f, 0.f); }
-int32_t gn_program_add_join(gn_program* p) { return push_generic(p, OP_JOIN, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0.f, 0.f); }
+int32_t gn_program_add_fork(gn_program* p) { return push(p, __func__, make_op(Kind::Fork, "fork")); }
+int32_t gn_program_add_main(gn_program* p) { return push(p, __func__, make_op(Kind::Main, "main")); }
+int32_t gn_program_add_join(gn_program* p) { return push(p, __func__, make_op(Kind::Join, "join")); }
 int64_t gn_program_num_ops(const gn_program* p) { return p ? (int64_t)p->ops.size() : 0; }
 
 // in-call tile tuning (genima_amd/incall_tune.py): read back a recorded gn_gemm op, and replace its tile / K split (+ the workspace its
 // split-K partial sums use).  A tile never changes the summation order along K; a K split does (as documented on gn_gemm_desc).
 int32_t gn_program_get_gemm(const gn_program* p, int64_t op, gn_gemm_desc* out) {
   GN_REQUIRE(p && out && op >= 0 && op < (int64_t)p->ops.size(), "gn_program_get_gemm: bad argument");
-  if (p->ops[(size_t)op].type != OP_GEMM) return GN_ERR_INVALID;  // (no error text: callers probe every op)
+  if (p->ops[(size_t)op].kind != Kind::Gemm) return GN_ERR_INVALID;  // (no error text: callers probe every op)
   *out = p->ops[(size_t)op].gemm;
   return GN_OK;
 }
 int32_t gn_program_set_gemm_plan(gn_program* p, int64_t op, int32_t tile, int32_t splitk, void* workspace) {
-  GN_REQUIRE(p && op >= 0 && op < (int64_t)p->ops.size() && p->ops[(size_t)op].type == OP_GEMM, "gn_program_set_gemm_plan: op %ld is not a gn_gemm", (long)op);
+  GN_REQUIRE(p && op >= 0 && op < (int64_t)p->ops.size() && p->ops[(size_t)op].kind == Kind::Gemm, "gn_program_set_gemm_plan: op %ld is not a gn_gemm", (long)op);
   GN_REQUIRE(!p->exec, "gn_program_set_gemm_plan: the program is captured (re-capture after tuning)");
   GN_REQUIRE(tile >= 0 && tile <= GN_NUM_GEMM_TILES && splitk >= 0, "gn_program_set_gemm_plan: tile %d (0 = heuristic, 1 .. %d) / splitk %d out of range", tile, GN_NUM_GEMM_TILES, splitk);
   gn_gemm_desc d = p->ops[(size_t)op].gemm;  // validated on a copy: a refused plan leaves the recorded op as it was
@@ -407,14 +329,14 @@ int32_t gn_program_set_sink(gn_program* p, int64_t op, int32_t index, const gn_s
   GN_REQUIRE(p && sink && op >= 0 && op < (int64_t)p->ops.size(), "gn_program_set_sink: bad argument");
   GN_REQUIRE(!p->exec, "gn_program_set_sink: the program is captured");
   Op& o = p->ops[(size_t)op];
-  if (o.type == OP_GEMM) {
+  if (o.kind == Kind::Gemm) {
     GN_REQUIRE(index == 0 && !o.gemm.sink.stats, "gn_program_set_sink: a gn_gemm op has one output and takes one sink");
     GN_REQUIRE(o.gemm.out_mode == GN_OUT_ROWMAJOR && !o.gemm.out2 && o.gemm.act != GN_ACT_GEGLU && !o.gemm.fp8 && (o.gemm.batch <= 1 || o.gemm.up_phases),
                "gn_program_set_sink: this gn_gemm does not write a plain row-major f16 tensor");
     o.gemm.sink = *sink;
     return GN_OK;
   }
-  if (o.type == OP_ADD_MULTI) {
+  if (o.kind == Kind::AddMulti) {
     GN_REQUIRE(index >= 0 && index < o.addm.count && !o.addm.sink[index].stats && channels > 0 && channels % 8 == 0 && o.addm.n[index] % channels == 0,
                "gn_program_set_sink: bad gn_add_multi tensor index / channel count");
     for (int i = 0; i < o.addm.count; ++i)
@@ -428,7 +350,7 @@ int32_t gn_program_set_sink(gn_program* p, int64_t op, int32_t index, const gn_s
   return GN_ERR_INVALID;
 }
 int32_t gn_program_set_norm_out(gn_program* p, int64_t op, const gn_norm_out* n) {
-  GN_REQUIRE(p && n && n->y && op >= 0 && op < (int64_t)p->ops.size() && p->ops[(size_t)op].type == OP_GEMM, "gn_program_set_norm_out: op %ld is not a gn_gemm", (long)op);
+  GN_REQUIRE(p && n && n->y && op >= 0 && op < (int64_t)p->ops.size() && p->ops[(size_t)op].kind == Kind::Gemm, "gn_program_set_norm_out: op %ld is not a gn_gemm", (long)op);
   GN_REQUIRE(!p->exec, "gn_program_set_norm_out: the program is captured");
   gn_gemm_desc d = p->ops[(size_t)op].gemm;
   GN_REQUIRE(!d.norm_out.y, "gn_program_set_norm_out: this gn_gemm already normalises its output");
@@ -438,10 +360,10 @@ int32_t gn_program_set_norm_out(gn_program* p, int64_t op, const gn_norm_out* n)
   return GN_OK;
 }
 int32_t gn_program_set_memset_bytes(gn_program* p, int64_t op, int64_t bytes) {
-  GN_REQUIRE(p && op >= 0 && op < (int64_t)p->ops.size() && p->ops[(size_t)op].type == OP_MEMSET && bytes > 0 && bytes <= p->ops[(size_t)op].g.n0,
+  GN_REQUIRE(p && op >= 0 && op < (int64_t)p->ops.size() && p->ops[(size_t)op].kind == Kind::Memset && bytes > 0 && bytes <= p->ops[(size_t)op].ms.bytes,
              "gn_program_set_memset_bytes: op %ld is not a memset of at least %ld bytes", (long)op, (long)bytes);
   GN_REQUIRE(!p->exec, "gn_program_set_memset_bytes: the program is captured");
-  p->ops[(size_t)op].g.n0 = bytes;
+  p->ops[(size_t)op].ms.bytes = bytes;
   return GN_OK;
 }
 int64_t gn_desc_sizeof(int32_t which) {
@@ -462,7 +384,10 @@ int64_t gn_desc_sizeof(int32_t which) {
 }
 int32_t gn_program_add_memset(gn_program* p, void* ptr, int64_t bytes) {
   GN_REQUIRE(ptr && bytes > 0, "gn_program_add_memset: null / empty");
-  return push_generic(p, OP_MEMSET, nullptr, nullptr, nullptr, ptr, bytes, 0, 0, 0, 0, 0, 0.f, 0.f);
+  Op op = make_op(Kind::Memset, "gn_memset");
+  op.ms.ptr = ptr;
+  op.ms.bytes = bytes;
+  return push(p, __func__, std::move(op));
 }
 
 static uint64_t seg_mask(const gn_program* p) { return p->segs.size() >= 64 ? ~0ull : ((1ull << p->segs.size()) - 1ull); }
@@ -492,16 +417,16 @@ int32_t gn_program_run(gn_program* p, int64_t first, int64_t last) {
   int32_t rc = GN_OK;
   for (int64_t i = first; i < last && rc == GN_OK; ++i) {
     const Op& op = p->ops[(size_t)i];
-    if (op.type == OP_FORK || op.type == OP_MAIN || op.type == OP_JOIN) {
+    if (op.kind == Kind::Fork || op.kind == Kind::Main || op.kind == Kind::Join) {
       if (!two_streams) continue;
-      if (op.type == OP_FORK) {
+      if (op.kind == Kind::Fork) {
         if (guarded) {
           // a side section whose every kernel is skipped is not opened: an empty branch would hand the next join the same predecessors twice
           // (the join in front of it already ordered the side stream's work), and there is nothing to overlap
           bool any = false;
           for (int64_t j = i + 1; j < last && !any; ++j) {
-            const int t = p->ops[(size_t)j].type;
-            if (t == OP_FORK || t == OP_MAIN || t == OP_JOIN) break;
+            const Kind t = p->ops[(size_t)j].kind;
+            if (t == Kind::Fork || t == Kind::Main || t == Kind::Join) break;
             any = !op_skipped(p, j);
           }
           if (!any) continue;
@@ -513,7 +438,7 @@ int32_t gn_program_run(gn_program* p, int64_t first, int64_t last) {
         }
         p->ctx->stream = p->side;
         forked = true;
-      } else if (op.type == OP_MAIN) {
+      } else if (op.kind == Kind::Main) {
         p->ctx->stream = main_stream;
       } else if (forked) {
         p->ctx->stream = main_stream;
@@ -530,7 +455,7 @@ int32_t gn_program_run(gn_program* p, int64_t first, int64_t last) {
     if (rc != GN_OK) {
       char tmp[900];
       snprintf(tmp, sizeof(tmp), "%s", g_err);
-      gn_set_error("op %ld (type %d): %s", (long)i, op.type, tmp);
+      gn_set_error("op %ld (%s): %s", (long)i, op.name, tmp);
     }
   }
   p->ctx->stream = main_stream;

@@ -189,8 +189,8 @@ class Engine:
         if self.gn_bridge:
             self._stats_arena = torch.zeros(self.STATS_ARENA_BYTES // 8, dtype=torch.int64, device=self.device)
             self._memset_op = self.num_ops
-            check(self.lib.gn_program_add_memset(self._prog, _ptr(self._stats_arena), self.STATS_ARENA_BYTES), "gn_program_add_memset")
-            self.meta.append(dict(kind="memset", flops=0.0, bytes=float(self.STATS_ARENA_BYTES), shape=()))
+            self._emit(None, "gn_program_add_memset", (_ptr(self._stats_arena), self.STATS_ARENA_BYTES), (),
+                       dict(kind="memset", flops=0.0, bytes=float(self.STATS_ARENA_BYTES), shape=()))
 
     # ------------------------------------------------------------------------------------------------ housekeeping
     def __del__(self):
@@ -372,6 +372,20 @@ class Engine:
         if self.record:
             self._keep.extend(t for t in ts if t is not None)
 
+    def _emit(self, eager, rec: str, args, keep, meta, rec_args=None):
+        """The one place that forks on ``self.record``.  Recording: append ``<rec>(program, *args)`` (``rec_args`` where the recording
+        entry takes other arguments), keep the tensors of ``keep`` alive and note the op's ``meta`` -- a dict, or a callable making it, so that
+        eager calls do not build it.  Eager: launch ``<eager>(context, *args)`` now (``eager``: a symbol name, a callable that launches, or
+        None for the stream markers, which do nothing)."""
+        if self.record:
+            check(getattr(self.lib, rec)(self._prog, *(args if rec_args is None else rec_args)), rec)
+            self._keepalive(*keep)
+            self.meta.append(meta() if callable(meta) else meta)
+        elif callable(eager):
+            eager()
+        elif eager is not None:
+            check(getattr(self.lib, eager)(self._ctx, *args), eager)
+
     @property
     def num_ops(self) -> int:
         return int(self.lib.gn_program_num_ops(self._prog)) if self.record else 0
@@ -551,25 +565,24 @@ class Engine:
         if ws_bytes > 0:
             ws = self._workspace(ws_bytes)
             d.workspace = ws.data_ptr()
-        if self.record:
-            if (d.out_mode == OUT_ROWMAJOR and not d.out2 and d.act != ACT_GEGLU and not d.fp8 and (d.batch <= 1 or d.up_phases)
-                    and not d.out_row_width or d.up_phases):
-                # the op that wrote this tensor: a GroupNorm recorded later may move into its reduce (norm_out) or take its statistics (bridge)
-                # (a phase conv launch writes the whole upsampled tensor: 4 phases x M rows)
-                if d.up_phases or int(d.ldo) == int(d.N):  # a dense tensor (a slice of a wider buffer is not what a GroupNorm reads)
-                    self._writer[int(d.out)] = _Writer(self.num_ops, 0, int(d.M) * int(d.N) * (4 if d.up_phases else 1), 4 if d.up_phases else 1, gemm=True)
-            check(self.lib.gn_program_add_gemm(self._prog, C.byref(d)), "gn_program_add_gemm")
-            self._keepalive(*keep, ws)
+        if self.record and (d.out_mode == OUT_ROWMAJOR and not d.out2 and d.act != ACT_GEGLU and not d.fp8 and (d.batch <= 1 or d.up_phases)
+                            and not d.out_row_width or d.up_phases):
+            # the op that wrote this tensor: a GroupNorm recorded later may move into its reduce (norm_out) or take its statistics (bridge)
+            # (a phase conv launch writes the whole upsampled tensor: 4 phases x M rows)
+            if d.up_phases or int(d.ldo) == int(d.N):  # a dense tensor (a slice of a wider buffer is not what a GroupNorm reads)
+                self._writer[int(d.out)] = _Writer(self.num_ops, 0, int(d.M) * int(d.N) * (4 if d.up_phases else 1), 4 if d.up_phases else 1, gemm=True)
+
+        def meta():
             kind = (f"conv{d.KH}x{d.KW}" if d.conv else "linear")
             n_out = d.N // 2 if d.act == ACT_GEGLU else d.N
             # a phase conv of an upsampling 3x3 conv (KH = 2, strided output view) does 4 / 9 of the reference algorithm's multiply-adds
             ref_scale = 9.0 / 4.0 if (d.conv and d.KH == 2 and d.out_row_width) else 1.0
             nph = 4.0 if d.up_phases else 1.0  # the four phases of an upsampling conv in one launch
-            self.meta.append(dict(kind=kind, flops=nph * 2.0 * d.M * d.N * d.K,
-                                  bytes=2.0 * (d.M * d.K / max(1, d.KH * d.KW if d.conv else 1) + nph * d.N * d.K + nph * d.M * n_out),
-                                  shape=(int(d.M), int(d.N), int(d.K)), ref_flops=nph * 2.0 * d.M * d.N * d.K * ref_scale))
-        else:
-            self.run_gemm(d)
+            return dict(kind=kind, flops=nph * 2.0 * d.M * d.N * d.K,
+                        bytes=2.0 * (d.M * d.K / max(1, d.KH * d.KW if d.conv else 1) + nph * d.N * d.K + nph * d.M * n_out),
+                        shape=(int(d.M), int(d.N), int(d.K)), ref_flops=nph * 2.0 * d.M * d.N * d.K * ref_scale)
+
+        self._emit(lambda: self.run_gemm(d), "gn_program_add_gemm", (C.byref(d),), (*keep, ws), meta)
 
     def run_gemm(self, d: GemmDesc):
         """Eager launch; with ``self.gemm_log`` set (a list) each launch is bracketed by HIP events for the per-shape tables."""
@@ -614,25 +627,21 @@ class Engine:
         return cur
 
     # ---- two-stream sections of a recorded program (gn_program_add_fork / main / join); no-ops when executing eagerly
+    def _marker(self, op: str, on_side: bool):
+        self._emit(None, "gn_program_add_" + op, (), (), dict(kind="stream", op=op, flops=0.0, bytes=0.0, shape=()))  # meta stays index-aligned with the op list
+        if self.record:
+            self._on_side = on_side
+
     def fork(self):
         """Ops recorded from here run on the program's side stream (after everything recorded so far)."""
-        if self.record:
-            check(self.lib.gn_program_add_fork(self._prog), "gn_program_add_fork")
-            self.meta.append(dict(kind="stream", op="fork", flops=0.0, bytes=0.0, shape=()))  # meta stays index-aligned with the op list
-            self._on_side = True
+        self._marker("fork", True)
 
     def main(self):
         """Back to the main stream; the side stream keeps running concurrently until join()."""
-        if self.record:
-            check(self.lib.gn_program_add_main(self._prog), "gn_program_add_main")
-            self.meta.append(dict(kind="stream", op="main", flops=0.0, bytes=0.0, shape=()))
-            self._on_side = False
+        self._marker("main", False)
 
     def join(self):
-        if self.record:
-            check(self.lib.gn_program_add_join(self._prog), "gn_program_add_join")
-            self.meta.append(dict(kind="stream", op="join", flops=0.0, bytes=0.0, shape=()))
-            self._on_side = False
+        self._marker("join", False)
 
     # ---- the GroupNorm bridge: producer statistics for a GroupNorm over x (| x2) ---------------------------------------------------------
     def bridge_stats(self, x: torch.Tensor, x2: Optional[torch.Tensor], groups: int) -> Optional[torch.Tensor]:
@@ -784,12 +793,8 @@ class Engine:
         return bool(self.lib.gn_tblock_supported(TBLOCK_TAIL, int(M), int(C)))
 
     def _tblock(self, d: TBlockDesc, keep, flops: float, nbytes: float):
-        if self.record:
-            check(self.lib.gn_program_add_tblock(self._prog, C.byref(d)), "gn_program_add_tblock")
-            self._keepalive(*keep)
-            self.meta.append(dict(kind="tblock", flops=flops, bytes=nbytes, shape=(int(d.M), int(d.C), int(d.kind)), ref_flops=flops))
-        else:
-            check(self.lib.gn_tblock(self._ctx, C.byref(d)), "gn_tblock")
+        self._emit("gn_tblock", "gn_program_add_tblock", (C.byref(d),), keep,
+                   lambda: dict(kind="tblock", flops=flops, bytes=nbytes, shape=(int(d.M), int(d.C), int(d.kind)), ref_flops=flops))
 
     def tblock_front(self, x: torch.Tensor, scsh: torch.Tensor, tape: torch.Tensor, rows_per_batch: int, *, ln_eps: float = 1e-5,
                      name: Optional[str] = None):
@@ -1050,13 +1055,9 @@ class Engine:
             dr = attn_dropout_desc(float(dropout[0]), int(dropout[1]))
             check(self.lib.gn_attention_dropout_fwd(self._ctx, C.byref(d), C.byref(dr)), "gn_attention_dropout_fwd")
             return out
-        if self.record:
-            check(self.lib.gn_program_add_attention(self._prog, C.byref(d)), "gn_program_add_attention")
-            self._keepalive(q, k, vt, out)
-            fl = 4.0 * B * heads * Nq * Nk * D * (0.5 if causal else 1.0)
-            self.meta.append(dict(kind="attention", flops=fl, bytes=2.0 * B * Cq * (2 * Nq + 2 * Nk), shape=(B, heads, Nq, Nk, D)))
-        else:
-            check(self.lib.gn_attention_fwd(self._ctx, C.byref(d)), "gn_attention_fwd")
+        self._emit("gn_attention_fwd", "gn_program_add_attention", (C.byref(d),), (q, k, vt, out),
+                   lambda: dict(kind="attention", flops=4.0 * B * heads * Nq * Nk * D * (0.5 if causal else 1.0),
+                                bytes=2.0 * B * Cq * (2 * Nq + 2 * Nk), shape=(B, heads, Nq, Nk, D)))
         return out
 
     def attention_fp8(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, *, out: Optional[torch.Tensor] = None,
@@ -1118,12 +1119,8 @@ class Engine:
             st = self.bridge_stats(x, x2, groups)
         if st is not None:  # the producers of x (| x2) leave the statistics: ONE coalesced apply launch
             d.stats_in, d.stats_replicas = st.data_ptr(), int(st.shape[0])
-        if self.record:
-            check(self.lib.gn_program_add_groupnorm(self._prog, C.byref(d)), "gn_program_add_groupnorm")
-            self._keepalive(x, x2, gamma, beta, out, ws)
-            self.meta.append(dict(kind="groupnorm", flops=0.0, bytes=2.0 * 2 * B * HW * (C1 + C2), shape=(B, HW, C1 + C2) + (("st",) if st is not None else ())))
-        else:
-            check(self.lib.gn_groupnorm_fwd(self._ctx, C.byref(d)), "gn_groupnorm_fwd")
+        self._emit("gn_groupnorm_fwd", "gn_program_add_groupnorm", (C.byref(d),), (x, x2, gamma, beta, out, ws),
+                   lambda: dict(kind="groupnorm", flops=0.0, bytes=2.0 * 2 * B * HW * (C1 + C2), shape=(B, HW, C1 + C2) + (("st",) if st is not None else ())))
         return out
 
     def _norm_out(self, x, gamma, beta, groups, eps, act, out, B, HW, Cc) -> bool:
@@ -1164,12 +1161,8 @@ class Engine:
         d.B, d.HW, d.C1, d.C2, d.groups, d.act, d.eps = B, HW, C1, C2, groups, ACT_NONE, eps
         ws = self._workspace(int(self.lib.gn_groupnorm_workspace_bytes(C.byref(d))))
         d.workspace = ws.data_ptr()
-        if self.record:
-            check(self.lib.gn_program_add_groupnorm(self._prog, C.byref(d)), "gn_program_add_groupnorm")
-            self._keepalive(x, x2, gamma, beta, scsh, ws)
-            self.meta.append(dict(kind="groupnorm", flops=0.0, bytes=2.0 * B * HW * Cc, shape=(B, HW, Cc, 0)))
-        else:
-            check(self.lib.gn_groupnorm_fwd(self._ctx, C.byref(d)), "gn_groupnorm_fwd")
+        self._emit("gn_groupnorm_fwd", "gn_program_add_groupnorm", (C.byref(d),), (x, x2, gamma, beta, scsh, ws),
+                   lambda: dict(kind="groupnorm", flops=0.0, bytes=2.0 * B * HW * Cc, shape=(B, HW, Cc, 0)))
         return scsh
 
     def conv2d_gn_supported(self, x: torch.Tensor, cout: int) -> bool:
@@ -1192,13 +1185,9 @@ class Engine:
         d.x, d.scsh, d.w, d.bias, d.residual, d.out = _ptr(x), _ptr(scsh), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out)
         d.ldr, d.ldo = (residual.stride(-2) if residual is not None else 0), out.stride(-2)
         d.B, d.H, d.W, d.Cin, d.Cout, d.act = B, H, W, Cin, N, act
-        if self.record:
-            check(self.lib.gn_program_add_conv3x3_gn(self._prog, C.byref(d)), "gn_program_add_conv3x3_gn")
-            self._keepalive(x, scsh, w, bias, residual, out)
-            M, K = B * H * W, 9 * Cin
-            self.meta.append(dict(kind="conv3x3", flops=2.0 * M * N * K, bytes=2.0 * (M * Cin + N * K + M * N), shape=(M, N, K), ref_flops=2.0 * M * N * K))
-        else:
-            check(self.lib.gn_conv3x3_gn(self._ctx, C.byref(d)), "gn_conv3x3_gn")
+        M, K = B * H * W, 9 * Cin
+        self._emit("gn_conv3x3_gn", "gn_program_add_conv3x3_gn", (C.byref(d),), (x, scsh, w, bias, residual, out),
+                   lambda: dict(kind="conv3x3", flops=2.0 * M * N * K, bytes=2.0 * (M * Cin + N * K + M * N), shape=(M, N, K), ref_flops=2.0 * M * N * K))
         return out
 
     def conv2d_patch_route(self, x: torch.Tensor, cout: int, x2: Optional[torch.Tensor] = None, groups: int = 32) -> int:
@@ -1258,14 +1247,10 @@ class Engine:
         d.ldr, d.ldo = (residual.stride(-2) if residual is not None else 0), out.stride(-2)
         d.ldshift = (ldshift or shift.stride(0)) if shift is not None else 0
         d.B, d.H, d.W, d.C1, d.C2, d.Cout, d.act = B, H, W, C1, C2, N, act
-        if self.record:
-            check(self.lib.gn_program_add_conv3x3_patch(self._prog, C.byref(d)), "gn_program_add_conv3x3_patch")
-            self._keepalive(x, x2, scsh, w, bias, shift, residual, out)
-            M, K = B * H * W, 9 * (C1 + C2)  # (the rows of the conv it replaces: same kind, shape and formulas as conv2d's)
-            self.meta.append(dict(kind="conv3x3", flops=2.0 * M * N * K, bytes=2.0 * (M * (C1 + C2) + N * K + M * N), shape=(M, N, K),
-                                  ref_flops=2.0 * M * N * K, route="patch"))
-        else:
-            check(self.lib.gn_conv3x3_patch(self._ctx, C.byref(d)), "gn_conv3x3_patch")
+        M, K = B * H * W, 9 * (C1 + C2)  # (the rows of the conv it replaces: same kind, shape and formulas as conv2d's)
+        self._emit("gn_conv3x3_patch", "gn_program_add_conv3x3_patch", (C.byref(d),), (x, x2, scsh, w, bias, shift, residual, out),
+                   lambda: dict(kind="conv3x3", flops=2.0 * M * N * K, bytes=2.0 * (M * (C1 + C2) + N * K + M * N), shape=(M, N, K),
+                                ref_flops=2.0 * M * N * K, route="patch"))
         return out
 
     def tiny_block_supported(self, x: torch.Tensor) -> bool:
@@ -1284,15 +1269,10 @@ class Engine:
             self._wrote(out)
         wp = (C.c_void_p * 3)(*[_ptr(w) for w in ws])
         bp = (C.c_void_p * 3)(*[_ptr(b) for b in biases])
-        args = (_ptr(x), wp, bp, _ptr(out), B, H, W, Cc)
-        if self.record:
-            check(self.lib.gn_program_add_tiny_block(self._prog, *args), "gn_program_add_tiny_block")
-            self._keepalive(x, out, *ws, *biases)
-            M, K = B * H * W, 9 * Cc
-            self.meta.append(dict(kind="tiny_block", flops=3 * 2.0 * M * Cc * K, bytes=2.0 * (2 * M * Cc + 3 * Cc * K), shape=(M, Cc, K),
-                                  ref_flops=3 * 2.0 * M * Cc * K))
-        else:
-            check(self.lib.gn_tiny_block(self._ctx, *args), "gn_tiny_block")
+        M, K = B * H * W, 9 * Cc
+        self._emit("gn_tiny_block", "gn_program_add_tiny_block", (_ptr(x), wp, bp, _ptr(out), B, H, W, Cc), (x, out, *ws, *biases),
+                   lambda: dict(kind="tiny_block", flops=3 * 2.0 * M * Cc * K, bytes=2.0 * (2 * M * Cc + 3 * Cc * K), shape=(M, Cc, K),
+                                ref_flops=3 * 2.0 * M * Cc * K))
         return out
 
     def layernorm(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, *,
@@ -1303,26 +1283,18 @@ class Engine:
             out = self.buf(name, x.shape)
         else:
             self._wrote(out)
-        args = (_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), M, Cc, eps)
-        if self.record:
-            check(self.lib.gn_program_add_layernorm(self._prog, *args), "gn_program_add_layernorm")
-            self._keepalive(x, gamma, beta, out)
-            self.meta.append(dict(kind="layernorm", flops=0.0, bytes=2.0 * 2 * M * Cc, shape=(M, Cc)))
-        else:
-            check(self.lib.gn_layernorm_fwd(self._ctx, *args), "gn_layernorm_fwd")
+        self._emit("gn_layernorm_fwd", "gn_program_add_layernorm", (_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), M, Cc, eps), (x, gamma, beta, out),
+                   lambda: dict(kind="layernorm", flops=0.0, bytes=2.0 * 2 * M * Cc, shape=(M, Cc)))
         return out
 
     # ------------------------------------------------------------------------------------------------ small ops
     def _small(self, fn_name: str, keep, *args, nbytes: Optional[float] = None):
         """``nbytes``: the bytes the op actually touches when that is not the size of its operands (gathers read a few rows of a table)."""
-        if self.record:
-            check(getattr(self.lib, "gn_program_add_" + fn_name)(self._prog, *args), "gn_program_add_" + fn_name)
-            self._keepalive(*keep)
-            if nbytes is None:
-                nbytes = float(sum(t.numel() * t.element_size() for t in keep if t is not None))
-            self.meta.append(dict(kind=fn_name, flops=0.0, bytes=float(nbytes), shape=()))
-        else:
-            check(getattr(self.lib, "gn_" + fn_name)(self._ctx, *args), "gn_" + fn_name)
+        def meta():
+            nb = float(sum(t.numel() * t.element_size() for t in keep if t is not None)) if nbytes is None else float(nbytes)
+            return dict(kind=fn_name, flops=0.0, bytes=nb, shape=())
+
+        self._emit("gn_" + fn_name, "gn_program_add_" + fn_name, args, keep, meta)
 
     def timestep_embedding(self, t: torch.Tensor, dim: int, flip_sin_to_cos=True, freq_shift=0.0, *, name=None):
         """t: f32 [B] device tensor -> f16 [B, dim]."""
@@ -1698,12 +1670,9 @@ class Engine:
             self._wrote(out)
         self._wrote(state)
         args = (_ptr(state), _ptr(steps), _ptr(reset), _ptr(out), B, T, A, ld, int(K), int(h), float(m))
-        f16 = chunk.dtype == F16
-        if self.record:
-            check(self.lib.gn_program_add_action_ensemble(self._prog, _ptr(chunk), int(f16), *args), "gn_program_add_action_ensemble")
-            self._keepalive(chunk, state, steps, reset, out)
-            self.meta.append(dict(kind="action_ensemble", flops=0.0, bytes=float(4 * B * A * (T + K * h + h) + chunk.element_size() * B * T * A), shape=()))
-        else:
-            fn = self.lib.gn_action_ensemble_f16 if f16 else self.lib.gn_action_ensemble
-            check(fn(self._ctx, _ptr(chunk), *args), "gn_action_ensemble")
+        f16 = chunk.dtype == F16  # (the recording entry takes the chunk's type as an argument and binds the matching launch)
+        self._emit("gn_action_ensemble_f16" if f16 else "gn_action_ensemble", "gn_program_add_action_ensemble", (_ptr(chunk), *args),
+                   (chunk, state, steps, reset, out),
+                   lambda: dict(kind="action_ensemble", flops=0.0, bytes=float(4 * B * A * (T + K * h + h) + chunk.element_size() * B * T * A), shape=()),
+                   rec_args=(_ptr(chunk), int(f16), *args))
         return out

@@ -36,7 +36,8 @@ def test_loader_binds_and_reports_version():
     assert ctypes.sizeof(_lib.NormOut) == 40  # 3 pointers + float + 3 int32
     assert ctypes.sizeof(_lib.GemmDesc) == base + 32 + 56 + 40  # the GroupNorm bridge's sink + norm_in, the reduce-side norm_out
     # ... and the compiled structs agree with the binding's (the loader refuses a mismatch)
-    for which, cls in enumerate((_lib.GemmDesc, _lib.AttnDesc, _lib.GroupNormDesc, _lib.TBlockDesc, _lib.ConvGnDesc, _lib.StatsSink, _lib.NormIn, _lib.NormOut)):
+    assert len(_lib.DESC_CLASSES) == 11 and lib.gn_desc_sizeof(len(_lib.DESC_CLASSES)) == -1  # the loader's list covers every index the library knows
+    for which, cls in enumerate(_lib.DESC_CLASSES):
         assert int(lib.gn_desc_sizeof(which)) == ctypes.sizeof(cls), cls.__name__
 
 

@@ -46,6 +46,80 @@ def test_segment_calls_without_a_device():
     assert lib.gn_program_destroy(prog) == 0
 
 
+def test_recording_without_a_device():
+    """Recording is host code too: every ``gn_program_add_*`` appends exactly one op (stream markers included), and what it refuses at
+    record time it refuses by name and appends nothing.  Pointers are stored, never read, so zeroed host memory stands in for the context
+    and the tensors; nothing here replays the program."""
+    lib = _lib.load()
+    mem = ctypes.create_string_buffer(4096)
+    base = (ctypes.addressof(mem) + 63) // 64 * 64
+    ctx, buf = ctypes.c_void_p(base), ctypes.c_void_p(base + 1024)
+    prog = ctypes.c_void_p()
+    assert lib.gn_program_create(ctx, ctypes.byref(prog)) == 0
+    three = (ctypes.c_void_p * 3)(buf, buf, buf)
+    four = (ctypes.c_int64 * 4)(1, 2, 3, 4)
+    ptrs, lens = (ctypes.c_void_p * 2)(buf, buf), (ctypes.c_int64 * 2)(8, 16)
+    gemm = _lib.GemmDesc(M=123, N=40, K=64)
+    byref = ctypes.byref
+    ops = {  # entry point -> arguments behind the program
+        "gemm": (byref(gemm),), "attention": (byref(_lib.AttnDesc()),), "groupnorm": (byref(_lib.GroupNormDesc()),),
+        "tblock": (byref(_lib.TBlockDesc()),), "conv3x3_gn": (byref(_lib.ConvGnDesc()),), "conv3x3_patch": (byref(_lib.ConvPatchDesc()),),
+        "tiny_block": (buf, three, three, buf, 1, 5, 7, 64), "layernorm": (buf, buf, buf, buf, 5, 24, 1e-5),
+        "timestep_embedding": (buf, buf, 3, 16, 1, 0.5), "scale_pad": (buf, buf, 5, 6, 16, 0.5),
+        "scale_cat_pad": (buf, buf, buf, 7, 5, 12, 3, 20, 16, 0.5, 2.0), "euler_step": (buf, buf, 9, 4, 8, 2.5, 1.25),
+        "image_f16_to_u8": (buf, buf, 30, 8), "image_u8_to_f16": (buf, buf, 30, 8, 2.0, -1.0),
+        "image_normalize_u8": (buf, buf, 30, 8, 1.0, 2.0, 3.0, 4.0, 5.0, 6.0), "add": (buf, buf, buf, 104),
+        "add_multi": (ptrs, ptrs, ptrs, lens, 2), "add_noise": (buf, buf, buf, buf, buf, 3, 40), "act": (buf, buf, 48, 2),
+        "film": (buf, buf, buf, buf, 48, 3, 6, 16, 1), "embedding": (buf, buf, buf, buf, 2, 3, 8), "softmax_rows": (buf, 5, 16, 24, 0.7),
+        "maxpool3x3s2": (buf, buf, 2, 5, 7, 8), "gather_rows": (buf, buf, buf, 2, 3, 8), "copy4d": (buf, buf, four, four, four, 8),
+        "argmax_rows_i32": (buf, buf, 5, 7), "action_ensemble": (buf, 1, buf, buf, buf, buf, 2, 6, 5, 8, 4, 3, 0.02),
+        "memset": (buf, 256), "fork": (), "main": (), "join": (),
+    }
+    assert {"gn_program_add_" + n for n in ops} == {n for n in _lib.SIGNATURES if n.startswith("gn_program_add_")}, "one of each kind"
+    index = {}
+    for n, (name, args) in enumerate(ops.items()):
+        fn = getattr(lib, "gn_program_add_" + name)
+        assert fn(prog, *args) == 0, (name, lib.gn_last_error())
+        assert lib.gn_program_num_ops(prog) == n + 1, name
+        index[name] = n
+    count = len(ops)
+
+    def refused(name, *args, program=prog):
+        assert getattr(lib, "gn_program_add_" + name)(program, *args) != 0, (name, args)
+        assert ("gn_program_add_" + name).encode() in lib.gn_last_error(), (name, lib.gn_last_error())
+        assert lib.gn_program_num_ops(prog) == count, f"{name}: a refused op is not recorded"
+
+    for name, args in ops.items():
+        refused(name, *args, program=None)
+    for name in ("gemm", "attention", "groupnorm", "tblock", "conv3x3_gn", "conv3x3_patch"):
+        refused(name, None)
+    refused("tiny_block", buf, None, three, buf, 1, 5, 7, 64)
+    refused("tiny_block", buf, three, None, buf, 1, 5, 7, 64)
+    refused("tiny_block", buf, three, three, buf, 1, 5, 7, 32)   # unsupported channel count
+    refused("tiny_block", buf, three, three, buf, 0, 5, 7, 64)
+    refused("tiny_block", None, three, three, buf, 1, 5, 7, 64)
+    for bad in (dict(h=0), dict(h=7), dict(K=0), dict(ld=4), dict(m=-1.0), dict(B=0), dict(state=None)):  # h > T, K < ceil(T / h), ld < A
+        a = dict(dict(state=buf, B=2, T=6, A=5, ld=8, K=4, h=3, m=0.02), **bad)
+        refused("action_ensemble", buf, 0, a["state"], buf, buf, buf, a["B"], a["T"], a["A"], a["ld"], a["K"], a["h"], a["m"])
+    for arrays in ((None, four, four), (four, None, four), (four, four, None)):
+        refused("copy4d", buf, buf, *arrays, 8)
+    refused("add_multi", ptrs, ptrs, ptrs, lens, 0)
+    refused("add_multi", ptrs, ptrs, ptrs, lens, 17)
+    refused("add_multi", None, ptrs, ptrs, lens, 2)
+    refused("memset", None, 256)
+    refused("memset", buf, 0)
+
+    # the payloads that are read and rewritten after recording are where they were put
+    back = _lib.GemmDesc()
+    assert lib.gn_program_get_gemm(prog, index["gemm"], byref(back)) == 0 and (back.M, back.N, back.K) == (123, 40, 64)
+    assert all(lib.gn_program_get_gemm(prog, i, byref(back)) != 0 for name, i in index.items() if name != "gemm")
+    assert lib.gn_program_set_memset_bytes(prog, index["memset"], 128) == 0
+    assert lib.gn_program_set_memset_bytes(prog, index["memset"], 256) != 0, "a memset only shrinks"
+    assert lib.gn_program_set_memset_bytes(prog, index["add"], 8) != 0 and b"gn_program_set_memset_bytes" in lib.gn_last_error()
+    assert lib.gn_program_num_ops(prog) == count
+    assert lib.gn_program_destroy(prog) == 0
+
+
 class _FakeEngine:
     """What pipeline._replay / _ids_changed use of an Engine."""
 
