@@ -248,6 +248,7 @@ SIGNATURES = {
     "gn_replay_gather": (_I32, [_P, C.POINTER(ReplayGatherDesc)]),
     "gn_replay_render": (_I32, [_P, C.POINTER(ReplayRenderDesc)]),
     "gn_openloop_image_metrics": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "gn_openloop_sphere_metrics": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_openloop_action_metrics": (_I32, [_P, _P, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_gather_rows": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_argmax_rows_i32": (_I32, [_P, _P, _P, _I32, _I32]),

@@ -8,6 +8,13 @@
 // hand-off between its four waves, and five 64-bit vector atomics per block add them to the view's row, which the entry point zeroed on the
 // same stream.  Integer addition commutes, so the bits do not depend on the order the blocks arrive in.  No thread leaves before the fold.
 //
+// Sphere kernel.  Grid: x = sphere, y = view, z = sample (only the n_valid scored ones): one workgroup per window, 256 threads striding its
+// at most 256 x 256 pixels (pixel i of the window -> ly = i / w, lx = i - ly * w), byte loads (windows are small and their rows start anywhere).
+// A thread sees at most 256 pixels, so 14 of its 16 sums fit 32 bits, and so does a wave's total of them (<= 64 * 256 * 765 * 255 = 3.2e9);
+// the two second moments (<= 256 * 765 * 130 050 = 2.5e10) are 64-bit per thread and go through the wave sum as a 24-bit low part and a high
+// part.  The four waves' totals meet in LDS as 64-bit values; threads 0 .. 16 add them and store the window's 17 values with plain stores: the
+// workgroup owns its row, so there is no atomic, no memset, and an empty window writes its 17 zeros itself.  No thread leaves before the fold.
+//
 // Action kernel.  One thread per (sample, chunk position): the A - 1 joint terms in index order in f32 (this file is compiled without fma
 // contraction, so a term is one subtraction, one multiplication and one addition, each rounded), then the gripper flag.
 #include "common.h"
@@ -106,6 +113,92 @@ __global__ __launch_bounds__(OL_THREADS) void openloop_image_kernel(const uint8_
   }
 }
 
+constexpr int OL_WIN_MAX = 256;  // a window's longest side
+constexpr int OL_SPH_COLS = 17;
+
+__device__ __forceinline__ int ol_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__global__ __launch_bounds__(OL_THREADS) void openloop_sphere_kernel(const uint8_t* __restrict__ gen, const uint8_t* __restrict__ gt,
+                                                                     const uint8_t* __restrict__ cond, const uint8_t* __restrict__ occupied,
+                                                                     const int32_t* __restrict__ win, unsigned long long* __restrict__ out, int V, int H,
+                                                                     int W, int S, int tiled, int threshold, int row0) {
+  __shared__ unsigned long long part[OL_THREADS / 64][OL_SPH_COLS - 1];
+  const int s = blockIdx.x, v = blockIdx.y, b = blockIdx.z;
+  const long view = (long)b * V + v;
+  const int32_t* wp = win + (view * S + s) * 4;
+  // clamped into the image and to OL_WIN_MAX per side: no address below depends on the table's values being sane
+  const int x0 = ol_clamp(wp[0], 0, W), y0 = ol_clamp(wp[1], 0, H);
+  const int w = ol_clamp(ol_clamp(wp[2], 0, W) - x0, 0, OL_WIN_MAX), h = ol_clamp(ol_clamp(wp[3], 0, H) - y0, 0, OL_WIN_MAX);
+  const uint32_t n = (uint32_t)w * (uint32_t)h;
+  const long vo = view * H;                                                    // first row of the view in gt / cond / occupied
+  const long go = tiled ? ((long)b * 2 * H + (long)(v >> 1) * H) : vo;        // ... and in gen
+  const long gw = tiled ? 2L * W : (long)W, gx = tiled ? (long)(v & 1) * W : 0L;
+  uint32_t a[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // columns 1-3, 5-7, 9-16
+  unsigned long long m2g = 0, m2t = 0;                         // columns 4 and 8
+  for (uint32_t i = threadIdx.x; i < n; i += OL_THREADS) {
+    const uint32_t ly = i / (uint32_t)w, lx = i - ly * (uint32_t)w;
+    const int x = x0 + (int)lx, y = y0 + (int)ly;
+    const long po = (vo + y) * W + x;
+    const ol_gptr8 g8 = (ol_gptr8)(gen + ((go + y) * gw + gx + x) * 3), t8 = (ol_gptr8)(gt + po * 3), c8 = (ol_gptr8)(cond + po * 3);
+    const int g[3] = {g8[0], g8[1], g8[2]}, t[3] = {t8[0], t8[1], t8[2]}, c[3] = {c8[0], c8[1], c8[2]};
+    const uint8_t occ = ((ol_gptr8)occupied)[po];
+    int dg = 0, dt = 0;
+    uint32_t se = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      dg += abs(g[k] - c[k]);
+      dt += abs(t[k] - c[k]);
+      se += (uint32_t)((g[k] - t[k]) * (g[k] - t[k]));
+    }
+    const uint32_t ag = dg > threshold ? (uint32_t)(dg - threshold) : 0u, at = dt > threshold ? (uint32_t)(dt - threshold) : 0u;
+    const uint32_t r2 = lx * lx + ly * ly;
+    a[0] += ag;
+    a[1] += ag * lx;
+    a[2] += ag * ly;
+    m2g += (unsigned long long)(ag * r2);  // <= 765 * 130 050: the product fits 32 bits
+    a[3] += at;
+    a[4] += at * lx;
+    a[5] += at * ly;
+    m2t += (unsigned long long)(at * r2);
+    if (occ) {
+      a[6] += 1;
+      a[7] += se;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        a[8 + k] += (uint32_t)g[k];
+        a[11 + k] += (uint32_t)t[k];
+      }
+    }
+  }
+  const int wave = threadIdx.x >> 6;
+  const bool lead = (threadIdx.x & 63) == 0;
+  // LDS slot = column - 1
+  constexpr int slot[14] = {0, 1, 2, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14, 15};
+#pragma unroll
+  for (int i = 0; i < 14; ++i) {
+    const uint32_t t = ol_wave_sum(a[i]);
+    if (lead) part[wave][slot[i]] = t;
+  }
+  {
+    const uint32_t glo = ol_wave_sum((uint32_t)m2g & 0xFFFFFFu), ghi = ol_wave_sum((uint32_t)(m2g >> 24));
+    const uint32_t tlo = ol_wave_sum((uint32_t)m2t & 0xFFFFFFu), thi = ol_wave_sum((uint32_t)(m2t >> 24));
+    if (lead) {
+      part[wave][3] = (unsigned long long)glo + ((unsigned long long)ghi << 24);
+      part[wave][7] = (unsigned long long)tlo + ((unsigned long long)thi << 24);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < OL_SPH_COLS) {
+    unsigned long long t = n;  // column 0: the window's area
+    if (threadIdx.x > 0) {
+      t = 0;
+#pragma unroll
+      for (int k = 0; k < OL_THREADS / 64; ++k) t += part[k][threadIdx.x - 1];
+    }
+    out[((((long)(row0 + b) * V + v) * S + s) * OL_SPH_COLS) + threadIdx.x] = t;
+  }
+}
+
 __global__ __launch_bounds__(OL_THREADS) void openloop_action_kernel(const f16* __restrict__ a_hat, long ld_hat, long bs_hat, const float* __restrict__ actions,
                                                                      const float* __restrict__ joint_scale, float* __restrict__ out, int T, int A, int row0,
                                                                      int n) {
@@ -142,6 +235,34 @@ int32_t gn_openloop_image_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_t
   const int64_t threads = (int64_t)H * ((W + 3) / 4);
   hipLaunchKernelGGL(openloop_image_kernel, dim3((unsigned)cdiv64(threads, OL_THREADS), (unsigned)V, (unsigned)n_valid), dim3(OL_THREADS), 0, ctx->stream, gen,
                      gt, occupied, (unsigned long long*)img_out, V, H, W, tiled ? 1 : 0, row0);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int32_t gn_openloop_sphere_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_t* gt, const uint8_t* cond, const uint8_t* occupied, const int32_t* win,
+                                   const int32_t* win_host, uint64_t* sph_out, int32_t B, int32_t V, int32_t H, int32_t W, int32_t S, int32_t tiled,
+                                   int32_t threshold, int32_t row0, int32_t n_valid, int32_t rows) {
+  GN_REQUIRE(ctx && gen && gt && cond && occupied && win && sph_out, "gn_openloop_sphere_metrics: null argument");
+  GN_REQUIRE(B > 0 && B <= 65535 && V > 0 && V <= 65535 && H > 0 && W > 0 && (int64_t)H * W * 3 <= INT32_MAX,
+             "gn_openloop_sphere_metrics: B (%d), V (%d), H (%d), W (%d) out of range", B, V, H, W);
+  GN_REQUIRE(S >= 1 && S <= 8, "gn_openloop_sphere_metrics: S (%d) must lie in [1, 8]", S);
+  GN_REQUIRE(threshold >= 0, "gn_openloop_sphere_metrics: threshold (%d) must not be negative", threshold);
+  GN_REQUIRE(!tiled || V == 4, "gn_openloop_sphere_metrics: the tiled layout holds 4 views, got V = %d", V);
+  GN_REQUIRE(n_valid >= 0 && n_valid <= B && row0 >= 0 && (int64_t)row0 + n_valid <= rows,
+             "gn_openloop_sphere_metrics: n_valid (%d) must lie in [0, B = %d] and rows row0 (%d) .. row0 + n_valid inside the table's %d", n_valid, B, row0, rows);
+  GN_REQUIRE(((uintptr_t)win & 3) == 0 && ((uintptr_t)win_host & 3) == 0 && ((uintptr_t)sph_out & 7) == 0,
+             "gn_openloop_sphere_metrics: win must be 4-byte and sph_out 8-byte aligned");
+  if (win_host) {
+    for (int64_t i = 0; i < (int64_t)B * V * S; ++i) {
+      const int32_t* q = win_host + i * 4;
+      GN_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[2] >= q[0] && q[3] >= q[1] && q[2] <= W && q[3] <= H && q[2] - q[0] <= OL_WIN_MAX && q[3] - q[1] <= OL_WIN_MAX,
+                 "gn_openloop_sphere_metrics: window %ld = (%d, %d, %d, %d) must lie inside the %d x %d image with x0 <= x1, y0 <= y1 and at most %d per side",
+                 (long)i, q[0], q[1], q[2], q[3], W, H, OL_WIN_MAX);
+    }
+  }
+  if (n_valid == 0) return GN_OK;
+  hipLaunchKernelGGL(openloop_sphere_kernel, dim3((unsigned)S, (unsigned)V, (unsigned)n_valid), dim3(OL_THREADS), 0, ctx->stream, gen, gt, cond, occupied, win,
+                     (unsigned long long*)sph_out, V, H, W, S, tiled ? 1 : 0, threshold, row0);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

@@ -1474,6 +1474,33 @@ class Engine:
                                                  B if n_valid is None else int(n_valid), rows), "gn_openloop_image_metrics")
         return out
 
+    def openloop_sphere_metrics(self, gen, gt, cond, occupied, win, out, *, threshold: int = 30, row0: int = 0, n_valid: Optional[int] = None,
+                                win_host=None):
+        """``gn_openloop_sphere_metrics``: ``gen`` / ``gt`` / ``occupied`` as ``openloop_image_metrics`` takes them, ``cond`` uint8
+        [B * V, H, W, 3] (the frames the render was drawn over), ``win`` int32 [B * V, S, 4] on the device (``render.sphere_windows``) -> rows
+        ``row0 .. row0 + n_valid - 1`` of ``out`` int64 [rows, V, S, 17], each window's values stored by its own workgroup; samples
+        ``b >= n_valid`` (default B) write nothing.  ``win_host``: an int32 numpy copy of ``win``; with it bad windows are refused, without it
+        the kernel clamps them.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("openloop_sphere_metrics is an eager op: the result rows change from batch to batch")
+        H, W = int(gt.shape[1]), int(gt.shape[2])
+        tiled = gen.dim() == 4
+        B = int(gen.shape[0])
+        V = 4 if tiled else int(gen.shape[1])
+        S, rows = int(win.shape[1]), int(out.shape[0])
+        for t, dt, shape in ((gen, torch.uint8, (B, 2 * H, 2 * W, 3) if tiled else (B, V, H, W, 3)), (gt, torch.uint8, (B * V, H, W, 3)),
+                             (cond, torch.uint8, (B * V, H, W, 3)), (occupied, torch.uint8, (B * V, H, W)), (win, torch.int32, (B * V, S, 4)),
+                             (out, torch.int64, (rows, V, S, 17))):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
+        hp = None
+        if win_host is not None:
+            assert str(win_host.dtype) == "int32" and win_host.flags.c_contiguous and win_host.shape == (B * V, S, 4), win_host.shape
+            hp = win_host.ctypes.data
+        check(self.lib.gn_openloop_sphere_metrics(self._ctx, _ptr(gen), _ptr(gt), _ptr(cond), _ptr(occupied), _ptr(win), hp, _ptr(out), B, V, H, W, S,
+                                                  int(tiled), int(threshold), int(row0), B if n_valid is None else int(n_valid), rows),
+              "gn_openloop_sphere_metrics")
+        return out
+
     def openloop_action_metrics(self, a_hat, actions, out, *, joint_scale=None, row0: int = 0, n_valid: Optional[int] = None):
         """``gn_openloop_action_metrics``: ``a_hat`` f16 [B, T, >= A] (any row pitch and sample stride: ``act_tiled``'s view of the padded
         chunk is taken as it is) against ``actions`` f32 [B, T, A] -> rows ``row0 .. row0 + n_valid - 1`` of ``out`` f32 [rows, T, 2] =

@@ -12,6 +12,13 @@ here.  What a demo tree does give is, for every transition, t
 * a second controller pass on the GROUND-TRUTH target, the "oracle" row: what the controller does when the diffusion model is perfect, so the
   difference between the two rows is the diffusion model's share of the error.
 
+* where each drawn sphere landed: per (transition, camera, sphere) the mass, centroid, spread and colour of what the generated image changed
+  against the observation inside the sphere's window, beside the same of the rendered target -- ``gn_openloop_sphere_metrics`` over
+  ``render.sphere_windows``.  The in-mask RMSE cannot tell a sphere drawn 6 px off from a blurred or a missing one; these can.
+
+``OpenLoopEval(agent, None, ...)`` is the diffusion-only mode (no controller exists while the ControlNet is being fine-tuned):
+``diffusion_validator`` makes a ``train_loop.TrainLoop`` ``validate`` callable of it.
+
 Frames, scores and the per-transition tables stay on the device; ``run()`` ends with one device-to-host copy of the tables.
 
 What this is NOT: a success rate.  Every chunk is predicted from a demo state, so errors never compound and nothing is executed.
@@ -29,6 +36,8 @@ from . import harness
 from .replay import DEFAULT_CAMERAS, DeviceReplay
 
 IMAGE_COLUMNS = ("se_in", "n_in", "se_out", "n_out", "wrap_sq")  # gn_openloop_image_metrics' five values per (transition, camera)
+SPHERE_COLUMNS = ("area", "gen_m", "gen_mx", "gen_my", "gen_mr2", "gt_m", "gt_mx", "gt_my", "gt_mr2", "n_occ", "se_occ", "gen_r", "gen_g", "gen_b",
+                  "gt_r", "gt_g", "gt_b")  # gn_openloop_sphere_metrics' 17 values per (transition, camera, sphere)
 
 
 def _mean(x) -> Optional[float]:
@@ -40,10 +49,16 @@ def _mean(x) -> Optional[float]:
 class OpenLoopResult:
     """The per-transition tables of one evaluation, on the host.  ``image`` int64 [N, V, 5] (``IMAGE_COLUMNS``; None for a controller-only
     run); ``actions``: ``{"generated" | "oracle": {"norm" | "rad": f32 [N, T, 2]}}`` -- ``[.., 0]`` the joint L1 SUM over the ``joints`` arm
-    joints, normalised or in radians, ``[.., 1]`` the gripper flag; ``episode`` / ``step`` / ``task`` int32 [N] (``task`` indexes ``tasks``)."""
+    joints, normalised or in radians, ``[.., 1]`` the gripper flag; ``episode`` / ``step`` / ``task`` int32 [N] (``task`` indexes ``tasks``).
+    ``spheres`` int64 [N, V, S, 17] (``SPHERE_COLUMNS``) with ``windows`` int32 [N, V, S, 4], or both None: the per-sphere table and the
+    windows it was summed over.  A sphere is DRAWN where the ground truth changed its window (gt mass > 0); the accessors are NaN elsewhere.
+    Overlapping windows share pixels, so a neighbour's mass can enter a sphere's sums."""
 
-    def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int):
-        self.image, self.actions = image, actions
+    def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int,
+                 spheres=None, windows=None):
+        if (spheres is None) != (windows is None):
+            raise ValueError("OpenLoopResult: spheres and windows come together (the score needs the windows' diagonals)")
+        self.image, self.actions, self.spheres, self.windows = image, actions, spheres, windows
         self.episode, self.step, self.task = np.asarray(episode, np.int32), np.asarray(step, np.int32), np.asarray(task, np.int32)
         self.tasks, self.cameras, self.joints, self.H, self.W = list(tasks), list(cameras), int(joints), int(H), int(W)
 
@@ -63,7 +78,63 @@ class OpenLoopResult:
         """f64 [N]: the reference's validation ``mse`` (numpy's wrapping uint8 arithmetic) of the whole tiled image."""
         return self.image[..., 4].astype(np.float64).sum(axis=1) / float(len(self.cameras) * self.H * self.W * 3)
 
-    def _summary(self, rows: np.ndarray) -> Dict:
+    # ---- per sphere, f64 [N, V, S]
+    def _col(self, i: int) -> np.ndarray:
+        return self.spheres[..., i].astype(np.float64)
+
+    def sphere_drawn(self) -> np.ndarray:
+        """bool [N, V, S]: the ground truth changed something in the window (gt mass > 0)."""
+        return self.spheres[..., 5] > 0
+
+    def _moments(self, o: int):
+        """-> (mass, centroid x, centroid y, radial RMS spread) of the four sums at columns o .. o + 3; NaN where the mass is 0."""
+        m = self._col(o)
+        nan = np.full(m.shape, np.nan)
+        cx, cy = (np.divide(self._col(o + k), m, out=nan.copy(), where=m > 0) for k in (1, 2))
+        r2 = np.divide(self._col(o + 3), m, out=nan.copy(), where=m > 0)
+        with np.errstate(invalid="ignore"):
+            return m, cx, cy, np.sqrt(np.maximum(0.0, r2 - cx * cx - cy * cy))
+
+    def sphere_shift(self) -> np.ndarray:
+        """The distance in pixels between the generated and the true centroid; NaN where either mass is 0."""
+        (_, gx, gy, _), (_, tx, ty, _) = self._moments(1), self._moments(5)
+        return np.hypot(gx - tx, gy - ty)
+
+    def sphere_mass_ratio(self) -> np.ndarray:
+        g, t = self._col(1), self._col(5)
+        return np.divide(g, t, out=np.full(g.shape, np.nan), where=t > 0)
+
+    def sphere_spread_ratio(self) -> np.ndarray:
+        """Generated over true radial RMS spread; NaN where either mass is 0 or the true spread is 0 (a one-pixel target)."""
+        sg, st = self._moments(1)[3], self._moments(5)[3]
+        return np.divide(sg, st, out=np.full(sg.shape, np.nan), where=st > 0)
+
+    def sphere_colour_l1(self) -> np.ndarray:
+        """Mean over the channels of |sum gen_c - sum gt_c| / n_occ over the window's occupied pixels; NaN where undrawn or n_occ is 0."""
+        n = self._col(9)
+        d = np.abs(self.spheres[..., 11:14] - self.spheres[..., 14:17]).astype(np.float64).mean(axis=-1)
+        return np.where(self.sphere_drawn(), np.divide(d, n, out=np.full(n.shape, np.nan), where=n > 0), np.nan)
+
+    def _sphere_summary(self, rows: np.ndarray, found_mass: float) -> Dict:
+        drawn = self.sphere_drawn()[rows]
+        shift, mass = self.sphere_shift()[rows], self.sphere_mass_ratio()[rows]
+        spread, colour = self.sphere_spread_ratio()[rows], self.sphere_colour_l1()[rows]
+        w = self.windows[rows].astype(np.float64)
+        penalty = 0.5 * np.hypot(w[..., 2] - w[..., 0], w[..., 3] - w[..., 1])  # half the window's diagonal: a sphere that is not there
+        scored = np.where(np.isnan(shift), penalty, shift)
+
+        def block(sel):  # sel: bool over [n, V', S], the drawn spheres of one camera or of all
+            n = int(sel.sum())
+            return {"n_drawn": n, "found_rate": float((mass[sel] >= found_mass).mean()) if n else None, "shift_px": _mean(shift[sel]),
+                    "mass_ratio": _mean(mass[sel]), "spread_ratio": _mean(spread[sel]), "colour_l1": _mean(colour[sel])}
+
+        per = {c: block(drawn & (np.arange(len(self.cameras)) == v)[None, :, None]) for v, c in enumerate(self.cameras)}
+        out = {k: {c: per[c][k] for c in self.cameras} for k in ("n_drawn", "found_rate", "shift_px", "mass_ratio", "spread_ratio", "colour_l1")}
+        out["overall"] = block(drawn)
+        out["score"] = float(scored[drawn].mean()) if drawn.any() else None
+        return out
+
+    def _summary(self, rows: np.ndarray, found_mass: float = 0.5) -> Dict:
         out: Dict = {"n": int(rows.sum())}
         for name, tabs in self.actions.items():
             norm, rad = tabs["norm"][rows].astype(np.float64), tabs["rad"][rows].astype(np.float64)
@@ -78,17 +149,22 @@ class OpenLoopResult:
                             "sphere_missing": {c: int(np.isnan(sph[:, v]).sum()) for v, c in enumerate(self.cameras)},
                             "background_rmse": {c: _mean(bg[:, v]) for v, c in enumerate(self.cameras)},
                             "wrapped_mse": _mean(self.wrapped_mse()[rows])}
+            if self.spheres is not None:
+                out["image"]["spheres"] = self._sphere_summary(rows, found_mass)
         return out
 
-    def summary(self) -> Dict:
+    def summary(self, found_mass: float = 0.5) -> Dict:
         """Means over all transitions, in numpy f64: per row (``generated``, ``oracle``) the joint L1 per joint -- normalised and in radians --
         and the gripper accuracy, overall and per chunk position; per camera the sphere-region RMSE over the transitions that drew a sphere
         there (None where none did; ``sphere_missing`` counts the others), the background RMSE and the wrapped ``mse``; ``per_task`` the same
-        for each task when there is more than one."""
-        out = self._summary(np.ones(len(self), bool))
+        for each task when there is more than one.  With a sphere table, ``["image"]["spheres"]``: per camera (and under ``overall``) ``n_drawn``,
+        ``found_rate`` (the share of drawn spheres whose mass ratio is at least ``found_mass``) and the means of the shift in pixels, the mass
+        ratio, the spread ratio and the colour L1; ``score``, lower is better: the mean over the drawn spheres of the shift, a sphere without
+        generated mass counting as half the diagonal of its window.  Like every score here it is not a success rate."""
+        out = self._summary(np.ones(len(self), bool), found_mass)
         out["cameras"], out["tasks"] = self.cameras, self.tasks
         if len(self.tasks) > 1:
-            out["per_task"] = {t: self._summary(self.task == i) for i, t in enumerate(self.tasks)}
+            out["per_task"] = {t: self._summary(self.task == i, found_mass) for i, t in enumerate(self.tasks)}
         return out
 
     def to_json(self, path: str) -> Dict:
@@ -117,25 +193,46 @@ class OpenLoopEval:
     and optionally ``description.txt``, or ``(demo, frames, traj[, description])`` tuples.  ``render_cfg``: the ``render.RenderConfig`` the
     targets are drawn with (the one the diffusion model's training targets were rendered with).  ``stats``: the TRAINING run's ``(action_stats,
     proprio_stats)`` (``replay.load_stats`` of the snapshot directory) -- a held-out set must not be normalised with its own statistics.
-    ``tokenizer``: the controller's task-token source, as ``DeviceReplay`` takes it.
+    ``tokenizer``: the controller's task-token source, as ``DeviceReplay`` takes it.  ``change_threshold``: ``gn_openloop_sphere_metrics``'
+    threshold on the summed absolute channel difference against the observation (a starting value, not measured against a trained checkpoint).
+
+    ``controller=None`` with a diffusion agent is the diffusion-only mode: no controller pass, no action tables (``result.actions == {}``); the
+    device and the engine come from the agent's pipeline, ``stats`` may be None (the replay then normalises with the set's own statistics, and
+    nothing that depends on them is scored) and ``action_sequence`` (default: the controller's ``num_queries``, else 20) sets the replay's
+    chunk length.  Its image and sphere tables equal those of a run with a controller on the same seed bit for bit.
 
     Per batch, on the device: ``DeviceReplay.sample`` (the frames, proprioception, normalised action chunk, task tokens) -> ``gn_render_spheres``
     over the frames (``full``, ``occupied``) -> the four views on the 2x2 canvas -> the pipeline (``harness.make_prompt`` ids, one generator
-    seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image and action scores -> the controller again on ``full`` -> its action
+    seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image, sphere and action scores -> the controller again on ``full`` -> its action
     scores.  The transitions are walked in order; the last batch is padded by repeating its last index and scores only its first rows, so one
     recorded program per network serves the whole run."""
 
     def __init__(self, diffusion_agent, controller, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None,
-                 batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None):
-        from .render import load_atlas, load_traj
+                 batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
+                 change_threshold: int = 30, action_sequence: Optional[int] = None):
+        from .render import load_atlas, load_traj, sphere_windows
 
-        if controller.execution is not None:
-            raise ValueError(f"OpenLoopEval: the controller has an execution mode set ({controller.execution}); open-loop scoring compares whole "
-                             "chunks -- call set_execution() with nothing set first")
-        if int(controller.config.get("frame_stack", 1)) > 1:
-            raise NotImplementedError("OpenLoopEval: frame-stacked controllers (frame_stack > 1) are not scored")
-        if stats is None:
-            raise ValueError("OpenLoopEval: stats = (action_stats, proprio_stats) of the TRAINING run is required (replay.load_stats)")
+        if controller is None:
+            if diffusion_agent is None:
+                raise ValueError("OpenLoopEval: nothing to score -- give a diffusion agent, a controller or both")
+            device = diffusion_agent.pipe.device
+            if engine is None:
+                engine = diffusion_agent.pipe.unet.engine()
+            T = 20 if action_sequence is None else int(action_sequence)
+        else:
+            if controller.execution is not None:
+                raise ValueError(f"OpenLoopEval: the controller has an execution mode set ({controller.execution}); open-loop scoring compares whole "
+                                 "chunks -- call set_execution() with nothing set first")
+            if int(controller.config.get("frame_stack", 1)) > 1:
+                raise NotImplementedError("OpenLoopEval: frame-stacked controllers (frame_stack > 1) are not scored")
+            if stats is None:
+                raise ValueError("OpenLoopEval: stats = (action_stats, proprio_stats) of the TRAINING run is required (replay.load_stats)")
+            device, T = controller.device, int(controller.config["num_queries"])
+            if action_sequence is not None and int(action_sequence) != T:
+                raise ValueError(f"OpenLoopEval: action_sequence = {action_sequence} contradicts the controller's num_queries = {T}")
+        if int(change_threshold) < 0:
+            raise ValueError(f"OpenLoopEval: change_threshold = {change_threshold} must not be negative")
+        self.change_threshold = int(change_threshold)
         self.agent, self.controller, self.cameras, self.V = diffusion_agent, controller, tuple(cameras), len(cameras)
         if diffusion_agent is not None and self.V != 4:
             raise ValueError(f"OpenLoopEval: the 2x2 canvas takes exactly four cameras, got {self.V}")
@@ -150,13 +247,12 @@ class OpenLoopEval:
             else:
                 eps.append((ep[0], ep[1]) + tuple(ep[3:4]))
                 trajs.append(ep[2])
-        self.replay = DeviceReplay(eps, self.cameras, engine=engine, device=controller.device, frame_stack=1,
-                                   action_sequence=int(controller.config["num_queries"]), batch_size=self.batch_size, tokenizer=tokenizer,
+        self.replay = DeviceReplay(eps, self.cameras, engine=engine, device=device, frame_stack=1, action_sequence=T, batch_size=self.batch_size, tokenizer=tokenizer,
                                    image_size=H if H == W and isinstance(eps[0], str) else None, stats=stats)
         rp = self.replay
         if (rp.H, rp.W) != (H, W):
             raise ValueError(f"OpenLoopEval: the frames are {rp.H} x {rp.W}, the render config draws {H} x {W}")
-        if rp.A != int(controller.config["action_dim"]):
+        if controller is not None and rp.A != int(controller.config["action_dim"]):
             raise ValueError(f"OpenLoopEval: the demos' actions have {rp.A} elements, the controller's {controller.config['action_dim']}")
         self.E, self.N, self.H, self.W, self.T, self.A = rp.E, rp.N, H, W, rp.T, rp.A
         dev = self.E.device
@@ -174,14 +270,20 @@ class OpenLoopEval:
         rows = ((starts[ep_of] + step)[:, None] * self.V + np.arange(self.V)[None]).reshape(-1)
         self.views = {k: torch.from_numpy(np.ascontiguousarray(vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:]))).to(dev) for k in vt}
         self.atlas = torch.from_numpy(load_atlas(render_cfg.texture_dir)).to(dev)
+        self.windows = self.windows_host = None
+        if diffusion_agent is not None:  # the spheres' windows of every transition, once: int32 [N, V, S, 4], host and device
+            tab = {k: vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:]) for k in ("cams", "spheres", "count")}
+            self.windows_host = np.ascontiguousarray(sphere_windows(tab["cams"], tab["spheres"], tab["count"], H, W))
+            self.windows = torch.from_numpy(self.windows_host).to(dev)
         self.samples = int(render_cfg.samples)
         self.step_index, self.episode_index = step, ep_of.copy()
         names = [_task_of(ep, d) for ep, d in zip(episodes, rp.descriptions)]
         self.tasks = sorted(set(names))
         self.task_index = np.asarray([self.tasks.index(names[e]) for e in ep_of], np.int32)
         # ---- scales, prompt ids
-        std = torch.from_numpy(np.asarray(stats[0]["std"], np.float64)[: self.A - 1].astype(np.float32)).to(dev)
-        self.joint_std = std.contiguous()
+        self.joint_std = None
+        if controller is not None:
+            self.joint_std = torch.from_numpy(np.asarray(stats[0]["std"], np.float64)[: self.A - 1].astype(np.float32)).to(dev).contiguous()
         self.prompts = [harness.make_prompt(d) for d in rp.descriptions]
         self.prompt_ids = torch.cat([diffusion_agent.pipe.encode_ids([p]) for p in self.prompts]) if diffusion_agent is not None else None
         self._n_index = torch.arange(rp.N, dtype=torch.int64, device=dev)
@@ -202,6 +304,8 @@ class OpenLoopEval:
         occupied = torch.empty((B * V, H, W), dtype=torch.uint8, device=E.device)
         E.render_spheres(v["cams"], v["spheres"], v["tex_index"], v["count"], self.atlas, H, W, self.samples, bg=frames, full=full, occupied=occupied)
         batch["full"], batch["occupied"] = full, occupied
+        if self.windows is not None:
+            batch["windows"] = self.windows.index_select(0, sel).reshape(B * V, -1, 4).contiguous()
         if V == 4:  # view v -> the tile at row v / 2, column v % 2 (tiling.CROP_ORDER): layout only
             batch["tiled"] = frames.view(B, 2, 2, H, W, 3).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * H, 2 * W, 3)
         return batch
@@ -238,15 +342,18 @@ class OpenLoopEval:
         def act():
             return {unit: torch.zeros((N, T, 2), dtype=torch.float32, device=dev) for unit in ("norm", "rad")}
 
-        tabs = {"oracle": act()}
+        tabs = {"oracle": act()} if self.controller is not None else {}
         if self.agent is not None:
-            tabs["generated"] = act()
+            if self.controller is not None:
+                tabs["generated"] = act()
             tabs["image"] = torch.zeros((N, self.V, 5), dtype=torch.int64, device=dev)
+            tabs["spheres"] = torch.zeros((N, self.V, int(self.windows.shape[2]), 17), dtype=torch.int64, device=dev)
         return tabs
 
     def run_batch(self, start: int, tabs, generator) -> None:
         """One evaluator batch: steps 1 - 7 for transitions ``start ..``, everything on the device, nothing read back."""
-        self._fresh_controller()
+        if self.controller is not None:
+            self._fresh_controller()
         idx = self.batch_indices(start)
         n_valid = min(self.batch_size, self.N - start)
         with torch.inference_mode():  # as harness.control_step runs the same two programs
@@ -254,11 +361,16 @@ class OpenLoopEval:
             B = len(idx)
             if self.agent is not None:
                 gen = self.generate(batch, idx, generator)
-                a_hat = self.controller.act_tiled(gen, batch["low_dim_state"], batch.get("lang_tokens"))
+                if self.controller is not None:
+                    a_hat = self.controller.act_tiled(gen, batch["low_dim_state"], batch.get("lang_tokens"))
                 self.E.openloop_image_metrics(gen, batch["full"], batch["occupied"], tabs["image"], row0=start, n_valid=n_valid)
-                self._score_actions(a_hat, batch, tabs["generated"], start, n_valid)  # before the oracle pass overwrites the program's chunk
-            a_hat = self._chunk(batch["full"].view(B, self.V, self.H, self.W, 3), batch)
-            self._score_actions(a_hat, batch, tabs["oracle"], start, n_valid)
+                self.E.openloop_sphere_metrics(gen, batch["full"], batch["images_u8"].view(B * self.V, self.H, self.W, 3), batch["occupied"],
+                                               batch["windows"], tabs["spheres"], threshold=self.change_threshold, row0=start, n_valid=n_valid)
+                if self.controller is not None:
+                    self._score_actions(a_hat, batch, tabs["generated"], start, n_valid)  # before the oracle pass overwrites the program's chunk
+            if self.controller is not None:
+                a_hat = self._chunk(batch["full"].view(B, self.V, self.H, self.W, 3), batch)
+                self._score_actions(a_hat, batch, tabs["oracle"], start, n_valid)
 
     def run(self) -> OpenLoopResult:
         tabs = self._tables()
@@ -266,7 +378,7 @@ class OpenLoopEval:
         for start in range(0, self.N, self.batch_size):
             self.run_batch(start, tabs, generator)
         # the one device-to-host copy: every table as bytes of one buffer
-        flat = [tabs[k][m] for k in ("generated", "oracle") if k in tabs for m in ("norm", "rad")] + ([tabs["image"]] if "image" in tabs else [])
+        flat = [tabs[k][m] for k in ("generated", "oracle") if k in tabs for m in ("norm", "rad")] + [tabs[k] for k in ("image", "spheres") if k in tabs]
         host = torch.cat([t.reshape(-1).view(torch.uint8) for t in flat]).cpu().numpy()
         out, o = [], 0
         for t in flat:
@@ -278,8 +390,9 @@ class OpenLoopEval:
             if name in tabs:
                 actions[name] = {"norm": out[k], "rad": out[k + 1]}
                 k += 2
-        image = out[k] if "image" in tabs else None
-        return OpenLoopResult(image, actions, self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1, self.H, self.W)
+        image, spheres = (out[k], out[k + 1]) if "image" in tabs else (None, None)
+        return OpenLoopResult(image, actions, self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1, self.H, self.W,
+                              spheres=spheres, windows=self.windows_host if spheres is not None else None)
 
 
 def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None):
@@ -297,5 +410,43 @@ def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, 
         s = ev.run().summary()["oracle"]
         return {"select": s["joint_l1_norm"], "joint_l1_norm": s["joint_l1_norm"], "joint_l1_rad": s["joint_l1_rad"],
                 "gripper_acc": s["gripper_acc"], "n": float(len(ev.replay))}
+
+    return validate
+
+
+VALIDATION_JSONL = "validation.jsonl"
+
+
+def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, out_dir=None, tokenizer=None, batch_size: int = 8,
+                        num_inference_steps: int = 5, seed: int = 0, engine=None):
+    """-> a ``validate(global_step)`` callable for ``train_loop.TrainLoop``: each call wraps ``make_pipe()`` (for instance
+    ``validation.validation_pipeline(..., trainer, "euler_discrete")`` over the trainer's current weights) as the agent of a diffusion-only
+    ``OpenLoopEval`` on held-out demos and returns ``{"step", "select", "found_rate", "shift_px", "mass_ratio", "spread_ratio", "colour_l1",
+    "sphere_rmse", "background_rmse", "wrapped_mse", "n"}`` -- ``select`` is ``summary()["image"]["spheres"]["score"]`` (lower is better), the
+    sphere fields are its ``overall`` block, the two RMSEs the means over all cameras.  With ``out_dir`` the dict is also appended as one JSON
+    line to ``<out_dir>/validation.jsonl``.  The demo set is loaded onto the device at the first call and kept; later calls swap the agent.
+    ``TrainLoop`` ignores the return value; it is there for callers that rank checkpoints themselves."""
+    import types
+
+    state: Dict = {}
+
+    def validate(global_step: int) -> Dict:
+        agent = types.SimpleNamespace(pipe=make_pipe())
+        ev = state.get("ev")
+        if ev is None:
+            ev = state["ev"] = OpenLoopEval(agent, None, episodes, cameras, render_cfg=render_cfg, stats=None, tokenizer=tokenizer, batch_size=batch_size,
+                                            num_inference_steps=num_inference_steps, seed=seed, engine=engine)
+        ev.agent = agent
+        res = ev.run()
+        im = res.summary()["image"]
+        sp = im["spheres"]
+        line = {"step": int(global_step), "select": sp["score"], "found_rate": sp["overall"]["found_rate"], "shift_px": sp["overall"]["shift_px"],
+                "mass_ratio": sp["overall"]["mass_ratio"], "spread_ratio": sp["overall"]["spread_ratio"], "colour_l1": sp["overall"]["colour_l1"],
+                "sphere_rmse": _mean(res.sphere_rmse()), "background_rmse": _mean(res.background_rmse()), "wrapped_mse": im["wrapped_mse"], "n": len(res)}
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, VALIDATION_JSONL), "a") as f:
+                f.write(json.dumps(line) + "\n")
+        return line
 
     return validate

@@ -96,6 +96,36 @@ def pack_views(views: Sequence, S: int = 4) -> Dict[str, np.ndarray]:
             "tex_index": np.stack([v[2] for v in views]).astype(np.int32), "count": np.asarray([v[3] for v in views], np.int32)}
 
 
+WINDOW_HALF_MAX = 127.0  # a window is at most 255 pixels a side: inside gn_openloop_sphere_metrics' 256
+
+
+def sphere_windows(cams, spheres, count, H: int, W: int, scale: float = 2.0, min_half: float = 3.0) -> np.ndarray:
+    """The pixel window around each sphere's projected centre, for ``gn_openloop_sphere_metrics``: ``cams`` [..., 18], ``spheres``
+    [..., S, 16], ``count`` [...] (the ``pack_views`` / ``replay.view_tables`` layouts) -> int32 [..., S, 4] = (x0, y0, x1, y1), half-open.
+
+    ``gn_render_spheres``' ray rule (include/genima_hip.h) inverted, in numpy f64: with ``R | t`` the camera pose and ``c`` the sphere pose's
+    translation column, ``p = R^T (c - t)``, ``z = -p.z``, ``u = cx + fx p.x / z``, ``v = cy - fy p.y / z``, ``r_px = |fx| radius / z``,
+    ``h = min(max(min_half, scale r_px), 127)``; ``x0 = clip(floor(u - h), 0, W)``, ``x1 = clip(ceil(u + h), 0, W)``, ``y0`` / ``y1`` likewise
+    with ``v`` and ``H``.  A sphere with index ``s >= count``, with ``z`` outside ``[znear, zfar]`` or whose clipped window is empty gets
+    ``(0, 0, 0, 0)``.  ``r_px`` is the radius at the centre's depth: ``scale`` is the margin for perspective and for a generated sphere that
+    sits beside the true one.  Windows of different spheres may overlap; they then share pixels."""
+    cams, sph, count = np.asarray(cams, np.float64), np.asarray(spheres, np.float64), np.asarray(count)
+    S = sph.shape[-2]
+    fx, fy, cx, cy, znear, zfar = (cams[..., i, None] for i in (0, 1, 2, 3, 16, 17))
+    pose = cams[..., 4:16].reshape(cams.shape[:-1] + (3, 4))
+    d = sph[..., [3, 7, 11]] - pose[..., None, :, 3]  # c - t, [..., S, 3]
+    p = np.einsum("...ji,...sj->...si", pose[..., :3], d)  # R^T (c - t)
+    z = -p[..., 2]
+    ok = (np.arange(S) < count[..., None]) & (z >= znear) & (z <= zfar) & (z > 0)
+    zs = np.where(ok, z, 1.0)
+    u, v = cx + fx * p[..., 0] / zs, cy - fy * p[..., 1] / zs
+    h = np.minimum(np.maximum(float(min_half), float(scale) * np.abs(fx) * sph[..., 12] / zs), WINDOW_HALF_MAX)
+    with np.errstate(invalid="ignore"):
+        win = np.stack([np.clip(np.floor(u - h), 0, W), np.clip(np.floor(v - h), 0, H), np.clip(np.ceil(u + h), 0, W), np.clip(np.ceil(v + h), 0, H)], axis=-1)
+    ok &= np.isfinite(win).all(axis=-1) & (win[..., 2] > win[..., 0]) & (win[..., 3] > win[..., 1])
+    return np.where(ok[..., None], win, 0.0).astype(np.int32)
+
+
 # ---- the device path ----
 def _engine(engine=None):
     if engine is None:

@@ -809,7 +809,7 @@ typedef struct gn_replay_render_desc {
 int32_t gn_replay_render(gn_ctx* ctx, const gn_replay_render_desc* d);
 
 /* Open-loop evaluation scores (genima_amd/openloop.py OpenLoopEval): a generated image against the rendered ground truth, and a predicted action
- * chunk against the demo's.  Both write rows row0 .. row0 + n_valid - 1 of a result table of `rows` rows: sample b < n_valid writes row
+ * chunk against the demo's.  All three entry points write rows row0 .. row0 + n_valid - 1 of a result table of `rows` rows: sample b < n_valid writes row
  * row0 + b, samples b >= n_valid (the padding of a last batch) write nothing.  Eager only.  A refused call (NULL required pointer, B, V, H, W,
  * T <= 0, A < 2, n_valid outside [0, B], row0 < 0 or row0 + n_valid > rows, tiled with V != 4) launches nothing and leaves the outputs as they
  * were; n_valid == 0 is accepted and does nothing.
@@ -838,6 +838,34 @@ int32_t gn_openloop_image_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_t
                                   int32_t H, int32_t W, int32_t tiled, int32_t row0, int32_t n_valid, int32_t rows);
 int32_t gn_openloop_action_metrics(gn_ctx* ctx, const void* a_hat, int64_t ld_hat, int64_t bs_hat, const float* actions, const float* joint_scale,
                                    float* act_out, int32_t B, int32_t T, int32_t A, int32_t row0, int32_t n_valid, int32_t rows);
+
+/* gn_openloop_sphere_metrics: where the generated spheres landed (row0, n_valid, rows as above: sample b writes the S * 17 values of each of its
+ * views into row row0 + b).  Per (sample b < n_valid, view v, sphere s < S), integer sums over the pixels
+ * (x, y), x0 <= x < x1, y0 <= y < y1, of the sphere's window, with local coordinates lx = x - x0, ly = y - y0:
+ *   gen, gt, occupied   as gn_openloop_image_metrics takes them (tiled selects gen's layout);  cond uint8 [B * V][H][W][3]: the observation
+ *             frames the render was drawn over (gn_render_spheres' bg)
+ *   win       int32 [B * V][S][4] = (x0, y0, x1, y1), half-open, DEVICE memory, 4-byte aligned (genima_amd/render.py sphere_windows makes them;
+ *             windows of different spheres may overlap, and then share pixels: every window is summed on its own)
+ *   win_host  NULL, or a HOST copy of win.  With it the entry point checks every one of the B * V * S windows and refuses the call unless
+ *             0 <= x0 <= x1 <= W, 0 <= y0 <= y1 <= H, x1 - x0 <= 256 and y1 - y0 <= 256.  Without it nothing can be refused by value; the
+ *             kernel ALWAYS clamps what it reads: x0 into [0, W], x1 into [x0, min(W, x0 + 256)], y likewise with H -- for a window that
+ *             passes the check this changes nothing, and no table value can make the kernel read or write outside its buffers.
+ *   threshold int32 >= 0.  Per pixel: a_gen = max(0, sum_c |gen_c - cond_c| - threshold), a_gt = max(0, sum_c |gt_c - cond_c| - threshold)
+ *   sph_out   uint64 [rows][V][S][17], 8-byte aligned:
+ *     [0]       the window's area in pixels
+ *     [1..4]    sum a_gen, sum a_gen lx, sum a_gen ly, sum a_gen (lx^2 + ly^2)
+ *     [5..8]    the same four sums with a_gt
+ *     [9]       n_occ = the number of window pixels with occupied != 0
+ *     [10]      sum over those pixels and the 3 channels of (gen - gt)^2
+ *     [11..13]  sum of gen's r, g, b over those pixels;  [14..16] the same of gt
+ *   One workgroup owns one window and stores its 17 values itself (no atomics, no zeroing pass: an empty window stores 17 zeros), so every
+ *   run gives the same bits.  A window holds at most 65 536 pixels and a column stays below 6.6e12.  Refused, launching nothing and leaving
+ *   sph_out as it was: a NULL pointer other than win_host, B, V, H, W as gn_openloop_image_metrics bounds them, S outside [1, 8], threshold
+ *   < 0, tiled with V != 4, n_valid outside [0, B], row0 < 0 or row0 + n_valid > rows, a misaligned win / win_host / sph_out, and a window
+ *   that fails win_host's check.  n_valid == 0 is accepted and does nothing.  Eager only. */
+int32_t gn_openloop_sphere_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_t* gt, const uint8_t* cond, const uint8_t* occupied, const int32_t* win,
+                                   const int32_t* win_host, uint64_t* sph_out, int32_t B, int32_t V, int32_t H, int32_t W, int32_t S, int32_t tiled,
+                                   int32_t threshold, int32_t row0, int32_t n_valid, int32_t rows);
 
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of

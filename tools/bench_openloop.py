@@ -3,11 +3,11 @@ ControlNet, the full ACT config), B = 8, V = 4, 256^2 views, synthetic episodes,
 inside every repetition:
 
   (a) the bare joint call: the pipeline (``output_type="pt"``) -> ``GenimaACT.act_tiled``
-  (b) one evaluator batch (``OpenLoopEval.run_batch``): sample -> ``gn_render_spheres`` -> tile -> pipeline -> ``act_tiled`` -> image and
-      action scores -> the oracle controller pass on the rendered target -> its action scores
+  (b) one evaluator batch (``OpenLoopEval.run_batch``): sample -> ``gn_render_spheres`` -> tile -> pipeline -> ``act_tiled`` -> image, sphere
+      and action scores -> the oracle controller pass on the rendered target -> its action scores
 
 Each figure is the median (with min / max) of ``--reps`` individually synchronised repetitions after ``--warmup``, a host clock around work
-that ends in a stream synchronise.  The oracle controller pass alone is timed the same way, and the three launches -- the two metric kernels
+that ends in a stream synchronise.  The oracle controller pass alone is timed the same way, and the four launches -- the three metric kernels
 and ``gn_render_spheres`` -- by device events (5 x 100 launches).  The claim checked: (b) costs no more than (a) plus the run's own min-max
 spread of (a).
 
@@ -115,12 +115,14 @@ def main():
     res["evaluator_minus_bare_ms"] = round(b["median_ms"] - a["median_ms"], 4)
     res["bare_spread_ms"] = round(a["max_ms"] - a["min_ms"], 4)
     res["evaluator_within_bare_spread"] = bool(res["evaluator_minus_bare_ms"] <= res["bare_spread_ms"])
-    # the three launches alone
+    # the four launches alone
     out_img, a_hat = bare()
     sel = torch.from_numpy(idx).cuda()
     v = {k: t.index_select(0, sel).reshape((B * ev.V,) + tuple(t.shape[2:])).contiguous() for k, t in ev.views.items()}
     frames = batch["images_u8"].view(B * ev.V, S, S, 3)
     launches = {"image_metrics_us": lambda: E.openloop_image_metrics(out_img, batch["full"], batch["occupied"], tabs["image"]),
+                "sphere_metrics_us": lambda: E.openloop_sphere_metrics(out_img, batch["full"], frames, batch["occupied"], batch["windows"], tabs["spheres"],
+                                                                       threshold=ev.change_threshold),
                 "action_metrics_us": lambda: E.openloop_action_metrics(a_hat, batch["action"], tabs["generated"]["rad"], joint_scale=ev.joint_std),
                 "render_spheres_us": lambda: E.render_spheres(v["cams"], v["spheres"], v["tex_index"], v["count"], ev.atlas, S, S, ev.samples, bg=frames,
                                                               full=batch["full"], occupied=batch["occupied"])}
@@ -137,6 +139,9 @@ def main():
             E.synchronize()
             us.append(E.event_elapsed_ms(s, e) / 100 * 1e3)
         res[name] = {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
+    wh = ev.windows_host[idx]
+    res["sphere_windows"] = {"n": int(wh[..., 0].size), "non_empty": int(((wh[..., 2] > wh[..., 0]) & (wh[..., 3] > wh[..., 1])).sum()),
+                             "pixels": int(((wh[..., 2] - wh[..., 0]) * (wh[..., 3] - wh[..., 1])).sum()), "change_threshold": ev.change_threshold}
     res["image_metrics_bytes"] = int(out_img.numel() + batch["full"].numel() + batch["occupied"].numel())
     line = json.dumps(res)
     print(line, flush=True)

@@ -10,7 +10,9 @@ ground truth, the predicted action chunk against the demo's, and the controller 
 Reads ``<dataset_root>/<task>/variation0/episodes/<episode>/{<camera>_rgb/<ts>.png, demo.npz, traj.npz[, description.txt]}`` (the camera frames
 are the SCENE frames the diffusion agent sees at run time; ``tools/render_dataset.py`` writes ``traj.npz``, ``genima_amd.replay.save_demo``
 ``demo.npz``).  ``--stats_dir`` holds the TRAINING run's ``action_stats.json`` / ``proprio_stats.json``: the held-out demos are normalised with
-those, never with their own.  Prints the summary and writes it as JSON.  Open-loop error is not a success rate: every chunk is predicted from
+those, never with their own.  Prints the summary and writes it as JSON; with a diffusion agent it carries ``image.spheres``, the per-sphere
+location / mass / spread / colour scores (``--change_threshold`` sets their threshold against the observation).  ``--no_controller`` scores the
+diffusion checkpoint alone (no ``--controller_snapshot`` / ``--stats_dir`` needed: the mode a ControlNet fine-tune validates in).  Open-loop error is not a success rate: every chunk is predicted from
 a demo state, nothing is executed and no error compounds."""
 import argparse
 import json
@@ -31,8 +33,10 @@ def parse(argv=None):
     ap.add_argument("--diffusion_ckpt", default="", help="the fine-tune's output directory (checkpoint-N/controlnet) or a ControlNet directory")
     ap.add_argument("--agent", default="SDControlNetAgent", choices=["SDControlNetAgent", "SDXLControlNetAgent", "SDPix2PixAgent"])
     ap.add_argument("--autoencoder", default="")
-    ap.add_argument("--controller_snapshot", required=True, help="latest.pt / best.pt / <epoch>.pt of tools/train_act.py")
-    ap.add_argument("--stats_dir", required=True, help="directory of the training run's action_stats.json and proprio_stats.json")
+    ap.add_argument("--controller_snapshot", default=None, help="latest.pt / best.pt / <epoch>.pt of tools/train_act.py")
+    ap.add_argument("--stats_dir", default=None, help="directory of the training run's action_stats.json and proprio_stats.json")
+    ap.add_argument("--no_controller", action="store_true", help="diffusion-only mode: image and sphere scores, no action tables")
+    ap.add_argument("--change_threshold", type=int, default=30, help="gn_openloop_sphere_metrics' threshold on the summed channel difference against the observation")
     ap.add_argument("--clip_text", default=None, help="transformers CLIPTextModel directory (weights and tokenizer) of the controller")
     ap.add_argument("--cameras", nargs="+", default=list(P.DEFAULT_CAMERAS))
     ap.add_argument("--image_size", type=int, default=256)
@@ -44,7 +48,10 @@ def parse(argv=None):
     ap.add_argument("--guidance_scale", type=float, default=0.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="openloop.json")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if not a.no_controller and not (a.controller_snapshot and a.stats_dir):
+        ap.error("--controller_snapshot and --stats_dir are required unless --no_controller is given")
+    return a
 
 
 def main(argv=None):
@@ -75,11 +82,15 @@ def main(argv=None):
                                upcast_vae=False, fused_projections=True, enable_xformers_memory_efficient_attention=True,
                                show_diffusion_progress=False, torch_compile=False, autoencoder=a.autoencoder)
     dagent = getattr(A, a.agent)(ns)
-    cfg = dict(configs.ACT_POLICY, num_queries=a.action_sequence, num_views=len(a.cameras), image_size=a.image_size, use_lang_cond=tokenizer is not None)
-    controller = GenimaACT(cfg, None, configs.ACT_CLIP_TEXT, clip_sd, device="cuda", seed=a.seed)
-    harness.load_controller_ckpt(controller, a.controller_snapshot)
-    ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=P.load_stats(a.stats_dir), tokenizer=tokenizer,
-                      batch_size=a.batch_size, num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed)
+    controller = stats = None
+    if not a.no_controller:
+        cfg = dict(configs.ACT_POLICY, num_queries=a.action_sequence, num_views=len(a.cameras), image_size=a.image_size, use_lang_cond=tokenizer is not None)
+        controller = GenimaACT(cfg, None, configs.ACT_CLIP_TEXT, clip_sd, device="cuda", seed=a.seed)
+        harness.load_controller_ckpt(controller, a.controller_snapshot)
+        stats = P.load_stats(a.stats_dir)
+    ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=stats, tokenizer=tokenizer, batch_size=a.batch_size,
+                      num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed, change_threshold=a.change_threshold,
+                      action_sequence=a.action_sequence)
     print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
     summary = ev.run().to_json(a.out)
     print(json.dumps(summary, indent=1))
