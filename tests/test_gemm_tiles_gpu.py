@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from genima_amd._lib import GEMM_DMA, GEMM_PPP, GEMM_RING, gemm_tiles
+import gemm_ref
 from util import assert_close, randn_h
 
 pytestmark = pytest.mark.gpu
@@ -99,7 +100,7 @@ def test_f32_accumulate_and_transposed_every_tile(eng, tile_override, tile):
 def test_linear_random_shapes_and_tiles(eng, tile_override):
     """Seeded sweep: random (M, N, K) -- row / column / reduction tails everywhere --, random tile, random epilogue (bias, residual before or
     after the activation, activation) against torch; the tails decide which loader / epilogue branches run, so the fixed shapes above are
-    not enough on their own."""
+    not enough on their own.  Every case is also held to the per-element f64 bound of tests/gemm_ref.py."""
     import random
 
     rnd = random.Random(1234)
@@ -123,11 +124,16 @@ def test_linear_random_shapes_and_tiles(eng, tile_override):
             ref = ACTS[act](x.float().cpu() @ w.float().cpu().t() + (b.float().cpu() if use_b else 0)) + (r.float().cpu() if use_r else 0)
         if y is not None:
             assert_close(y, ref, what=f"case {case}: tile {tile} {M}x{N}x{K} act {act} bias {use_b} res {use_r} first {rfirst}")
+            # (splitk left at 1: the planner may split the K = 1024 small-M cases 2 ways, 2 additions beside 2 x 1024 in the bound's count)
+            r64 = gemm_ref.gemm_ref(torch.float64, x.cpu(), w.cpu(), b.cpu() if use_b else None, res=r.cpu() if use_r else None,
+                                    res_first=bool(use_r and rfirst and act), act=act)
+            gemm_ref.assert_within(y, r64.y, r64.bound, f"case {case}: tile {tile} {M}x{N}x{K} act {act} bias {use_b} res {use_r} first {rfirst}, f64 bound")
 
 
 def test_conv_random_shapes_and_tiles(eng, tile_override):
     """Seeded sweep of the implicit-GEMM conv: kernel 1 / 3, stride 1 / 2, virtual concat, fused nearest-2x upsample, ragged maps and
-    channel counts, random tile, shift / residual epilogues -- against torch's conv2d on the same f16 inputs."""
+    channel counts, random tile, shift / residual epilogues -- against torch's conv2d on the same f16 inputs, and per element against the f64 im2col
+    reference and bound of tests/gemm_ref.py."""
     import random
 
     rnd = random.Random(4321)
@@ -156,6 +162,9 @@ def test_conv_random_shapes_and_tiles(eng, tile_override):
         y = eng.conv2d(x, w, b, ksize=k, stride=stride, x2=x2, shift=shift, residual=res, upsample2x=ups)
         want = ref + (shift.float().cpu()[:, None, None, :] if shift is not None else 0) + (res.float().cpu() if res is not None else 0)
         assert_close(y, want, what=f"case {case}: tile {tile} conv k{k} s{stride} ups {ups} {C1}+{C2}->{Cout} @{H}x{W} b{B}")
+        r64 = gemm_ref.conv_ref(torch.float64, x.cpu(), x2.cpu() if C2 else None, w.cpu(), b.cpu(), k, stride, None, ups,
+                                shift.cpu() if shift is not None else None, res.cpu() if res is not None else None)
+        gemm_ref.assert_within(y, r64.y, r64.bound, f"case {case}: tile {tile} conv k{k} s{stride} ups {ups} {C1}+{C2}->{Cout} @{H}x{W} b{B}, f64 bound")
 
 
 DMA_TILES = [t for t in TILES if gemm_tiles()[t].family in (GEMM_DMA, GEMM_RING)]  # the kernels that carry the LayerNorm fold (the library maps the others onto them)
