@@ -250,6 +250,8 @@ SIGNATURES = {
     "gn_openloop_image_metrics": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_openloop_sphere_metrics": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_openloop_action_metrics": (_I32, [_P, _P, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "gn_openloop_exec_actions": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
+    "gn_openloop_exec_metrics": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32]),
     "gn_gather_rows": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_argmax_rows_i32": (_I32, [_P, _P, _P, _I32, _I32]),
     "gn_copy4d": (_I32, [_P, _P, _P, _P, _P, _P, _I32]),

@@ -25,6 +25,7 @@ _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]  # measured: helps attention
 # mode fuses in the backend whatever a source-level `#pragma clang fp contract(off)` says)
 # render.hip, replay_render.hip: likewise -- their blend is numpy's unfused f64 multiply / multiply / add, compared bit for bit
 # openloop.hip: likewise -- its joint sum is stated as one f32 subtraction, multiplication and addition per term
+# (gn_openloop_exec_actions replays ensemble.hip's rule bit for bit, so it is compiled IN ensemble.hip, under that file's flags, not here)
 EXTRA_FLAGS = {"optim8.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"], "replay_render.hip": ["-ffp-contract=off"], "openloop.hip": ["-ffp-contract=off"], "attention.hip": _VGPR_FORM, "attention_stream.hip": _VGPR_FORM, "attention_pwg.hip": _VGPR_FORM, "attention_bwd.hip": _VGPR_FORM, "attention_fp8.hip": _VGPR_FORM}
 
 
@@ -59,7 +60,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "attention_common.h", "attention_dropout.h", "gn_bridge.h", "image_convert.h", "render_common.h", "replay_common.h")] + [os.path.join(HERE, "..", "include", "genima_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "attention_common.h", "attention_dropout.h", "ensemble_common.h", "gn_bridge.h", "image_convert.h", "render_common.h", "replay_common.h")] + [os.path.join(HERE, "..", "include", "genima_hip.h")]
     # the objects are only as good as the flags they were built with: a probe build (GN_HIPCC_EXTRA=-DGN_PP_ABLATIONS ..., some of which give wrong
     # results on purpose) must never be reused by the next normal build, nor the other way round -- the flag set is stamped beside the objects
     stamp = os.path.join(objdir, ".flags")

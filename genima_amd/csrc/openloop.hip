@@ -17,6 +17,10 @@
 //
 // Action kernel.  One thread per (sample, chunk position): the A - 1 joint terms in index order in f32 (this file is compiled without fma
 // contraction, so a term is one subtraction, one multiplication and one addition, each rounded), then the gripper flag.
+//
+// Executed-action kernel (gn_openloop_exec_metrics).  One thread per transition: the action kernel's joint sum and gripper rule on the action an
+// execution mode executes at that step (gn_openloop_exec_actions' output; that kernel is in ensemble.hip, beside the rule it replays), and the
+// joint-space jump from the step before, of the executed and of the demo's action.  A thread reads rows n - 1 and n, writes row n.
 #include "common.h"
 
 namespace {
@@ -217,6 +221,30 @@ __global__ __launch_bounds__(OL_THREADS) void openloop_action_kernel(const f16* 
   o[1] = (((float)h[A - 1] > 0.0f) == (a[A - 1] > 0.5f)) ? 1.0f : 0.0f;
 }
 
+// sum_j scale[j] * |x[j] - y[j]| over the J joints in index order: one subtraction, one multiplication, one addition per term
+__device__ __forceinline__ float ol_joint_l1(const float* x, const float* y, const float* __restrict__ scale, int J) {
+  float sum = 0.0f;
+  for (int j = 0; j < J; ++j) {
+    const float d = fabsf(x[j] - y[j]);
+    sum += scale ? scale[j] * d : d;
+  }
+  return sum;
+}
+
+__global__ __launch_bounds__(OL_THREADS) void openloop_exec_metrics_kernel(const float* __restrict__ exec, const float* __restrict__ demo,
+                                                                           const int32_t* __restrict__ first_tr, const float* __restrict__ joint_scale,
+                                                                           float* __restrict__ out, int N, int A) {
+  const int n = blockIdx.x * OL_THREADS + threadIdx.x;
+  if (n >= N) return;
+  const float *x = exec + (long)n * A, *d = demo + (long)n * A;
+  const bool first = n == 0 || first_tr[n] >= n;  // an episode's first step (a damaged entry above n reads as one too: row n - 1 is never needed then)
+  float* o = out + (long)n * 4;
+  o[0] = ol_joint_l1(x, d, joint_scale, A - 1);
+  o[1] = ((x[A - 1] > 0.0f) == (d[A - 1] > 0.5f)) ? 1.0f : 0.0f;
+  o[2] = first ? 0.0f : ol_joint_l1(x, x - A, joint_scale, A - 1);
+  o[3] = first ? 0.0f : ol_joint_l1(d, d - A, joint_scale, A - 1);
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,6 +309,18 @@ int32_t gn_openloop_action_metrics(gn_ctx* ctx, const void* a_hat, int64_t ld_ha
   const int n = n_valid * T;
   hipLaunchKernelGGL(openloop_action_kernel, dim3((unsigned)cdiv64(n, OL_THREADS)), dim3(OL_THREADS), 0, ctx->stream, (const f16*)a_hat, (long)ld_hat,
                      (long)bs_hat, actions, joint_scale, act_out, T, A, row0, n);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int32_t gn_openloop_exec_metrics(gn_ctx* ctx, const float* exec, const float* demo, const int32_t* first_tr, const float* joint_scale, float* out, int32_t N,
+                                 int32_t A) {
+  GN_REQUIRE(ctx && exec && demo && first_tr && out, "gn_openloop_exec_metrics: null argument");
+  GN_REQUIRE(N > 0 && A >= 2 && (int64_t)N * A <= INT32_MAX, "gn_openloop_exec_metrics: N (%d), A (%d) out of range", N, A);
+  GN_REQUIRE((((uintptr_t)exec | (uintptr_t)demo | (uintptr_t)first_tr | (uintptr_t)joint_scale | (uintptr_t)out) & 3) == 0,
+             "gn_openloop_exec_metrics: misaligned argument");
+  hipLaunchKernelGGL(openloop_exec_metrics_kernel, dim3((unsigned)cdiv64(N, OL_THREADS)), dim3(OL_THREADS), 0, ctx->stream, exec, demo, first_tr, joint_scale,
+                     out, N, A);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

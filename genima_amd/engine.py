@@ -1518,6 +1518,66 @@ class Engine:
                                                   B, T, A, int(row0), B if n_valid is None else int(n_valid), rows), "gn_openloop_action_metrics")
         return out
 
+    @staticmethod
+    def _first_tr_host(who: str, first_tr_host, N: int):
+        """The optional host copy of ``first_tr``: with it an entry outside ``0 .. n`` is refused before anything is launched."""
+        if first_tr_host is None:
+            return
+        import numpy as np
+
+        h = np.asarray(first_tr_host)
+        if h.dtype != np.int32 or h.shape != (N,):
+            raise GenimaHipError(f"{who}: first_tr_host must be int32 [{N}], got {h.dtype} {h.shape}")
+        bad = np.nonzero((h < 0) | (h > np.arange(N)))[0]
+        if bad.size:
+            raise GenimaHipError(f"{who}: first_tr[{int(bad[0])}] = {int(h[bad[0]])} must lie in 0 .. {int(bad[0])}")
+
+    def openloop_exec_actions(self, chunks, first_tr, h: int, temporal_agg: bool = False, m: float = 0.01, *, A: Optional[int] = None, out=None,
+                              n_calls=None, first_tr_host=None):
+        """``gn_openloop_exec_actions``: ``chunks`` f16 [N, T, ld] (row n: the chunk predicted at transition n; the first ``A`` columns count),
+        ``first_tr`` int32 [N] on the device (the first transition of n's episode) -> ``out`` f32 [N, A]: the action an execution mode
+        ``(h, temporal_agg, m)`` executes at every transition, bit for bit what ``action_ensemble`` returns when it is called every ``h`` steps
+        of each episode.  ``n_calls``: int32 [N] or None, the number of calls averaged.  ``first_tr_host``: an int32 numpy copy of
+        ``first_tr``; with it an entry outside ``0 .. n`` is refused, without it the kernel clamps.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("openloop_exec_actions is an eager op: it scores tables that a run has filled")
+        if chunks.dim() != 3 or chunks.dtype != F16 or not chunks.is_cuda or chunks.stride(2) != 1 or chunks.stride(0) != chunks.shape[1] * chunks.stride(1):
+            raise GenimaHipError("openloop_exec_actions: chunks must be f16 [N, T, ld] on the device with contiguous rows of one pitch")
+        N, T = int(chunks.shape[0]), int(chunks.shape[1])
+        A = int(chunks.shape[2]) if A is None else int(A)
+        if not 0 < A <= chunks.shape[2]:
+            raise GenimaHipError(f"openloop_exec_actions: A = {A} columns asked of chunks that hold {int(chunks.shape[2])}")
+        if out is None:
+            out = torch.empty((N, A), dtype=torch.float32, device=chunks.device)
+        for t, dt, shape in ((first_tr, torch.int32, (N,)), (out, torch.float32, (N, A)), (n_calls, torch.int32, (N,))):
+            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                raise GenimaHipError(f"openloop_exec_actions: a contiguous device tensor {dt} {shape} expected")
+        self._first_tr_host("openloop_exec_actions", first_tr_host, N)
+        check(self.lib.gn_openloop_exec_actions(self._ctx, _ptr(chunks), _ptr(first_tr), _ptr(out), _ptr(n_calls), N, T, A, int(chunks.stride(1)), int(h),
+                                                int(bool(temporal_agg)), float(m)), "gn_openloop_exec_actions")
+        return out
+
+    def openloop_exec_metrics(self, exec_actions, demo, first_tr, out=None, *, joint_scale=None, first_tr_host=None):
+        """``gn_openloop_exec_metrics``: ``exec_actions`` f32 [N, A] (``openloop_exec_actions``) against ``demo`` f32 [N, A], the normalised
+        demo action of each transition -> ``out`` f32 [N, 4] = (joint L1 sum over the A - 1 joints, gripper flag, executed jump from the step
+        before, the demo's jump; both jumps 0 at an episode's first step).  ``joint_scale``: f32 [A - 1] or None (= 1).  ``first_tr`` /
+        ``first_tr_host`` as ``openloop_exec_actions`` takes them.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("openloop_exec_metrics is an eager op: it scores tables that a run has filled")
+        if exec_actions.dim() != 2:
+            raise GenimaHipError("openloop_exec_metrics: exec_actions must be f32 [N, A]")
+        N, A = (int(s) for s in exec_actions.shape)
+        if out is None:
+            out = torch.empty((N, 4), dtype=torch.float32, device=exec_actions.device)
+        for t, dt, shape, optional in ((exec_actions, torch.float32, (N, A), False), (demo, torch.float32, (N, A), False), (first_tr, torch.int32, (N,), False),
+                                       (joint_scale, torch.float32, (A - 1,), True), (out, torch.float32, (N, 4), False)):
+            if (t is None and not optional) or (t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape)):
+                raise GenimaHipError(f"openloop_exec_metrics: a contiguous device tensor {dt} {shape} expected")
+        self._first_tr_host("openloop_exec_metrics", first_tr_host, N)
+        check(self.lib.gn_openloop_exec_metrics(self._ctx, _ptr(exec_actions), _ptr(demo), _ptr(first_tr), _ptr(joint_scale), _ptr(out), N, A),
+              "gn_openloop_exec_metrics")
+        return out
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

@@ -16,6 +16,12 @@ here.  What a demo tree does give is, for every transition, t
   against the observation inside the sphere's window, beside the same of the rendered target -- ``gn_openloop_sphere_metrics`` over
   ``render.sphere_windows``.  The in-mask RMSE cannot tell a sphere drawn 6 px off from a blurred or a missing one; these can.
 
+* optionally, what an execution mode would have executed: ``executions=[(execution_horizon, temporal_agg, m), ...]`` keeps every chunk in a
+  device table and replays ``gn_action_ensemble``'s rule over it for every step of every episode -- ``gn_openloop_exec_actions``, bit for bit
+  the controller's own ensembling kernel -- then scores the executed action against the demo's and measures how far it jumps from step to step
+  -- ``gn_openloop_exec_metrics``.  Observations are teacher-forced, so a rollout with horizon h uses exactly the chunks of the transitions at
+  steps 0, h, 2h, ... of each episode: a sweep costs a few launches per setting on top of the pass made anyway.
+
 ``OpenLoopEval(agent, None, ...)`` is the diffusion-only mode (no controller exists while the ControlNet is being fine-tuned):
 ``diffusion_validator`` makes a ``train_loop.TrainLoop`` ``validate`` callable of it.
 
@@ -46,19 +52,45 @@ def _mean(x) -> Optional[float]:
     return float(x.mean()) if x.size else None
 
 
+EXEC_COLUMNS = ("joint_l1", "gripper", "jump", "demo_jump")  # gn_openloop_exec_metrics' four values per transition
+
+
+def parse_execution(text: str):
+    """``H[,agg[,M]]`` -> ``(execution_horizon, temporal_agg, m)``: ``"5"`` -> (5, False, 0.01), ``"5,agg"`` / ``"5,on"`` -> (5, True, 0.01),
+    ``"5,off,0.1"`` -> (5, False, 0.1).  The command lines' ``--execution`` / ``--val_execution``."""
+    parts = [p.strip().lower() for p in str(text).split(",")]
+    if not 1 <= len(parts) <= 3 or not parts[0]:
+        raise ValueError(f"execution setting {text!r}: H[,agg[,M]] expected")
+    try:
+        h = int(parts[0])
+        m = float(parts[2]) if len(parts) > 2 else 0.01
+    except ValueError:
+        raise ValueError(f"execution setting {text!r}: H[,agg[,M]] expected, H an integer and M a number") from None
+    words = {"agg": True, "on": True, "1": True, "true": True, "off": False, "0": False, "false": False, "": False}
+    if len(parts) > 1 and parts[1] not in words:
+        raise ValueError(f"execution setting {text!r}: the second field is one of agg / on / off")
+    return h, words[parts[1]] if len(parts) > 1 else False, m
+
+
 class OpenLoopResult:
     """The per-transition tables of one evaluation, on the host.  ``image`` int64 [N, V, 5] (``IMAGE_COLUMNS``; None for a controller-only
     run); ``actions``: ``{"generated" | "oracle": {"norm" | "rad": f32 [N, T, 2]}}`` -- ``[.., 0]`` the joint L1 SUM over the ``joints`` arm
     joints, normalised or in radians, ``[.., 1]`` the gripper flag; ``episode`` / ``step`` / ``task`` int32 [N] (``task`` indexes ``tasks``).
     ``spheres`` int64 [N, V, S, 17] (``SPHERE_COLUMNS``) with ``windows`` int32 [N, V, S, 4], or both None: the per-sphere table and the
     windows it was summed over.  A sphere is DRAWN where the ground truth changed its window (gt mass > 0); the accessors are NaN elsewhere.
-    Overlapping windows share pixels, so a neighbour's mass can enter a sphere's sums."""
+    Overlapping windows share pixels, so a neighbour's mass can enter a sphere's sums.
+
+    ``executions``: None, or per replayed execution mode ``{"h", "temporal_agg", "m", "K"}`` plus per row kind (``generated`` / ``oracle``)
+    ``{"actions": f32 [N, A], "n_calls": int32 [N], "scores": {"norm" | "rad": f32 [N, 4]}}`` (``EXEC_COLUMNS``: the joint L1 sum and the
+    gripper flag of the EXECUTED action against the demo's, the executed jump from the step before and the demo's own).  ``chunks``: the f16
+    [N, T, A] table per row kind that the modes were replayed from.  ``summary()`` reads neither; ``execution_summary()`` does."""
 
     def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int,
-                 spheres=None, windows=None):
+                 spheres=None, windows=None, executions=None, chunks=None):
         if (spheres is None) != (windows is None):
             raise ValueError("OpenLoopResult: spheres and windows come together (the score needs the windows' diagonals)")
         self.image, self.actions, self.spheres, self.windows = image, actions, spheres, windows
+        self.executions, self.chunks = executions, chunks
         self.episode, self.step, self.task = np.asarray(episode, np.int32), np.asarray(step, np.int32), np.asarray(task, np.int32)
         self.tasks, self.cameras, self.joints, self.H, self.W = list(tasks), list(cameras), int(joints), int(H), int(W)
 
@@ -167,8 +199,50 @@ class OpenLoopResult:
             out["per_task"] = {t: self._summary(self.task == i, found_mass) for i, t in enumerate(self.tasks)}
         return out
 
+    def _execution_block(self, tabs: Dict, h: int, rows: np.ndarray) -> Dict:
+        J = float(self.joints)
+        norm, rad = tabs["scores"]["norm"][rows].astype(np.float64), tabs["scores"]["rad"][rows].astype(np.float64)
+        step = self.step[rows].astype(np.int64)
+        pos = step % h
+        boundary, inside = (pos == 0) & (step > 0), pos > 0
+        out = {"joint_l1_norm": _mean(norm[:, 0] / J), "joint_l1_rad": _mean(rad[:, 0] / J), "gripper_acc": _mean(norm[:, 1]),
+               "mean_calls": _mean(tabs["n_calls"][rows]),
+               "by_position": {"n": [int((pos == p).sum()) for p in range(h)],
+                               "joint_l1_norm": [_mean(norm[pos == p, 0] / J) for p in range(h)],
+                               "joint_l1_rad": [_mean(rad[pos == p, 0] / J) for p in range(h)],
+                               "gripper_acc": [_mean(norm[pos == p, 1]) for p in range(h)]}}
+        for unit, t in (("norm", norm), ("rad", rad)):
+            for where, sel in (("boundary", boundary), ("inside", inside)):
+                out[f"jump_{where}_{unit}"] = _mean(t[sel, 2] / J)
+                out[f"demo_jump_{where}_{unit}"] = _mean(t[sel, 3] / J)
+        return out
+
+    def execution_summary(self) -> Optional[list]:
+        """None without ``executions``; else one dict per replayed mode, in numpy f64: ``h``, ``temporal_agg``, ``m``, ``K``, ``calls_per_step``
+        (= 1 / h: what the mode costs), and per row kind the per-joint L1 of the EXECUTED action (``joint_l1_norm`` / ``joint_l1_rad``), its
+        ``gripper_acc``, ``mean_calls`` (the calls averaged per step), ``by_position``: the three scores and the row count ``n`` by the
+        position ``s % h`` inside the call (how the error grows with the age of the prediction; None where no step has that position),
+        ``jump_boundary_*`` / ``jump_inside_*``: the mean per-joint jump between consecutive executed actions where a new call takes over
+        (``s % h == 0, s > 0``) and inside a call, beside ``demo_jump_*``, the demo's own over the same steps.  ``per_task``: the same per task
+        when there is more than one.  Open-loop like every score here: each chunk was predicted from a demo state."""
+        if self.executions is None:
+            return None
+        every, out = np.ones(len(self), bool), []
+        for ex in self.executions:
+            h = int(ex["h"])
+            d = {"h": h, "temporal_agg": bool(ex["temporal_agg"]), "m": float(ex["m"]), "K": int(ex["K"]), "calls_per_step": 1.0 / h}
+            kinds = [k for k in ("generated", "oracle") if k in ex]
+            for k in kinds:
+                d[k] = self._execution_block(ex[k], h, every)
+            if len(self.tasks) > 1:
+                d["per_task"] = {t: {k: self._execution_block(ex[k], h, self.task == i) for k in kinds} for i, t in enumerate(self.tasks)}
+            out.append(d)
+        return out
+
     def to_json(self, path: str) -> Dict:
         s = self.summary()
+        if self.executions is not None:
+            s = dict(s, executions=self.execution_summary())  # a key of its own: summary() itself is as it was
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as f:
             json.dump(s, f, indent=1)
@@ -201,6 +275,13 @@ class OpenLoopEval:
     nothing that depends on them is scored) and ``action_sequence`` (default: the controller's ``num_queries``, else 20) sets the replay's
     chunk length.  Its image and sphere tables equal those of a run with a controller on the same seed bit for bit.
 
+    ``executions``: None, or a sequence of ``(execution_horizon, temporal_agg, m)`` (``m`` may be left out: 0.01), each checked as
+    ``GenimaACT.set_execution`` checks them.  The controller passed in still has NO mode set: the modes are replayed from its whole chunks.
+    With them ``run()`` also keeps every scored chunk in an f16 device table [N, T, A] per row kind, and after the last batch launches
+    ``gn_openloop_exec_actions`` once and ``gn_openloop_exec_metrics`` twice (normalised, radians) per setting and row kind; the new tables
+    ride in the same device-to-host copy (``OpenLoopResult.executions`` / ``.chunks``).  With None nothing changes: the same launches, the
+    same tables, the same bits.
+
     Per batch, on the device: ``DeviceReplay.sample`` (the frames, proprioception, normalised action chunk, task tokens) -> ``gn_render_spheres``
     over the frames (``full``, ``occupied``) -> the four views on the 2x2 canvas -> the pipeline (``harness.make_prompt`` ids, one generator
     seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image, sphere and action scores -> the controller again on ``full`` -> its action
@@ -209,7 +290,7 @@ class OpenLoopEval:
 
     def __init__(self, diffusion_agent, controller, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None,
                  batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
-                 change_threshold: int = 30, action_sequence: Optional[int] = None):
+                 change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None):
         from .render import load_atlas, load_traj, sphere_windows
 
         if controller is None:
@@ -232,6 +313,19 @@ class OpenLoopEval:
                 raise ValueError(f"OpenLoopEval: action_sequence = {action_sequence} contradicts the controller's num_queries = {T}")
         if int(change_threshold) < 0:
             raise ValueError(f"OpenLoopEval: change_threshold = {change_threshold} must not be negative")
+        self.executions = self.first_tr = self.first_tr_host = None
+        if executions is not None:  # the execution modes to replay over the chunks, checked as GenimaACT.set_execution checks them
+            from .act import check_ensemble_m, execution_slots
+
+            if controller is None:
+                raise ValueError("OpenLoopEval: executions replays the controller's chunks; the diffusion-only mode has none")
+            self.executions = []
+            for ex in executions:
+                ex = tuple(ex)
+                if not 2 <= len(ex) <= 3:
+                    raise ValueError(f"OpenLoopEval: an execution setting is (execution_horizon, temporal_agg[, m]), got {ex!r}")
+                h, K = execution_slots(T, ex[0], bool(ex[1]))
+                self.executions.append({"h": int(h), "temporal_agg": bool(ex[1]), "m": check_ensemble_m(ex[2] if len(ex) > 2 else 0.01), "K": int(K)})
         self.change_threshold = int(change_threshold)
         self.agent, self.controller, self.cameras, self.V = diffusion_agent, controller, tuple(cameras), len(cameras)
         if diffusion_agent is not None and self.V != 4:
@@ -287,6 +381,11 @@ class OpenLoopEval:
         self.prompts = [harness.make_prompt(d) for d in rp.descriptions]
         self.prompt_ids = torch.cat([diffusion_agent.pipe.encode_ids([p]) for p in self.prompts]) if diffusion_agent is not None else None
         self._n_index = torch.arange(rp.N, dtype=torch.int64, device=dev)
+        if self.executions is not None:  # the first transition of each one's episode, host and device
+            self.first_tr_host = np.ascontiguousarray((np.arange(rp.N) - step).astype(np.int32))
+            self.first_tr = torch.from_numpy(self.first_tr_host).to(dev)
+            if tuple(rp.action.shape) != (rp.N, rp.A):
+                raise ValueError(f"OpenLoopEval: the replay's demo actions are {tuple(rp.action.shape)}, expected {(rp.N, rp.A)}")
 
     # ---- the steps of one batch (the tests recompute a batch from these inputs)
     def batch_indices(self, start: int) -> np.ndarray:
@@ -348,7 +447,30 @@ class OpenLoopEval:
                 tabs["generated"] = act()
             tabs["image"] = torch.zeros((N, self.V, 5), dtype=torch.int64, device=dev)
             tabs["spheres"] = torch.zeros((N, self.V, int(self.windows.shape[2]), 17), dtype=torch.int64, device=dev)
+        if self.executions is not None:  # every scored chunk, as the controller's head wrote it
+            tabs["chunks"] = {k: torch.zeros((N, T, self.A), dtype=torch.float16, device=dev) for k in ("generated", "oracle") if k in tabs}
         return tabs
+
+    def _keep_chunk(self, a_hat, tabs, kind: str, row0: int, n_valid: int):
+        if "chunks" in tabs:
+            tabs["chunks"][kind][row0: row0 + n_valid].copy_(a_hat[:n_valid, : self.T, : self.A])
+
+    def replay_executions(self, tabs) -> Optional[list]:
+        """After the last batch: per setting and row kind, the executed action of every transition (``gn_openloop_exec_actions`` over the chunk
+        table) and its scores in both units (``gn_openloop_exec_metrics``).  Device tensors; nothing is read back."""
+        if self.executions is None:
+            return None
+        E, dev, N, out = self.E, self.E.device, self.N, []
+        for ex in self.executions:
+            d = dict(ex)
+            for kind, chunks in tabs["chunks"].items():
+                n_calls = torch.empty((N,), dtype=torch.int32, device=dev)
+                acts = E.openloop_exec_actions(chunks, self.first_tr, ex["h"], ex["temporal_agg"], ex["m"], n_calls=n_calls, first_tr_host=self.first_tr_host)
+                d[kind] = {"actions": acts, "n_calls": n_calls,
+                           "scores": {"norm": E.openloop_exec_metrics(acts, self.replay.action, self.first_tr),
+                                      "rad": E.openloop_exec_metrics(acts, self.replay.action, self.first_tr, joint_scale=self.joint_std)}}
+            out.append(d)
+        return out
 
     def run_batch(self, start: int, tabs, generator) -> None:
         """One evaluator batch: steps 1 - 7 for transitions ``start ..``, everything on the device, nothing read back."""
@@ -368,9 +490,11 @@ class OpenLoopEval:
                                                batch["windows"], tabs["spheres"], threshold=self.change_threshold, row0=start, n_valid=n_valid)
                 if self.controller is not None:
                     self._score_actions(a_hat, batch, tabs["generated"], start, n_valid)  # before the oracle pass overwrites the program's chunk
+                    self._keep_chunk(a_hat, tabs, "generated", start, n_valid)
             if self.controller is not None:
                 a_hat = self._chunk(batch["full"].view(B, self.V, self.H, self.W, 3), batch)
                 self._score_actions(a_hat, batch, tabs["oracle"], start, n_valid)
+                self._keep_chunk(a_hat, tabs, "oracle", start, n_valid)
 
     def run(self) -> OpenLoopResult:
         tabs = self._tables()
@@ -379,12 +503,31 @@ class OpenLoopEval:
             self.run_batch(start, tabs, generator)
         # the one device-to-host copy: every table as bytes of one buffer
         flat = [tabs[k][m] for k in ("generated", "oracle") if k in tabs for m in ("norm", "rad")] + [tabs[k] for k in ("image", "spheres") if k in tabs]
+        n_before = len(flat)
+        execs = self.replay_executions(tabs)
+        if execs is not None:  # appended: 4-byte tables first, the f16 chunk tables last (every table then starts on its own type's grid)
+            kinds = list(tabs["chunks"])
+            for d in execs:
+                for k in kinds:
+                    flat += [d[k]["actions"], d[k]["n_calls"], d[k]["scores"]["norm"], d[k]["scores"]["rad"]]
+            flat += [tabs["chunks"][k] for k in kinds]
         host = torch.cat([t.reshape(-1).view(torch.uint8) for t in flat]).cpu().numpy()
+        np_of = {torch.int64: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.float16: np.float16}
         out, o = [], 0
         for t in flat:
             n = t.numel() * t.element_size()
-            out.append(host[o: o + n].view(np.int64 if t.dtype == torch.int64 else np.float32).reshape(tuple(t.shape)).copy())
+            out.append(host[o: o + n].view(np_of[t.dtype]).reshape(tuple(t.shape)).copy())
             o += n
+        executions = chunks = None
+        if execs is not None:
+            executions, k = [], n_before
+            for ex in self.executions:
+                d = dict(ex)
+                for kind in kinds:
+                    d[kind] = {"actions": out[k], "n_calls": out[k + 1], "scores": {"norm": out[k + 2], "rad": out[k + 3]}}
+                    k += 4
+                executions.append(d)
+            chunks = {kind: out[k + i] for i, kind in enumerate(kinds)}
         actions, k = {}, 0
         for name in ("generated", "oracle"):
             if name in tabs:
@@ -392,24 +535,38 @@ class OpenLoopEval:
                 k += 2
         image, spheres = (out[k], out[k + 1]) if "image" in tabs else (None, None)
         return OpenLoopResult(image, actions, self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1, self.H, self.W,
-                              spheres=spheres, windows=self.windows_host if spheres is not None else None)
+                              spheres=spheres, windows=self.windows_host if spheres is not None else None, executions=executions, chunks=chunks)
 
 
-def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None):
+def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None,
+                         execution=None):
     """-> a ``validate`` callable for ``ControllerTrainLoop``: ``(agent, epochs_done) -> {"select", "joint_l1_norm", "joint_l1_rad",
     "gripper_acc", "n"}``.  It scores the controller ALONE on held-out demos with the ground-truth targets (the oracle row: sample, render,
     controller; no diffusion agent), reads the agent's current weights and changes none; ``select`` is the normalised joint L1, so
-    ``best.pt`` follows its minimum.  The demo set is loaded onto the device at the first call and kept."""
+    ``best.pt`` follows its minimum.  The demo set is loaded onto the device at the first call and kept.
+
+    ``execution = (execution_horizon, temporal_agg[, m])``: the mode the controller will be run with.  ``select`` is then the normalised joint
+    L1 of the EXECUTED action under that mode (``OpenLoopResult.execution_summary``), and the dict gains ``exec_joint_l1_norm``,
+    ``exec_joint_l1_rad``, ``exec_gripper_acc``, ``exec_jump_boundary_norm``, ``exec_jump_inside_norm`` (None where no step qualifies) and
+    ``exec_calls_per_step``.  Without it the dict is as before."""
     state: Dict = {}
 
     def validate(agent, epochs_done: int) -> Dict[str, float]:
         ev = state.get("ev")
         if ev is None or ev.controller is not agent:
             ev = state["ev"] = OpenLoopEval(None, agent, episodes, cameras, render_cfg=render_cfg, stats=stats, tokenizer=tokenizer,
-                                            batch_size=batch_size, engine=engine)
-        s = ev.run().summary()["oracle"]
-        return {"select": s["joint_l1_norm"], "joint_l1_norm": s["joint_l1_norm"], "joint_l1_rad": s["joint_l1_rad"],
-                "gripper_acc": s["gripper_acc"], "n": float(len(ev.replay))}
+                                            batch_size=batch_size, engine=engine, executions=None if execution is None else [execution])
+        res = ev.run()
+        s = res.summary()["oracle"]
+        out = {"select": s["joint_l1_norm"], "joint_l1_norm": s["joint_l1_norm"], "joint_l1_rad": s["joint_l1_rad"],
+               "gripper_acc": s["gripper_acc"], "n": float(len(ev.replay))}
+        if execution is not None:
+            x = res.execution_summary()[0]
+            o = x["oracle"]
+            out.update(select=o["joint_l1_norm"], exec_joint_l1_norm=o["joint_l1_norm"], exec_joint_l1_rad=o["joint_l1_rad"],
+                       exec_gripper_acc=o["gripper_acc"], exec_jump_boundary_norm=o["jump_boundary_norm"], exec_jump_inside_norm=o["jump_inside_norm"],
+                       exec_calls_per_step=x["calls_per_step"])
+        return out
 
     return validate
 

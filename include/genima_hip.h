@@ -867,6 +867,37 @@ int32_t gn_openloop_sphere_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_
                                    const int32_t* win_host, uint64_t* sph_out, int32_t B, int32_t V, int32_t H, int32_t W, int32_t S, int32_t tiled,
                                    int32_t threshold, int32_t row0, int32_t n_valid, int32_t rows);
 
+/* Open-loop scores of an execution mode (execution_horizon h, temporal_agg, m): what gn_action_ensemble would have executed at every step of
+ * every held-out episode, replayed from the chunks an evaluation computes anyway.  Observations are teacher-forced, so a rollout with horizon h
+ * uses exactly the chunks of the transitions at steps 0, h, 2h, ... of each episode.
+ *
+ * gn_openloop_exec_actions, per (transition n, action dimension a), one thread each:
+ *   chunks    f16 [N][T][ld], ld >= A the row pitch, only the first A columns are read: row n is the chunk predicted at transition n
+ *   first_tr  int32 [N], DEVICE memory: the index of the first transition of n's episode.  The kernel clamps it into [0, n]
+ *   exec      f32 [N][A];  n_calls  int32 [N] or NULL: the number of taking-part calls
+ *   With f = first_tr[n], the step s = n - f and the call that executes it starting at t = s - s % h, the taking-part calls are {t} without
+ *   temporal_agg, and with it u = t - j h for j = floor((T - 1 - (s - t)) / h) .. 0, keeping u >= 0: oldest first.  Then
+ *     exec[n][a] = sum_i w_i chunks[f + u_i][s - u_i][a] / sum_i w_i,   w_0 = 1, w_i = expf(-m i),
+ *   in f32 throughout, accumulated from the oldest call to the newest: bit for bit the row gn_action_ensemble_f16 returns for step s when it is
+ *   called at t = 0, h, 2h, ... with K = ceil(T / h) (K = 1 without temporal_agg) after a reset -- the two kernels share the weighted sum and
+ *   the compile flags.  Every read of chunks stays inside rows first_tr[n] .. n.
+ *
+ * gn_openloop_exec_metrics, per transition n, one thread each:
+ *   exec      f32 [N][A] (the above);  demo f32 [N][A]: the normalised demo action of each transition (row 0 of its chunk);  first_tr as above
+ *   joint_scale  f32 [A - 1] or NULL (= 1)
+ *   out       f32 [N][4]:
+ *     [0] = sum over j < A - 1 of joint_scale[j] * |exec[n][j] - demo[n][j]|, as gn_openloop_action_metrics sums it (one f32 subtraction, one
+ *           multiplication, one addition per term, in index order, no fused multiply-add)
+ *     [1] = 1.0 where (exec[n][A - 1] > 0) == (demo[n][A - 1] > 0.5), else 0.0: gn_openloop_action_metrics' gripper rule
+ *     [2] = the executed jump sum_j joint_scale[j] * |exec[n][j] - exec[n - 1][j]|, summed alike; 0 at an episode's first step (first_tr[n] >= n)
+ *     [3] = the same jump of demo
+ * Both are eager only, deterministic (plain loads and stores, no atomics) and order-independent.  Refused, launching nothing and leaving the
+ * outputs as they were: a NULL pointer other than n_calls / joint_scale, N or T <= 0, A < 2, ld < A, h outside 1 .. T, m < 0 or NaN. */
+int32_t gn_openloop_exec_actions(gn_ctx* ctx, const void* chunks, const int32_t* first_tr, float* exec, int32_t* n_calls, int32_t N, int32_t T,
+                                 int32_t A, int32_t ld, int32_t h, int32_t temporal_agg, float m);
+int32_t gn_openloop_exec_metrics(gn_ctx* ctx, const float* exec, const float* demo, const int32_t* first_tr, const float* joint_scale, float* out, int32_t N,
+                                 int32_t A);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */

@@ -11,9 +11,15 @@ that ends in a stream synchronise.  The oracle controller pass alone is timed th
 and ``gn_render_spheres`` -- by device events (5 x 100 launches).  The claim checked: (b) costs no more than (a) plus the run's own min-max
 spread of (a).
 
+With ``--exec_grid`` it also times whole runs (``OpenLoopEval.run``: every batch plus the final device-to-host copy) of two evaluators over the
+same agents that alternate inside every repetition -- one without ``executions`` (what the evaluator did before execution modes could be
+replayed) and one with the grid (h, temporal_agg, m) in {1, 5, 10, 20} x {off, on} x {0.01} -- and the two replay launches
+(``gn_openloop_exec_actions`` with h = 5 and temporal_agg, ``gn_openloop_exec_metrics``) by device events.  The claim checked there: the grid
+adds a few launch-shaped kernels per setting and nothing to a run without it.
+
 Prints one JSON line; needs an MI355X.
 
-    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12]
+    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid]
         [--sphere_textures tests/golden/sphere_textures] [--out profiles/openloop_b8.json]
 """
 import argparse
@@ -41,6 +47,7 @@ def main():
     ap.add_argument("--length", type=int, default=12)
     ap.add_argument("--family", default="sd-turbo")
     ap.add_argument("--sphere_textures", default=os.path.join(HERE, "tests", "golden", "sphere_textures"))
+    ap.add_argument("--exec_grid", action="store_true", help="also time whole runs without and with the 8-setting execution grid, and the two replay launches")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -126,6 +133,32 @@ def main():
                 "action_metrics_us": lambda: E.openloop_action_metrics(a_hat, batch["action"], tabs["generated"]["rad"], joint_scale=ev.joint_std),
                 "render_spheres_us": lambda: E.render_spheres(v["cams"], v["spheres"], v["tex_index"], v["count"], ev.atlas, S, S, ev.samples, bg=frames,
                                                               full=batch["full"], occupied=batch["occupied"])}
+    if args.exec_grid:
+        grid = [(h, agg, 0.01) for h in (1, 5, 10, 20) for agg in (False, True)]
+        ev_grid = OpenLoopEval(dagent, controller, eps, cams, render_cfg=rcfg, stats=(P.action_stats(demos), P.proprio_stats(demos)), tokenizer=tokens,
+                               batch_size=B, engine=E, executions=grid)
+        runs = {"run_plain": ev.run, "run_with_grid": ev_grid.run}
+        rms = {k: [] for k in runs}
+        for i in range(args.warmup + args.reps):
+            for k, fn in runs.items():
+                E.synchronize()
+                t = time.perf_counter()
+                fn()  # ends in its device-to-host copy
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    rms[k].append((time.perf_counter() - t) * 1e3)
+        for k in runs:
+            res[k] = stats(rms[k])
+        res["exec_grid"] = [list(g) for g in grid]
+        res["grid_minus_plain_ms"] = round(res["run_with_grid"]["median_ms"] - res["run_plain"]["median_ms"], 4)
+        res["plain_spread_ms"] = round(res["run_plain"]["max_ms"] - res["run_plain"]["min_ms"], 4)
+        res["grid_launches_per_run"] = 3 * 2 * len(grid)  # per setting and row kind: one replay, two scores
+        xt = ev_grid._tables()
+        ev_grid.run_batch(0, xt, gen)
+        x_acts = E.openloop_exec_actions(xt["chunks"]["oracle"], ev_grid.first_tr, 5, True, 0.01)
+        x_out = torch.empty((ev.N, 4), dtype=torch.float32, device=E.device)
+        launches["exec_actions_us"] = lambda: E.openloop_exec_actions(xt["chunks"]["oracle"], ev_grid.first_tr, 5, True, 0.01, out=x_acts)
+        launches["exec_metrics_us"] = lambda: E.openloop_exec_metrics(x_acts, ev_grid.replay.action, ev_grid.first_tr, x_out, joint_scale=ev_grid.joint_std)
     for name, launch in launches.items():
         us = []
         for _ in range(5):

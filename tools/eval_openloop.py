@@ -12,7 +12,9 @@ are the SCENE frames the diffusion agent sees at run time; ``tools/render_datase
 ``demo.npz``).  ``--stats_dir`` holds the TRAINING run's ``action_stats.json`` / ``proprio_stats.json``: the held-out demos are normalised with
 those, never with their own.  Prints the summary and writes it as JSON; with a diffusion agent it carries ``image.spheres``, the per-sphere
 location / mass / spread / colour scores (``--change_threshold`` sets their threshold against the observation).  ``--no_controller`` scores the
-diffusion checkpoint alone (no ``--controller_snapshot`` / ``--stats_dir`` needed: the mode a ControlNet fine-tune validates in).  Open-loop error is not a success rate: every chunk is predicted from
+diffusion checkpoint alone (no ``--controller_snapshot`` / ``--stats_dir`` needed: the mode a ControlNet fine-tune validates in).
+``--execution H[,agg[,M]]`` (repeatable; ``5``, ``5,agg``, ``5,agg,0.01``) also replays that execution mode over the run's chunks and adds, under
+``executions``, the error and the step-to-step jump of the EXECUTED actions (``OpenLoopResult.execution_summary``).  Open-loop error is not a success rate: every chunk is predicted from
 a demo state, nothing is executed and no error compounds."""
 import argparse
 import json
@@ -47,10 +49,21 @@ def parse(argv=None):
     ap.add_argument("--num_inference_steps", type=int, default=5)
     ap.add_argument("--guidance_scale", type=float, default=0.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--execution", action="append", default=None, metavar="H[,agg[,M]]",
+                    help="also score the actions an execution mode would execute: horizon H, 'agg' for temporal_agg, weight decay M (default 0.01); repeatable")
     ap.add_argument("--out", default="openloop.json")
     a = ap.parse_args(argv)
     if not a.no_controller and not (a.controller_snapshot and a.stats_dir):
         ap.error("--controller_snapshot and --stats_dir are required unless --no_controller is given")
+    if a.execution is not None:
+        from genima_amd.openloop import parse_execution
+
+        if a.no_controller:
+            ap.error("--execution replays the controller's chunks: it cannot be combined with --no_controller")
+        try:
+            a.execution = [parse_execution(e) for e in a.execution]
+        except ValueError as err:
+            ap.error(str(err))
     return a
 
 
@@ -90,7 +103,7 @@ def main(argv=None):
         stats = P.load_stats(a.stats_dir)
     ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=stats, tokenizer=tokenizer, batch_size=a.batch_size,
                       num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed, change_threshold=a.change_threshold,
-                      action_sequence=a.action_sequence)
+                      action_sequence=a.action_sequence, executions=a.execution)
     print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
     summary = ev.run().to_json(a.out)
     print(json.dumps(summary, indent=1))

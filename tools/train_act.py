@@ -19,7 +19,7 @@ fresh texture and blend factor for every frame of every batch:
 With ``--val_root DIR`` (a second tree of the same layout whose episodes hold the scene frames, ``demo.npz`` and ``traj.npz``) every snapshot
 is scored on the first ``--val_demos`` held-out demos of each task -- the controller alone on the rendered ground-truth targets
 (``genima_amd.openloop.controller_validator``) -- into ``validation.jsonl``, and the snapshot with the lowest normalised joint L1 is kept as
-``best.pt``.
+``best.pt``.  ``--val_execution H[,agg[,M]]`` ranks by the joint L1 of the actions executed under that execution mode instead.
 
 Writes
 ``<work_dir>/snapshots/<experiment_name>/{latest.pt, <epoch>.pt, action_stats.json, proprio_stats.json}``.  Nothing from RoboBase or RLBench is
@@ -61,6 +61,8 @@ def parse(argv=None):
     ap.add_argument("--val_root", default=None, help="held-out demo tree: score every snapshot on it (validation.jsonl) and keep the best as best.pt")
     ap.add_argument("--val_demos", type=int, default=5, help="held-out demos per task")
     ap.add_argument("--val_action_horizon", type=int, default=20, help="render.yaml's horizon of the joint targets drawn for validation")
+    ap.add_argument("--val_execution", default=None, metavar="H[,agg[,M]]",
+                    help="rank snapshots by the joint L1 of the actions EXECUTED under this mode (horizon H, 'agg' for temporal_agg, weight decay M) instead of whole chunks")
     return ap.parse_args(argv)
 
 
@@ -111,8 +113,9 @@ def main(argv=None):
     validate = None
     if a.val_root:
         from genima_amd import render as R
-        from genima_amd.openloop import controller_validator
+        from genima_amd.openloop import controller_validator, parse_execution
 
+        execution = parse_execution(a.val_execution) if a.val_execution else None
         vcfg = R.RenderConfig(image_width=a.image_size, image_height=a.image_size, action_horizon=a.val_action_horizon, texture_dir=a.sphere_textures)
         val_eps = P.list_episodes(a.val_root, a.tasks, a.val_demos)
         for ep in val_eps:
@@ -121,7 +124,7 @@ def main(argv=None):
             if not os.path.exists(os.path.join(ep, "traj.npz")):
                 R.save_traj(os.path.join(ep, "traj.npz"), R.traj_from_low_dim_obs(os.path.join(ep, "low_dim_obs.pkl"), vcfg.cameras))
         validate = controller_validator(val_eps, a.cameras, render_cfg=vcfg, stats=(replay.action_stats, replay.proprio_stats), tokenizer=tokenizer,
-                                        batch_size=a.batch_size, engine=replay.E)
+                                        batch_size=a.batch_size, engine=replay.E, execution=execution)
     ControllerTrainLoop(agent, replay, a.work_dir, a.experiment_name, a.num_train_epochs, a.checkpoint_every, a.num_checkpoints, log=log,
                         cfg={k: v for k, v in vars(a).items()}, validate=validate).train()
 
