@@ -185,7 +185,7 @@ class RenderDesc(C.Structure):
 # the structs gn_desc_sizeof(which) reports, in its order: load() refuses a library whose sizes differ (tests/test_abi.py checks the same list)
 DESC_CLASSES = (GemmDesc, AttnDesc, GroupNormDesc, TBlockDesc, ConvGnDesc, StatsSink, NormIn, NormOut, ConvPatchDesc, ReplayGatherDesc, ReplayRenderDesc)
 
-_P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_P, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); every symbol include/genima_hip.h declares (tests/test_abi.py checks the two agree)
 SIGNATURES = {
@@ -252,6 +252,7 @@ SIGNATURES = {
     "gn_openloop_action_metrics": (_I32, [_P, _P, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_openloop_exec_actions": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_openloop_exec_metrics": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32]),
+    "gn_openloop_triangulate": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _I32, _I32, _I32, _I32]),
     "gn_gather_rows": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_argmax_rows_i32": (_I32, [_P, _P, _P, _I32, _I32]),
     "gn_copy4d": (_I32, [_P, _P, _P, _P, _P, _P, _I32]),

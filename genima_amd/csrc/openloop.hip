@@ -21,6 +21,11 @@
 // Executed-action kernel (gn_openloop_exec_metrics).  One thread per transition: the action kernel's joint sum and gripper rule on the action an
 // execution mode executes at that step (gn_openloop_exec_actions' output; that kernel is in ensemble.hip, beside the rule it replays), and the
 // joint-space jump from the step before, of the executed and of the demo's action.  A thread reads rows n - 1 and n, writes row n.
+//
+// Triangulation kernel (gn_openloop_triangulate).  One thread per (transition, group, kind), one launch over the whole table after the last
+// batch: the thread walks the at most 8 views twice -- once to sum the normal equations of the closest point to the used rays, once for the
+// residuals at the solved point -- and rebuilds each ray from the tables both times instead of keeping eight of them in scratch.  All f64, no
+// contraction (this file's flag), the 3x3 system through its adjugate in one written order; the thread stores its own eight values.
 #include "common.h"
 
 namespace {
@@ -245,6 +250,115 @@ __global__ __launch_bounds__(OL_THREADS) void openloop_exec_metrics_kernel(const
   o[3] = first ? 0.0f : ol_joint_l1(d, d - A, joint_scale, A - 1);
 }
 
+// ---- triangulation (gn_openloop_triangulate) ----
+constexpr int OL_TRI_COLS = 8;
+
+struct ol_ray {
+  double o[3], d[3];  // origin (the camera position), unit direction
+  double u, v;        // the observation: the centroid in image coordinates
+  double fx, fy, cx, cy, R[9];
+};
+
+// The observation and the ray of view v for group (n, g), or false where the view is not used.  Called by both passes over the views: the
+// same statements on the same inputs, so both see the same bits.  A slot outside [0, S) reads as -1: no table value becomes an address
+// unclamped.
+__device__ __forceinline__ bool ol_tri_ray(const unsigned long long* __restrict__ sph, const int32_t* __restrict__ win, const float* __restrict__ cams,
+                                           const int32_t* __restrict__ slot, long n, int g, int v, int kind, double min_ratio, int V, int S, int G,
+                                           ol_ray& r) {
+  const int s = slot[(n * G + g) * V + v];
+  if (s < 0 || s >= S) return false;
+  const long row = (n * V + v) * S + s;
+  const unsigned long long* q = sph + row * OL_SPH_COLS;
+  const double gen_m = (double)q[1], gt_m = (double)q[5];
+  if (!(gt_m > 0.0)) return false;
+  if (kind == 0 && !(gen_m > 0.0 && gen_m >= min_ratio * gt_m)) return false;
+  const int o = kind == 0 ? 1 : 5;
+  const double m = kind == 0 ? gen_m : gt_m;
+  const int32_t* w = win + row * 4;
+  r.u = ((double)w[0] + (double)q[o + 1] / m) + 0.5;
+  r.v = ((double)w[1] + (double)q[o + 2] / m) + 0.5;
+  const float* c = cams + (n * V + v) * 18;
+  r.fx = (double)c[0], r.fy = (double)c[1], r.cx = (double)c[2], r.cy = (double)c[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r.R[i * 3 + j] = (double)c[4 + i * 4 + j];
+    r.o[i] = (double)c[4 + i * 4 + 3];
+  }
+  const double dx = (r.u - r.cx) / r.fx, dy = (r.cy - r.v) / r.fy;  // gn_render_spheres' ray through (u, v): pose * (dx, dy, -1)
+  double e[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) e[i] = (r.R[i * 3] * dx + r.R[i * 3 + 1] * dy) - r.R[i * 3 + 2];
+  const double len = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r.d[i] = e[i] / len;
+  return true;
+}
+
+__global__ __launch_bounds__(OL_THREADS) void openloop_triangulate_kernel(const unsigned long long* __restrict__ sph, const int32_t* __restrict__ win,
+                                                                          const float* __restrict__ cams, const int32_t* __restrict__ slot,
+                                                                          const double* __restrict__ centre, double* __restrict__ out, double min_ratio,
+                                                                          double min_det, int N, int V, int S, int G) {
+  const long i = (long)blockIdx.x * OL_THREADS + threadIdx.x;  // (n, g, kind)
+  if (i >= (long)N * G * 2) return;
+  const int kind = (int)(i & 1), g = (int)((i >> 1) % G);
+  const long n = (i >> 1) / G;
+  // A = sum (I - d d^T), b = sum (I - d d^T) o, over the used views in index order
+  double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0, b0 = 0, b1 = 0, b2 = 0;
+  int used = 0;
+  ol_ray r;
+  for (int v = 0; v < V; ++v) {
+    if (!ol_tri_ray(sph, win, cams, slot, n, g, v, kind, min_ratio, V, S, G, r)) continue;
+    ++used;
+    const double t = (r.d[0] * r.o[0] + r.d[1] * r.o[1]) + r.d[2] * r.o[2];
+    a00 += 1.0 - r.d[0] * r.d[0];
+    a01 -= r.d[0] * r.d[1];
+    a02 -= r.d[0] * r.d[2];
+    a11 += 1.0 - r.d[1] * r.d[1];
+    a12 -= r.d[1] * r.d[2];
+    a22 += 1.0 - r.d[2] * r.d[2];
+    b0 += r.o[0] - t * r.d[0];
+    b1 += r.o[1] - t * r.d[1];
+    b2 += r.o[2] - t * r.d[2];
+  }
+  const double nan = __longlong_as_double(0x7FF8000000000000LL);
+  double res[OL_TRI_COLS] = {(double)used, nan, nan, nan, nan, nan, nan, 0.0};
+  if (used >= 2) {
+    // the adjugate of the symmetric A, one fixed order of operations
+    const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+    const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+    const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+    const double m = ((a00 + a11) + a22) / 3.0;
+    const double cond = det / ((m * m) * m);
+    res[7] = cond;
+    if (cond >= min_det) {  // a NaN stays unsolved
+      const double x[3] = {((c00 * b0 + c01 * b1) + c02 * b2) / det, ((c01 * b0 + c11 * b1) + c12 * b2) / det, ((c02 * b0 + c12 * b1) + c22 * b2) / det};
+      const double* c = centre + (n * G + g) * 3;
+      const double e0 = x[0] - c[0], e1 = x[1] - c[1], e2 = x[2] - c[2];
+      double ray2 = 0.0, px2 = 0.0;
+      for (int v = 0; v < V; ++v) {
+        if (!ol_tri_ray(sph, win, cams, slot, n, g, v, kind, min_ratio, V, S, G, r)) continue;
+        const double w0 = x[0] - r.o[0], w1 = x[1] - r.o[1], w2 = x[2] - r.o[2];
+        const double t = (w0 * r.d[0] + w1 * r.d[1]) + w2 * r.d[2];
+        const double p0 = w0 - t * r.d[0], p1 = w1 - t * r.d[1], p2 = w2 - t * r.d[2];
+        ray2 += (p0 * p0 + p1 * p1) + p2 * p2;
+        // the reprojection: render.sphere_windows' formulas, p = R^T (x - o), z = -p.z
+        const double q0 = (r.R[0] * w0 + r.R[3] * w1) + r.R[6] * w2, q1 = (r.R[1] * w0 + r.R[4] * w1) + r.R[7] * w2;
+        const double z = -((r.R[2] * w0 + r.R[5] * w1) + r.R[8] * w2);
+        const double du = (r.cx + r.fx * q0 / z) - r.u, dv = (r.cy - r.fy * q1 / z) - r.v;
+        px2 += z > 0.0 ? du * du + dv * dv : nan;  // a point at or behind a used camera has no reprojection
+      }
+      res[1] = x[0], res[2] = x[1], res[3] = x[2];
+      res[4] = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+      res[5] = sqrt(ray2 / (double)used);
+      res[6] = sqrt(px2 / (double)used);
+    }
+  }
+  double* o = out + i * OL_TRI_COLS;
+#pragma unroll
+  for (int k = 0; k < OL_TRI_COLS; ++k) o[k] = res[k];
+}
+
 }  // namespace
 
 extern "C" {
@@ -321,6 +435,35 @@ int32_t gn_openloop_exec_metrics(gn_ctx* ctx, const float* exec, const float* de
              "gn_openloop_exec_metrics: misaligned argument");
   hipLaunchKernelGGL(openloop_exec_metrics_kernel, dim3((unsigned)cdiv64(N, OL_THREADS)), dim3(OL_THREADS), 0, ctx->stream, exec, demo, first_tr, joint_scale,
                      out, N, A);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int32_t gn_openloop_triangulate(gn_ctx* ctx, const uint64_t* sph, const int32_t* win, const float* cams, const int32_t* slot, const double* centre,
+                                const int32_t* slot_host, const int32_t* win_host, double* out, double min_ratio, double min_det, int32_t N, int32_t V,
+                                int32_t S, int32_t G) {
+  GN_REQUIRE(ctx && sph && win && cams && slot && centre && out, "gn_openloop_triangulate: null argument");
+  GN_REQUIRE(N >= 0 && V >= 2 && V <= 8 && S >= 1 && S <= 8 && G >= 1 && G <= 8 && (int64_t)N * V * S * OL_SPH_COLS <= INT32_MAX,
+             "gn_openloop_triangulate: N (%d) must not be negative, V (%d) must lie in [2, 8], S (%d) and G (%d) in [1, 8]", N, V, S, G);
+  GN_REQUIRE(min_ratio >= 0.0 && min_det > 0.0, "gn_openloop_triangulate: min_ratio (%g) must be >= 0 and min_det (%g) > 0", min_ratio, min_det);
+  GN_REQUIRE((((uintptr_t)sph | (uintptr_t)centre | (uintptr_t)out) & 7) == 0 &&
+                 (((uintptr_t)win | (uintptr_t)cams | (uintptr_t)slot | (uintptr_t)slot_host | (uintptr_t)win_host) & 3) == 0,
+             "gn_openloop_triangulate: sph, centre and out must be 8-byte, win, cams, slot and the host copies 4-byte aligned");
+  if (slot_host) {
+    for (int64_t i = 0; i < (int64_t)N * G * V; ++i)
+      GN_REQUIRE(slot_host[i] >= -1 && slot_host[i] < S, "gn_openloop_triangulate: slot %ld = %d must lie in [-1, S = %d)", (long)i, slot_host[i], S);
+  }
+  if (win_host) {
+    for (int64_t i = 0; i < (int64_t)N * V * S; ++i) {
+      const int32_t* q = win_host + i * 4;
+      GN_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[2] >= q[0] && q[3] >= q[1] && q[2] - q[0] <= OL_WIN_MAX && q[3] - q[1] <= OL_WIN_MAX,
+                 "gn_openloop_triangulate: window %ld = (%d, %d, %d, %d) must have 0 <= x0 <= x1, 0 <= y0 <= y1 and at most %d per side", (long)i, q[0], q[1],
+                 q[2], q[3], OL_WIN_MAX);
+    }
+  }
+  if (N == 0) return GN_OK;
+  hipLaunchKernelGGL(openloop_triangulate_kernel, dim3((unsigned)cdiv64((int64_t)N * G * 2, OL_THREADS)), dim3(OL_THREADS), 0, ctx->stream,
+                     (const unsigned long long*)sph, win, cams, slot, centre, out, min_ratio, min_det, N, V, S, G);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

@@ -1578,6 +1578,34 @@ class Engine:
               "gn_openloop_exec_metrics")
         return out
 
+    def openloop_triangulate(self, sph, win, cams, slot, centre, out=None, *, min_ratio: float = 0.5, min_det: float = 1e-6, slot_host=None, win_host=None):
+        """``gn_openloop_triangulate``: ``sph`` int64 [N, V, S, 17] (``openloop_sphere_metrics``' finished table), ``win`` int32 [N, V, S, 4],
+        ``cams`` f32 [N, V, 18], ``slot`` int32 [N, G, V] (the sphere slot of view v that shows group g, or -1), ``centre`` f64 [N, G, 3], all
+        on the device -> ``out`` f64 [N, G, 2, 8]: per group and kind (0 generated, 1 ground truth) the number of views used, the point
+        closest to their rays, its distance to ``centre``, the RMS ray and reprojection residuals and the conditioning; NaN in columns 1 .. 6
+        where fewer than two views found the sphere or the rays are parallel within ``min_det``.  ``slot_host`` / ``win_host``: int32 numpy
+        copies; with them a bad table is refused, without them the kernel reads a slot outside [0, S) as -1.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("openloop_triangulate is an eager op: it scores tables that a run has filled")
+        if sph.dim() != 4 or slot.dim() != 3:
+            raise GenimaHipError("openloop_triangulate: sph must be int64 [N, V, S, 17] and slot int32 [N, G, V]")
+        N, V, S = (int(s) for s in sph.shape[:3])
+        G = int(slot.shape[1])
+        if out is None:
+            out = torch.empty((N, G, 2, 8), dtype=torch.float64, device=sph.device)
+        for t, dt, shape in ((sph, torch.int64, (N, V, S, 17)), (win, torch.int32, (N, V, S, 4)), (cams, torch.float32, (N, V, 18)),
+                             (slot, torch.int32, (N, G, V)), (centre, torch.float64, (N, G, 3)), (out, torch.float64, (N, G, 2, 8))):
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                raise GenimaHipError(f"openloop_triangulate: a contiguous device tensor {dt} {shape} expected")
+        hp = []
+        for h, shape in ((slot_host, (N, G, V)), (win_host, (N, V, S, 4))):
+            if h is not None and not (str(h.dtype) == "int32" and h.flags.c_contiguous and h.shape == shape):
+                raise GenimaHipError(f"openloop_triangulate: a contiguous int32 host copy {shape} expected, got {h.dtype} {h.shape}")
+            hp.append(None if h is None else h.ctypes.data)
+        check(self.lib.gn_openloop_triangulate(self._ctx, _ptr(sph), _ptr(win), _ptr(cams), _ptr(slot), _ptr(centre), hp[0], hp[1], _ptr(out),
+                                               float(min_ratio), float(min_det), N, V, S, G), "gn_openloop_triangulate")
+        return out
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

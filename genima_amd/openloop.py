@@ -22,6 +22,11 @@ here.  What a demo tree does give is, for every transition, t
   -- ``gn_openloop_exec_metrics``.  Observations are teacher-forced, so a rollout with horizon h uses exactly the chunks of the transitions at
   steps 0, h, 2h, ... of each episode: a sweep costs a few launches per setting on top of the pass made anyway.
 
+* optionally, where the generated spheres are in the WORLD: ``triangulate=True`` triangulates every drawn sphere across the views from the
+  sphere table's centroids after the last batch -- ``gn_openloop_triangulate`` -- and compares the point with the sphere's true centre: the
+  error in metres and the cross-view residuals (do the four tiles agree on one arm pose?), for the generated image and for the ground-truth
+  render, whose row is the floor of the method.
+
 ``OpenLoopEval(agent, None, ...)`` is the diffusion-only mode (no controller exists while the ControlNet is being fine-tuned):
 ``diffusion_validator`` makes a ``train_loop.TrainLoop`` ``validate`` callable of it.
 
@@ -53,6 +58,47 @@ def _mean(x) -> Optional[float]:
 
 
 EXEC_COLUMNS = ("joint_l1", "gripper", "jump", "demo_jump")  # gn_openloop_exec_metrics' four values per transition
+POINT_COLUMNS = ("n_views", "x", "y", "z", "err_m", "ray_rms_m", "reproj_rms_px", "det")  # gn_openloop_triangulate's eight values per (transition, group, kind)
+POINT_KINDS = ("generated", "ground_truth")
+MAX_GROUPS = 8  # gn_openloop_triangulate's bound on G
+
+
+def sphere_groups(spheres, count, windows):
+    """The group tables of ``gn_openloop_triangulate``, on the host: ``spheres`` [N, V, S, 16], ``count`` [N, V], ``windows`` int32
+    [N, V, S, 4] (the per-transition view tables and ``render.sphere_windows`` of them) -> ``(slot int32 [N, G, V], centre f64 [N, G, 3])``.
+
+    A group is one distinct world centre among the spheres a transition draws (``s < count``): the translation column of the sphere's pose,
+    compared by exact f64 equality across the views -- every view packs the same f32 pose, so the same joint compares equal and nothing else
+    does.  Groups are listed in order of first appearance (view by view, slot by slot).  ``slot[n, g, v]`` is the slot of view ``v`` that
+    shows group ``g``, or -1 where the view does not draw it or where its window is ``(0, 0, 0, 0)``.  ``G`` is the largest group count of
+    any transition, at least 1; the rows past a transition's own groups hold -1 and a zero centre."""
+    sph, count, win = np.asarray(spheres, np.float64), np.asarray(count), np.asarray(windows)
+    N, V, S = sph.shape[:3]
+    found = []
+    for n in range(N):
+        groups = []  # [centre, {view: slot}]
+        for v in range(V):
+            for s in range(min(int(count[n, v]), S)):
+                c = sph[n, v, s, [3, 7, 11]]
+                for grp in groups:
+                    if (grp[0] == c).all():
+                        break
+                else:
+                    grp = [c, {}]
+                    groups.append(grp)
+                if v not in grp[1] and win[n, v, s].any():  # a view that packed one centre twice keeps its first slot
+                    grp[1][v] = s
+        found.append(groups)
+    G = max([1] + [len(g) for g in found])
+    if G > MAX_GROUPS:
+        raise ValueError(f"sphere_groups: a transition draws {G} distinct spheres; gn_openloop_triangulate takes at most {MAX_GROUPS}")
+    slot, centre = np.full((N, G, V), -1, np.int32), np.zeros((N, G, 3), np.float64)
+    for n, groups in enumerate(found):
+        for g, (c, where) in enumerate(groups):
+            centre[n, g] = c
+            for v, s in where.items():
+                slot[n, g, v] = s
+    return slot, centre
 
 
 def parse_execution(text: str):
@@ -83,14 +129,22 @@ class OpenLoopResult:
     ``executions``: None, or per replayed execution mode ``{"h", "temporal_agg", "m", "K"}`` plus per row kind (``generated`` / ``oracle``)
     ``{"actions": f32 [N, A], "n_calls": int32 [N], "scores": {"norm" | "rad": f32 [N, 4]}}`` (``EXEC_COLUMNS``: the joint L1 sum and the
     gripper flag of the EXECUTED action against the demo's, the executed jump from the step before and the demo's own).  ``chunks``: the f16
-    [N, T, A] table per row kind that the modes were replayed from.  ``summary()`` reads neither; ``execution_summary()`` does."""
+    [N, T, A] table per row kind that the modes were replayed from.  ``summary()`` reads neither; ``execution_summary()`` does.
+
+    ``points``: None, or f64 [N, G, 2, 8] (``POINT_COLUMNS``; kind 0 the generated image, kind 1 the ground-truth render): each drawn sphere
+    triangulated from the views that found it -- ``gn_openloop_triangulate`` -- with ``point_slots`` int32 [N, G, V] (the slot of each view
+    that shows group g, or -1), ``point_centres`` f64 [N, G, 3] (the true centres) and ``cams`` f32 [N, V, 18] (the camera tables), as
+    ``sphere_groups`` and the evaluator made them.  ``summary()`` does not read them; ``triangulation_summary()`` does."""
 
     def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int,
-                 spheres=None, windows=None, executions=None, chunks=None):
+                 spheres=None, windows=None, executions=None, chunks=None, points=None, point_slots=None, point_centres=None, cams=None):
         if (spheres is None) != (windows is None):
             raise ValueError("OpenLoopResult: spheres and windows come together (the score needs the windows' diagonals)")
+        if points is not None and (windows is None or point_slots is None or point_centres is None or cams is None):
+            raise ValueError("OpenLoopResult: points come with windows, point_slots, point_centres and cams (the 3D score's penalty needs them)")
         self.image, self.actions, self.spheres, self.windows = image, actions, spheres, windows
         self.executions, self.chunks = executions, chunks
+        self.points, self.point_slots, self.point_centres, self.cams = points, point_slots, point_centres, cams
         self.episode, self.step, self.task = np.asarray(episode, np.int32), np.asarray(step, np.int32), np.asarray(task, np.int32)
         self.tasks, self.cameras, self.joints, self.H, self.W = list(tasks), list(cameras), int(joints), int(H), int(W)
 
@@ -239,10 +293,64 @@ class OpenLoopResult:
             out.append(d)
         return out
 
+    def point_penalty(self) -> np.ndarray:
+        """f64 [N, G], metres: what an unsolved generated group counts as in ``score_mm`` -- half its mean window diagonal at the sphere's
+        depth.  Per view ``v`` with ``s = point_slots[n, g, v] >= 0``: the window ``windows[n, v, s]`` has the diagonal ``hypot(x1 - x0,
+        y1 - y0)`` pixels; with ``R | t`` the pose in ``cams[n, v, 4:16]`` and ``c = point_centres[n, g]`` the sphere lies ``z = -(R^T (c -
+        t)).z`` metres ahead, where one pixel spans ``z / |fx|`` metres (``fx = cams[n, v, 0]``); the view's term is ``0.5 diagonal z /
+        |fx|`` and the penalty is the mean of the terms.  NaN where no view shows the group."""
+        slots = self.point_slots
+        N, G, V = slots.shape
+        w = np.take_along_axis(self.windows.astype(np.float64), np.maximum(slots, 0).transpose(0, 2, 1)[..., None], axis=2)  # [N, V, G, 4]
+        diag = np.hypot(w[..., 2] - w[..., 0], w[..., 3] - w[..., 1]).transpose(0, 2, 1)  # [N, G, V]
+        cams = self.cams.astype(np.float64)
+        pose = cams[..., 4:16].reshape(N, V, 3, 4)
+        d = self.point_centres[:, :, None, :] - pose[:, None, :, :, 3]  # c - t, [N, G, V, 3]
+        z = -np.einsum("nvj,ngvj->ngv", pose[..., 2], d)  # -(R^T (c - t)).z: R's third column
+        term = np.where(slots >= 0, 0.5 * diag * z / np.abs(cams[:, None, :, 0]), np.nan)
+        cnt = (slots >= 0).sum(axis=-1)
+        return np.divide(np.nansum(term, axis=-1), cnt, out=np.full((N, G), np.nan), where=cnt > 0)
+
+    def _triangulation_block(self, rows: np.ndarray) -> Dict:
+        P = self.points[rows]
+        multi = P[:, :, 1, 0] >= 2  # the ground truth drew the group into at least two views
+        n = int(multi.sum())
+        out: Dict = {"n_groups": n}
+        solved = {}
+        for k, kind in enumerate(POINT_KINDS):
+            ok = solved[kind] = multi & ~np.isnan(P[:, :, k, 4])
+            err = P[:, :, k, 4][ok] * 1e3
+            out[kind] = {"solved_rate": float(ok.sum() / n) if n else None, "err_mm": _mean(err), "err_median_mm": float(np.median(err)) if err.size else None,
+                         "ray_mm": _mean(P[:, :, k, 5][ok] * 1e3), "reproj_px": _mean(P[:, :, k, 6][ok]), "views": _mean(P[:, :, k, 0][multi])}
+        both = solved["generated"] & solved["ground_truth"]
+        out["excess_mm"] = _mean((P[:, :, 0, 4] - P[:, :, 1, 4])[both] * 1e3)
+        scored = np.where(solved["generated"], P[:, :, 0, 4], self.point_penalty()[rows])
+        out["score_mm"] = float(scored[multi].mean() * 1e3) if n else None
+        return out
+
+    def triangulation_summary(self) -> Optional[Dict]:
+        """None without ``points``; else, in numpy f64: ``n_groups``, the number of spheres the ground truth drew into at least two views
+        (kind 1's view count >= 2: the spheres a triangulation can be asked of), and per kind (``generated``, ``ground_truth``) over those
+        groups ``solved_rate``, the mean and median 3D error ``err_mm`` / ``err_median_mm``, the mean RMS ray residual ``ray_mm`` and
+        reprojection residual ``reproj_px`` of the solved ones, and ``views``, the mean number of views used.  ``excess_mm``: the mean over
+        the groups solved in both kinds of the generated error minus the ground-truth error.  The centroid of "change against the
+        observation" is not the projection of the sphere's centre -- texture, perspective and overlapping windows bias it -- so the
+        ``ground_truth`` row is that bias, the floor of the method, and the excess is the model's own part.  ``score_mm``, lower is better:
+        the mean over the groups of the generated error, an unsolved group counting as ``point_penalty()``.  ``per_task``: the same per
+        task when there is more than one.  Teacher-forced like every score here, and not a success rate."""
+        if self.points is None:
+            return None
+        out = self._triangulation_block(np.ones(len(self), bool))
+        if len(self.tasks) > 1:
+            out["per_task"] = {t: self._triangulation_block(self.task == i) for i, t in enumerate(self.tasks)}
+        return out
+
     def to_json(self, path: str) -> Dict:
         s = self.summary()
         if self.executions is not None:
             s = dict(s, executions=self.execution_summary())  # a key of its own: summary() itself is as it was
+        if self.points is not None:
+            s = dict(s, spheres_3d=self.triangulation_summary())
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as f:
             json.dump(s, f, indent=1)
@@ -282,6 +390,13 @@ class OpenLoopEval:
     ride in the same device-to-host copy (``OpenLoopResult.executions`` / ``.chunks``).  With None nothing changes: the same launches, the
     same tables, the same bits.
 
+    ``triangulate``: also place every drawn sphere in the world.  At setup the group tables are built on the host (``sphere_groups``: which slot
+    of which view shows which sphere, and its true centre) and uploaded once; after the last batch ``run()`` launches
+    ``gn_openloop_triangulate`` once over the finished sphere table and the f64 table [N, G, 2, 8] rides in the same device-to-host copy
+    (``OpenLoopResult.points``, ``triangulation_summary()``).  ``tri_min_ratio``: a view counts for the generated image when its mass is at
+    least this share of the ground truth's; ``tri_min_det``: rays that cross worse than this are left unsolved.  It needs a diffusion agent;
+    with False nothing changes: the same launches, the same tables, the same bits.
+
     Per batch, on the device: ``DeviceReplay.sample`` (the frames, proprioception, normalised action chunk, task tokens) -> ``gn_render_spheres``
     over the frames (``full``, ``occupied``) -> the four views on the 2x2 canvas -> the pipeline (``harness.make_prompt`` ids, one generator
     seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image, sphere and action scores -> the controller again on ``full`` -> its action
@@ -290,7 +405,8 @@ class OpenLoopEval:
 
     def __init__(self, diffusion_agent, controller, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None,
                  batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
-                 change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None):
+                 change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None, triangulate: bool = False,
+                 tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6):
         from .render import load_atlas, load_traj, sphere_windows
 
         if controller is None:
@@ -326,6 +442,13 @@ class OpenLoopEval:
                     raise ValueError(f"OpenLoopEval: an execution setting is (execution_horizon, temporal_agg[, m]), got {ex!r}")
                 h, K = execution_slots(T, ex[0], bool(ex[1]))
                 self.executions.append({"h": int(h), "temporal_agg": bool(ex[1]), "m": check_ensemble_m(ex[2] if len(ex) > 2 else 0.01), "K": int(K)})
+        self.triangulate, self.tri_min_ratio, self.tri_min_det = bool(triangulate), float(tri_min_ratio), float(tri_min_det)
+        self.point_slots = self.point_slots_host = self.point_centres = self.point_centres_host = self.cams_host = None
+        if self.triangulate:
+            if diffusion_agent is None:
+                raise ValueError("OpenLoopEval: triangulate places the generated spheres; without a diffusion agent nothing is generated")
+            if not self.tri_min_ratio >= 0.0 or not self.tri_min_det > 0.0:
+                raise ValueError(f"OpenLoopEval: tri_min_ratio = {tri_min_ratio} must be >= 0 and tri_min_det = {tri_min_det} > 0")
         self.change_threshold = int(change_threshold)
         self.agent, self.controller, self.cameras, self.V = diffusion_agent, controller, tuple(cameras), len(cameras)
         if diffusion_agent is not None and self.V != 4:
@@ -369,6 +492,10 @@ class OpenLoopEval:
             tab = {k: vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:]) for k in ("cams", "spheres", "count")}
             self.windows_host = np.ascontiguousarray(sphere_windows(tab["cams"], tab["spheres"], tab["count"], H, W))
             self.windows = torch.from_numpy(self.windows_host).to(dev)
+            if self.triangulate:  # which slot of which view shows which sphere, and where it truly is: int32 [N, G, V], f64 [N, G, 3]
+                self.point_slots_host, self.point_centres_host = sphere_groups(tab["spheres"], tab["count"], self.windows_host)
+                self.point_slots, self.point_centres = (torch.from_numpy(a).to(dev) for a in (self.point_slots_host, self.point_centres_host))
+                self.cams_host = np.ascontiguousarray(tab["cams"])
         self.samples = int(render_cfg.samples)
         self.step_index, self.episode_index = step, ep_of.copy()
         names = [_task_of(ep, d) for ep, d in zip(episodes, rp.descriptions)]
@@ -472,6 +599,14 @@ class OpenLoopEval:
             out.append(d)
         return out
 
+    def triangulate_spheres(self, tabs) -> Optional[torch.Tensor]:
+        """After the last batch: every drawn sphere of the finished sphere table triangulated across the views, for the generated image and
+        for the ground-truth render -- one ``gn_openloop_triangulate`` launch -> f64 [N, G, 2, 8] on the device; nothing is read back."""
+        if not self.triangulate:
+            return None
+        return self.E.openloop_triangulate(tabs["spheres"], self.windows, self.views["cams"], self.point_slots, self.point_centres,
+                                           min_ratio=self.tri_min_ratio, min_det=self.tri_min_det, slot_host=self.point_slots_host, win_host=self.windows_host)
+
     def run_batch(self, start: int, tabs, generator) -> None:
         """One evaluator batch: steps 1 - 7 for transitions ``start ..``, everything on the device, nothing read back."""
         if self.controller is not None:
@@ -503,6 +638,9 @@ class OpenLoopEval:
             self.run_batch(start, tabs, generator)
         # the one device-to-host copy: every table as bytes of one buffer
         flat = [tabs[k][m] for k in ("generated", "oracle") if k in tabs for m in ("norm", "rad")] + [tabs[k] for k in ("image", "spheres") if k in tabs]
+        points = self.triangulate_spheres(tabs)
+        if points is not None:  # f64, straight after the int64 tables: the 8-byte tables stay together, ahead of everything narrower that follows
+            flat.append(points)
         n_before = len(flat)
         execs = self.replay_executions(tabs)
         if execs is not None:  # appended: 4-byte tables first, the f16 chunk tables last (every table then starts on its own type's grid)
@@ -512,7 +650,7 @@ class OpenLoopEval:
                     flat += [d[k]["actions"], d[k]["n_calls"], d[k]["scores"]["norm"], d[k]["scores"]["rad"]]
             flat += [tabs["chunks"][k] for k in kinds]
         host = torch.cat([t.reshape(-1).view(torch.uint8) for t in flat]).cpu().numpy()
-        np_of = {torch.int64: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.float16: np.float16}
+        np_of = {torch.int64: np.int64, torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int32, torch.float16: np.float16}
         out, o = [], 0
         for t in flat:
             n = t.numel() * t.element_size()
@@ -535,7 +673,9 @@ class OpenLoopEval:
                 k += 2
         image, spheres = (out[k], out[k + 1]) if "image" in tabs else (None, None)
         return OpenLoopResult(image, actions, self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1, self.H, self.W,
-                              spheres=spheres, windows=self.windows_host if spheres is not None else None, executions=executions, chunks=chunks)
+                              spheres=spheres, windows=self.windows_host if spheres is not None else None, executions=executions, chunks=chunks,
+                              points=out[k + 2] if points is not None else None, point_slots=self.point_slots_host,
+                              point_centres=self.point_centres_host, cams=self.cams_host)
 
 
 def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None,
@@ -575,24 +715,32 @@ VALIDATION_JSONL = "validation.jsonl"
 
 
 def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, out_dir=None, tokenizer=None, batch_size: int = 8,
-                        num_inference_steps: int = 5, seed: int = 0, engine=None):
+                        num_inference_steps: int = 5, seed: int = 0, engine=None, triangulate: bool = False, tri_min_ratio: float = 0.5,
+                        tri_min_det: float = 1e-6):
     """-> a ``validate(global_step)`` callable for ``train_loop.TrainLoop``: each call wraps ``make_pipe()`` (for instance
     ``validation.validation_pipeline(..., trainer, "euler_discrete")`` over the trainer's current weights) as the agent of a diffusion-only
     ``OpenLoopEval`` on held-out demos and returns ``{"step", "select", "found_rate", "shift_px", "mass_ratio", "spread_ratio", "colour_l1",
     "sphere_rmse", "background_rmse", "wrapped_mse", "n"}`` -- ``select`` is ``summary()["image"]["spheres"]["score"]`` (lower is better), the
     sphere fields are its ``overall`` block, the two RMSEs the means over all cameras.  With ``out_dir`` the dict is also appended as one JSON
     line to ``<out_dir>/validation.jsonl``.  The demo set is loaded onto the device at the first call and kept; later calls swap the agent.
-    ``TrainLoop`` ignores the return value; it is there for callers that rank checkpoints themselves."""
+    ``TrainLoop`` ignores the return value; it is there for callers that rank checkpoints themselves.
+
+    ``triangulate``: the evaluator's option; the dict then gains ``err_3d_mm`` (the mean 3D error of the generated spheres,
+    ``triangulation_summary()["generated"]["err_mm"]``) and ``excess_mm`` (what of it is the model's own); ``tri_min_ratio`` and
+    ``tri_min_det`` are the evaluator's and are read only with it.  ``select`` stays what it is."""
     import types
 
     state: Dict = {}
+    # the three options reach the evaluator only when triangulate is on: with it off OpenLoopEval is called with exactly the arguments it was
+    # called with before the option existed (tests/test_sphere_metrics_cpu.py compares them), so the default path cannot have changed
+    tri = dict(triangulate=True, tri_min_ratio=tri_min_ratio, tri_min_det=tri_min_det) if triangulate else {}
 
     def validate(global_step: int) -> Dict:
         agent = types.SimpleNamespace(pipe=make_pipe())
         ev = state.get("ev")
         if ev is None:
             ev = state["ev"] = OpenLoopEval(agent, None, episodes, cameras, render_cfg=render_cfg, stats=None, tokenizer=tokenizer, batch_size=batch_size,
-                                            num_inference_steps=num_inference_steps, seed=seed, engine=engine)
+                                            num_inference_steps=num_inference_steps, seed=seed, engine=engine, **tri)
         ev.agent = agent
         res = ev.run()
         im = res.summary()["image"]
@@ -600,6 +748,9 @@ def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CA
         line = {"step": int(global_step), "select": sp["score"], "found_rate": sp["overall"]["found_rate"], "shift_px": sp["overall"]["shift_px"],
                 "mass_ratio": sp["overall"]["mass_ratio"], "spread_ratio": sp["overall"]["spread_ratio"], "colour_l1": sp["overall"]["colour_l1"],
                 "sphere_rmse": _mean(res.sphere_rmse()), "background_rmse": _mean(res.background_rmse()), "wrapped_mse": im["wrapped_mse"], "n": len(res)}
+        if triangulate:
+            s3 = res.triangulation_summary()
+            line.update(err_3d_mm=s3["generated"]["err_mm"], excess_mm=s3["excess_mm"])
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, VALIDATION_JSONL), "a") as f:

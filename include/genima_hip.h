@@ -898,6 +898,44 @@ int32_t gn_openloop_exec_actions(gn_ctx* ctx, const void* chunks, const int32_t*
 int32_t gn_openloop_exec_metrics(gn_ctx* ctx, const float* exec, const float* demo, const int32_t* first_tr, const float* joint_scale, float* out, int32_t N,
                                  int32_t A);
 
+/* gn_openloop_triangulate: where the drawn spheres are in the WORLD.  Each sphere is triangulated from the centroids of the views that found
+ * it and compared with its true centre; one launch over the finished tables of a run.  All pointers but the two host copies are device memory.
+ *   sph       uint64 [N][V][S][17], 8-byte aligned: gn_openloop_sphere_metrics' table (columns 1..3 the generated mass and its x / y sums,
+ *             5..7 the ground truth's)
+ *   win       int32 [N][V][S][4], 4-byte aligned: the windows the table was summed over (only x0, y0 are read, as numbers)
+ *   cams      f32 [N][V][18]: gn_render_spheres' camera tables
+ *   slot      int32 [N][G][V]: the sphere slot s of view v that shows group g of transition n, or -1 (a group is one world point; slot s of two
+ *             views need not be the same sphere).  The kernel reads a slot outside [0, S) as -1, so no table value can make it read outside
+ *             its buffers
+ *   centre    f64 [N][G][3], 8-byte aligned: the true world centre of each group
+ *   slot_host, win_host   NULL, or HOST copies of slot and win.  With them the entry point refuses the call unless every slot lies in [-1, S)
+ *             and every window has 0 <= x0 <= x1, 0 <= y0 <= y1 and at most 256 per side
+ *   min_ratio f64 >= 0, min_det f64 > 0;  N >= 0, V in [2, 8], S in [1, 8], G in [1, 8], N * V * S * 17 < 2^31
+ *   out       f64 [N][G][2][8], 8-byte aligned; kind 0 is the generated image, kind 1 the ground-truth render
+ * Per (n, g, kind), one thread each, everything in f64 without fused multiply-add:
+ *   used      view v is used when s = slot[n][g][v] >= 0 and, with gen_m / gt_m columns 1 / 5 of sph[n][v][s]:  kind 1: gt_m > 0;
+ *             kind 0: gen_m > 0, gt_m > 0 and gen_m >= min_ratio * gt_m
+ *   observation  u = x0 + sum_x / m + 0.5, v = y0 + sum_y / m + 0.5 with the kind's own three columns: the centroid in image coordinates, a
+ *             pixel's centre at + 0.5 (gn_render_spheres' one-sample offset)
+ *   ray       origin o = the camera position (the pose's translation column), direction d = pose * (dx, dy, -1) normalised, dx = (u - cx) / fx,
+ *             dy = (cy - v) / fy (signed fx, fy): gn_render_spheres' ray through (u, v)
+ *   point     x solves A x = b, A = sum (I - d d^T), b = sum (I - d d^T) o over the used views in index order: the least-squares closest
+ *             point to the rays; x = adj(A) b / det(A) in one fixed order of operations
+ *   [0]       the number of used views
+ *   [1..3]    x
+ *   [4]       |x - centre[n][g]|
+ *   [5]       sqrt(mean over the used views of |(I - d d^T)(x - o)|^2): the RMS distance from x to the rays
+ *   [6]       sqrt(mean over the used views of (u' - u)^2 + (v' - v)^2), (u', v') the projection of x: p = R^T (x - o), z = -p.z,
+ *             u' = cx + fx p.x / z, v' = cy - fy p.y / z;  NaN when z <= 0 in a used view
+ *   [7]       det(A) / (trace(A) / 3)^3: 0 for parallel rays, at most 1; 0 with fewer than two used views
+ *   With fewer than two used views, or unless [7] >= min_det, the case is unsolved: [1..6] are NaN, [0] and [7] are still written.
+ * Plain loads and stores, no atomics, no zeroing pass: every run gives the same bits.  Refused, launching nothing and leaving out as it was: a
+ * NULL pointer other than the host copies, N < 0, V, S or G outside its range, min_ratio < 0 or NaN, min_det <= 0 or NaN, a misaligned
+ * pointer, a host table that fails its check.  N == 0 is accepted and does nothing.  Eager only. */
+int32_t gn_openloop_triangulate(gn_ctx* ctx, const uint64_t* sph, const int32_t* win, const float* cams, const int32_t* slot, const double* centre,
+                                const int32_t* slot_host, const int32_t* win_host, double* out, double min_ratio, double min_det, int32_t N, int32_t V,
+                                int32_t S, int32_t G);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */

@@ -17,9 +17,13 @@ replayed) and one with the grid (h, temporal_agg, m) in {1, 5, 10, 20} x {off, o
 (``gn_openloop_exec_actions`` with h = 5 and temporal_agg, ``gn_openloop_exec_metrics``) by device events.  The claim checked there: the grid
 adds a few launch-shaped kernels per setting and nothing to a run without it.
 
+With ``--triangulate`` it times whole runs of two evaluators that alternate in the same way -- one without and one with ``triangulate=True``
+-- and the ``gn_openloop_triangulate`` launch over the run's whole table by device events.  The expectation checked there: one small launch
+and N * G * 128 more bytes in the final copy do not show next to the diffusion calls.
+
 Prints one JSON line; needs an MI355X.
 
-    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid]
+    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid] [--triangulate]
         [--sphere_textures tests/golden/sphere_textures] [--out profiles/openloop_b8.json]
 """
 import argparse
@@ -48,6 +52,7 @@ def main():
     ap.add_argument("--family", default="sd-turbo")
     ap.add_argument("--sphere_textures", default=os.path.join(HERE, "tests", "golden", "sphere_textures"))
     ap.add_argument("--exec_grid", action="store_true", help="also time whole runs without and with the 8-setting execution grid, and the two replay launches")
+    ap.add_argument("--triangulate", action="store_true", help="also time whole runs without and with triangulate=True, and the triangulation launch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -159,6 +164,31 @@ def main():
         x_out = torch.empty((ev.N, 4), dtype=torch.float32, device=E.device)
         launches["exec_actions_us"] = lambda: E.openloop_exec_actions(xt["chunks"]["oracle"], ev_grid.first_tr, 5, True, 0.01, out=x_acts)
         launches["exec_metrics_us"] = lambda: E.openloop_exec_metrics(x_acts, ev_grid.replay.action, ev_grid.first_tr, x_out, joint_scale=ev_grid.joint_std)
+    if args.triangulate:
+        ev_tri = OpenLoopEval(dagent, controller, eps, cams, render_cfg=rcfg, stats=(P.action_stats(demos), P.proprio_stats(demos)), tokenizer=tokens,
+                              batch_size=B, engine=E, triangulate=True)
+        runs = {"run_without_triangulate": ev.run, "run_with_triangulate": ev_tri.run}
+        rms = {k: [] for k in runs}
+        for i in range(args.warmup + args.reps):
+            for k, fn in runs.items():
+                E.synchronize()
+                t = time.perf_counter()
+                fn()  # ends in its device-to-host copy
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    rms[k].append((time.perf_counter() - t) * 1e3)
+        for k in runs:
+            res[k] = stats(rms[k])
+        res["triangulate_minus_plain_ms"] = round(res["run_with_triangulate"]["median_ms"] - res["run_without_triangulate"]["median_ms"], 4)
+        res["run_without_triangulate_spread_ms"] = round(res["run_without_triangulate"]["max_ms"] - res["run_without_triangulate"]["min_ms"], 4)
+        res["triangulate_groups"] = int(ev_tri.point_slots_host.shape[1])
+        res["triangulate_extra_copy_bytes"] = int(ev_tri.N * ev_tri.point_slots_host.shape[1] * 128)
+        tt = ev_tri._tables()
+        for start in range(0, ev_tri.N, B):  # every batch: the launch below is timed over the finished table of a whole run
+            ev_tri.run_batch(start, tt, gen)
+        t_out = ev_tri.triangulate_spheres(tt)
+        launches["triangulate_us"] = lambda: E.openloop_triangulate(tt["spheres"], ev_tri.windows, ev_tri.views["cams"], ev_tri.point_slots, ev_tri.point_centres,
+                                                                    t_out, min_ratio=ev_tri.tri_min_ratio, min_det=ev_tri.tri_min_det)
     for name, launch in launches.items():
         us = []
         for _ in range(5):

@@ -14,8 +14,11 @@ those, never with their own.  Prints the summary and writes it as JSON; with a d
 location / mass / spread / colour scores (``--change_threshold`` sets their threshold against the observation).  ``--no_controller`` scores the
 diffusion checkpoint alone (no ``--controller_snapshot`` / ``--stats_dir`` needed: the mode a ControlNet fine-tune validates in).
 ``--execution H[,agg[,M]]`` (repeatable; ``5``, ``5,agg``, ``5,agg,0.01``) also replays that execution mode over the run's chunks and adds, under
-``executions``, the error and the step-to-step jump of the EXECUTED actions (``OpenLoopResult.execution_summary``).  Open-loop error is not a success rate: every chunk is predicted from
-a demo state, nothing is executed and no error compounds."""
+``executions``, the error and the step-to-step jump of the EXECUTED actions (``OpenLoopResult.execution_summary``).
+``--triangulate`` also triangulates every drawn sphere across the four views (``gn_openloop_triangulate``) and adds, under ``spheres_3d``,
+the 3D error in millimetres and the cross-view residuals of the generated image beside those of the ground-truth render, the floor of the
+method (``OpenLoopResult.triangulation_summary``; ``--tri_min_ratio`` / ``--tri_min_det`` set which views and which crossings count).
+Open-loop error is not a success rate: every chunk is predicted from a demo state, nothing is executed and no error compounds."""
 import argparse
 import json
 import os
@@ -51,6 +54,9 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--execution", action="append", default=None, metavar="H[,agg[,M]]",
                     help="also score the actions an execution mode would execute: horizon H, 'agg' for temporal_agg, weight decay M (default 0.01); repeatable")
+    ap.add_argument("--triangulate", action="store_true", help="also triangulate the drawn spheres across the views: the 3D error in mm and the cross-view residuals")
+    ap.add_argument("--tri_min_ratio", type=float, default=0.5, help="a view counts for the generated image when its mass is at least this share of the ground truth's")
+    ap.add_argument("--tri_min_det", type=float, default=1e-6, help="rays that cross worse than this (det(A) / (trace(A) / 3)^3) are left unsolved")
     ap.add_argument("--out", default="openloop.json")
     a = ap.parse_args(argv)
     if not a.no_controller and not (a.controller_snapshot and a.stats_dir):
@@ -103,7 +109,8 @@ def main(argv=None):
         stats = P.load_stats(a.stats_dir)
     ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=stats, tokenizer=tokenizer, batch_size=a.batch_size,
                       num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed, change_threshold=a.change_threshold,
-                      action_sequence=a.action_sequence, executions=a.execution)
+                      action_sequence=a.action_sequence, executions=a.execution, triangulate=a.triangulate, tri_min_ratio=a.tri_min_ratio,
+                      tri_min_det=a.tri_min_det)
     print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
     summary = ev.run().to_json(a.out)
     print(json.dumps(summary, indent=1))
