@@ -164,12 +164,20 @@ def affine(E: Engine, x: torch.Tensor, matrix: Sequence[float], out: Optional[to
 
 
 def augment_data(E: Engine, augmentations: Optional[str], batch: Dict[str, torch.Tensor], generator: Optional[torch.Generator] = None,
-                 resolution: Optional[int] = None, roles: Tuple[str, str] = ROLES):
+                 resolution: Optional[int] = None, roles: Tuple[str, str] = ROLES, extra: Optional[Dict[str, torch.Tensor]] = None):
     """``augment_data(args, batch)`` with ``args.augmentations`` given as the comma list; batch tensors NHWC f16 8-channel on the device.
     ``roles``: the batch keys of the image and conditioning roles (``P2P_ROLES`` for InstructPix2Pix).  ``resolution`` (the reference's
-    ``args.resolution``, RandomAffine's img_size) defaults to the batch's H; ``affine`` needs square images."""
+    ``args.resolution``, RandomAffine's img_size) defaults to the batch's H; ``affine`` needs square images.
+    ``extra`` (not in the reference): further NHWC f16 tensors with C % 8 == 0 and the images' H x W (a per-pixel mask, say) that must stay
+    registered with the images: each receives only the ops applied to BOTH roles -- ``affine`` then ``crop``, with the same draws -- and comes
+    back under its own key.  The generator is consumed identically with or without it."""
     ik, ck = roles
     images, cond = batch[ik], batch[ck]
+    extra = dict(extra or {})
+    for k, v in extra.items():
+        _check_nhwc(v, f"augment_data extra[{k!r}]")
+        if k in batch or tuple(v.shape[:3]) != tuple(images.shape[:3]):
+            raise ValueError(f"augment_data extra[{k!r}]: needs a key of its own and the images' {tuple(images.shape[:3])}, got {tuple(v.shape)}")
     augs = parse_augmentations(augmentations)
     if augs:
         H, W = int(images.shape[1]), int(images.shape[2])
@@ -184,10 +192,13 @@ def augment_data(E: Engine, augmentations: Optional[str], batch: Dict[str, torch
             m = affine_inverse_matrix(*draws["affine"])
             images = affine(E, images, m)
             cond = affine(E, cond, m)
+            extra = {k: affine(E, v, m) for k, v in extra.items()}
         if "crop" in draws:
             i, j = draws["crop"]
             images = reflect_pad_crop(E, images, i, j)
             cond = reflect_pad_crop(E, cond, i, j)
+            extra = {k: reflect_pad_crop(E, v, i, j) for k, v in extra.items()}
     out = dict(batch)
     out[ik], out[ck] = images, cond
+    out.update(extra)
     return out

@@ -239,6 +239,7 @@ class InstructPix2PixTrainer(ControlNetTrainer):
     ``unet`` (+ ``unet_ema`` with ``use_ema``, :846-856)."""
 
     trainable_subfolder = "unet"
+    supports_sphere_loss = False  # sphere_loss_weight is the ControlNet trainers' option: attach_frozen refuses it here
 
     def __init__(self, E: Engine, unet_cfg, unet_sd, *, use_ema: bool = False, ema_decay: float = 0.9999,
                  conditioning_dropout_prob: Optional[float] = None, **kw):

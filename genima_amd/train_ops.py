@@ -376,6 +376,43 @@ def mse_loss(E: Engine, pred: torch.Tensor, target: torch.Tensor, C_valid: int, 
     return loss, dpred
 
 
+def change_mask(E: Engine, target: torch.Tensor, cond: torch.Tensor, threshold: int, t_scale=(127.5, 127.5), c_scale=(255.0, 0.0)) -> torch.Tensor:
+    """Where ``target`` (f16 [B, H, W, ld], default scale: in [-1, 1]) differs from ``cond`` (default: in [0, 1]) by more than ``threshold``
+    byte levels summed over RGB (gn_change_mask: OpenLoopEval's ``a_gt > 0`` rule) -> f16 [B, H, W, 8], channel 0 the flag."""
+    B, H, W, ld_t = target.shape
+    mask = torch.empty((B, H, W, 8), dtype=F16, device=E.device)
+    check(E.lib.gn_change_mask(E._ctx, _ptr(target), _ptr(cond), _ptr(mask), B, H, W, ld_t, cond.shape[-1], float(t_scale[0]), float(t_scale[1]),
+                               float(c_scale[0]), float(c_scale[1]), int(threshold)), "gn_change_mask")
+    return mask
+
+
+def loss_weight_pool(E: Engine, mask: torch.Tensor, h: int, w: int, lam: float):
+    """mask f16 [B, H, W, ld] (channel 0) -> (weight f32 [B, h, w] = 1 + lam * marked share of the latent pixel's block, count int64 [1] =
+    marked mask pixels, wsum f64 [1] = sum of weight); all on the device (gn_loss_weight_pool)."""
+    B, H, W, ld = mask.shape
+    weight = torch.empty((B, h, w), dtype=F32, device=E.device)
+    count = torch.empty(1, dtype=torch.int64, device=E.device)
+    wsum = torch.empty(1, dtype=torch.float64, device=E.device)
+    check(E.lib.gn_loss_weight_pool(E._ctx, _ptr(mask), ld, _ptr(weight), _ptr(count), _ptr(wsum), B, H, W, h, w, float(lam)), "gn_loss_weight_pool")
+    return weight, count, wsum
+
+
+def mse_loss_weighted(E: Engine, pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, wsum: torch.Tensor, C_valid: int,
+                      grad_scale: float = 1.0):
+    """``mse_loss`` with a per-pixel f32 ``weight`` and the weighted mean: loss = sum(weight * (pred - target)^2) / (C_valid * wsum), wsum the
+    f64 [1] device sum of weight (loss_weight_pool's); dpred = grad_scale * d(loss)/dpred."""
+    ldp, ldt = pred.shape[-1], target.shape[-1]
+    pixels = pred.numel() // ldp
+    if weight.numel() != pixels or weight.dtype != F32 or wsum.dtype != torch.float64:
+        raise ValueError(f"mse_loss_weighted: weight must be f32 with {pixels} elements and wsum f64, got {tuple(weight.shape)} {weight.dtype} / {wsum.dtype}")
+    dpred = torch.empty_like(pred)
+    loss = torch.empty(1, dtype=F32, device=E.device)
+    ws = E._workspace(4096)
+    check(E.lib.gn_mse_loss_weighted(E._ctx, _ptr(pred), _ptr(target), _ptr(weight), _ptr(wsum), _ptr(dpred), _ptr(loss), _ptr(ws), pixels, C_valid, ldp,
+                                     ldt, float(grad_scale)), "gn_mse_loss_weighted")
+    return loss, dpred
+
+
 def sumsq(E: Engine, x: torch.Tensor, out: torch.Tensor):
     ws = E._workspace(8192)
     check(E.lib.gn_sumsq_f32(E._ctx, _ptr(x), x.numel(), _ptr(out), _ptr(ws)), "gn_sumsq_f32")

@@ -663,6 +663,33 @@ int32_t gn_zero_upsample2x(gn_ctx* ctx, const void* x, void* out, int32_t B, int
 int32_t gn_sumpool2x2(gn_ctx* ctx, const void* x, void* out, int32_t B, int32_t H, int32_t W, int32_t C);       /* upsample dgrad */
 int32_t gn_mse_loss(gn_ctx* ctx, const void* pred, const void* target, void* dpred, float* loss_out, void* workspace,
                     int64_t pixels, int32_t C, int32_t ld_pred, int32_t ld_target, float grad_scale);
+/* ---- sphere-weighted loss (csrc/loss_weight.hip): an EXTENSION of the reference, used only with ControlNetTrainer's sphere_loss_weight > 0.
+ * Eager only; none of the three synchronises; every argument check precedes the first launch: a refused call writes nothing, returns
+ * non-zero and sets the last error.  Each product and sum below is one rounded operation (no fused multiply-add).
+ *
+ * gn_change_mask: where the target image differs from the conditioning image, on the bytes the f16 batch was made from -- the `a_gt > 0`
+ * rule of the sphere metrics.  target / cond f16 [B][H][W][ld_t / ld_c], ld >= 3; mask f16 [B][H][W][8], 16-byte aligned.  Per pixel and
+ * channel c < 3: tb_c = clamp(rintf(target_c * t_mul + t_add), 0, 255) in f32 (a NaN gives 0), cb_c alike from cond with c_mul, c_add;
+ * d = sum_c |tb_c - cb_c| (exact integers); mask[..][0] = d > threshold ? 1 : 0, channels 1..7 = 0.  An image in [-1, 1] takes
+ * (127.5, 127.5), one in [0, 1] takes (255, 0).  Refused: a NULL pointer, B, H or W <= 0, ld < 3, threshold < 0, a non-finite scale or
+ * offset, a misaligned pointer. */
+int32_t gn_change_mask(gn_ctx* ctx, const void* target, const void* cond, void* mask, int32_t B, int32_t H, int32_t W, int32_t ld_t, int32_t ld_c,
+                       float t_mul, float t_add, float c_mul, float c_add, int32_t threshold);
+/* gn_loss_weight_pool: the per-latent-pixel loss weight.  mask f16 [B][H][W][ld_m] (channel 0 is read); F = H / h = W / w in 1 .. 16.
+ * n = the number of mask pixels of a latent pixel's F x F block whose channel 0 is != 0;
+ *   weight       f32 [B][h][w] = 1 + lambda * (n / (F * F)), in f32
+ *   count_total  int64 [1], 8-byte aligned = the sum of all n: integer additions only (64-bit vector atomics on this word, which the entry
+ *                point zeroes on the ctx stream), so every run gives the same bits
+ *   wsum         f64 [1], 8-byte aligned = (double)(B * h * w) + (double)lambda * (double)count_total / (double)(F * F) = the sum of weight
+ * Refused: a NULL pointer, a size <= 0, H % h or W % w != 0, H / h != W / w, F > 16, lambda < 0 or not finite, a misaligned pointer. */
+int32_t gn_loss_weight_pool(gn_ctx* ctx, const void* mask, int32_t ld_m, float* weight, int64_t* count_total, double* wsum, int32_t B, int32_t H,
+                            int32_t W, int32_t h, int32_t w, float lambda);
+/* gn_mse_loss_weighted: gn_mse_loss with a per-pixel weight and a weighted MEAN.  weight f32 [pixels]; wsum f64 [1] (device memory, read inside
+ * the kernels: the host never reads it).  gs = (grad_scale * 2) / (float)((double)C * wsum[0]); d = (float)pred - (float)target;
+ * dpred = the f16 nearest to (gs * weight[px]) * d -- the f32 factor gs * weight[px] times d, exact, rounded once -- for c < C, 0 in the padded channels; loss_out[0] = sum(weight * d * d) / (C * wsum[0]), by gn_mse_loss's
+ * fixed-order two-stage reduction (the same workspace).  dpred may be NULL.  With weight == 1 and wsum == pixels, dpred has gn_mse_loss's bits. */
+int32_t gn_mse_loss_weighted(gn_ctx* ctx, const void* pred, const void* target, const float* weight, const double* wsum, void* dpred, float* loss_out,
+                             void* workspace, int64_t pixels, int32_t C, int32_t ld_pred, int32_t ld_target, float grad_scale);
 int32_t gn_sumsq_f32(gn_ctx* ctx, const float* x, int64_t n, float* out, void* workspace);
 /* global-norm clipping after loss-scale removal (accelerator.clip_grad_norm_, diffusion/train_controlnet_genima.py:1403-1405):
  * norm = sqrt(sumsq[0]) * inv_scale; clip[0] = min(1, max_norm / (norm + 1e-6)); clip[1] = norm; clip[2] = 1 when non-finite
