@@ -300,6 +300,8 @@ SIGNATURES = {
     "gn_change_mask": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _I32]),
     "gn_loss_weight_pool": (_I32, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_mse_loss_weighted": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F]),
+    "gn_mse_loss_parts_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "gn_mse_loss_parts": (_I32, [_P, _P, _P, _P, _P, _P, _P] + [_I32] * 10),
     "gn_sumsq_f32": (_I32, [_P, _P, _I64, _P, _P]),
     "gn_clip_coef": (_I32, [_P, _P, _P, _F, _F]),
     "gn_adamw_flat": (_I32, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I32, _P, _F, _P, _I32]),

@@ -16,6 +16,10 @@
 // in f64 in a fixed order.  With ld_pred == 8 on the 16-byte grid a thread owns a pixel: one 16-byte load of pred, one 16- or 8-byte load of
 // target (ld_target 8 or 4), one 16-byte store of dpred; other layouts take gn_mse_loss's element walk.  The gradient scale is formed in the
 // kernel from wsum[0] in device memory: the host never reads it.
+//
+// Parts kernels (gn_mse_loss_parts; attach_frozen(loss_parts=), ControlNetTrainer.eval_loss).  The UNWEIGHTED squared error of a step split
+// into marked / unmarked share per sample and added into the row of a device f64 table the sample's bucket names.  f64 throughout (131 k
+// elements per step: not a bandwidth exercise), two stages in a fixed order, no floating-point atomics: two runs give the same bits.
 #include "common.h"
 
 #include <math.h>
@@ -181,6 +185,93 @@ __global__ void mse_weighted_final_kernel(const float* __restrict__ part, const 
   if (threadIdx.x == 0) out[0] = (float)(s / ((double)C * wsum[0]));
 }
 
+// ---- loss parts (gn_mse_loss_parts): a read-out, not a loss.  Stage one: workgroup (b, r) owns the LP_THREADS contiguous latent pixels
+// [r * LP_THREADS, (r + 1) * LP_THREADS) of sample b, one pixel per thread.  A thread past the sample's last pixel carries zeros INTO the
+// lane tree, so all 64 lanes of every wave take the same fixed butterfly; the four waves meet in LDS and thread 0 adds them in wave order.
+constexpr int LP_THREADS = 256;
+
+__device__ __forceinline__ double lp_wave_sum(double v) {  // fixed xor butterfly; all 64 lanes must be active
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(LP_THREADS) void mse_parts_partial_kernel(const f16* __restrict__ pred, const f16* __restrict__ target,
+                                                                       const uint16_t* __restrict__ mask, double* __restrict__ part, long hw, int ranges,
+                                                                       int w, int C, int ldp, int ldt, int H, int W, long ld_m, int F) {
+  __shared__ double red[3][LP_THREADS / 64];
+  const long b = blockIdx.x / ranges;
+  const long p = (long)(blockIdx.x % ranges) * LP_THREADS + threadIdx.x;
+  double S = 0.0, G = 0.0, n_d = 0.0;
+  if (p < hw) {
+    const long px = b * hw + p;
+    const f16* pp = pred + px * ldp;
+    const f16* tp = target + px * ldt;
+    double e = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const float d = __fsub_rn((float)pp[c], (float)tp[c]);
+      e += (double)d * (double)d;  // the product of two f32 values is exact in f64
+    }
+    uint32_t n = 0;
+    if (mask) {
+      const int x = (int)(p % w);
+      const long y = p / w;
+      const uint16_t* m = mask + ((b * H + y * F) * W + (long)x * F) * ld_m;
+      for (int fy = 0; fy < F; ++fy)
+        for (int fx = 0; fx < F; ++fx) n += (m[((long)fy * W + fx) * ld_m] & 0x7FFFu) != 0 ? 1u : 0u;  // gn_loss_weight_pool's != 0
+    }
+    const double s = (double)n / (double)(F * F);
+    S = s * e;
+    G = (1.0 - s) * e;
+    n_d = (double)n;  // an integer below 2^53 all the way to the table: exact
+  }
+  S = lp_wave_sum(S);
+  G = lp_wave_sum(G);
+  n_d = lp_wave_sum(n_d);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = S;
+    red[1][threadIdx.x >> 6] = G;
+    red[2][threadIdx.x >> 6] = n_d;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) part[(long)blockIdx.x * 3 + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
+  }
+}
+
+// Stage two, one workgroup: thread i adds the partials of samples i, i + LP_THREADS, ... in range order and leaves the sample's sums in its
+// first partial; then thread 0 alone adds the samples into their rows, b = 0 .. B - 1.  No atomics: the order is the program's.
+__global__ __launch_bounds__(LP_THREADS) void mse_parts_final_kernel(double* __restrict__ part, const int32_t* __restrict__ bucket,
+                                                                     double* __restrict__ table, int B, int ranges, int n_buckets, double ff, double hw) {
+  if (blockIdx.x != 0) return;
+  for (int b = threadIdx.x; b < B; b += LP_THREADS) {
+    double* q = part + (long)b * ranges * 3;
+    double s = q[0], g = q[1], n = q[2];
+    for (int r = 1; r < ranges; ++r) {
+      s += q[r * 3L];
+      g += q[r * 3L + 1];
+      n += q[r * 3L + 2];
+    }
+    q[0] = s; q[1] = g; q[2] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int b = 0; b < B; ++b) {
+      const double* q = part + (long)b * ranges * 3;
+      const int32_t k = bucket[b];
+      double* row = table + (long)((k >= 0 && k < n_buckets) ? k : n_buckets) * 5;
+      row[0] += q[0];
+      row[1] += q[1];
+      row[2] += q[2] / ff;
+      row[3] += hw;
+      row[4] += 1.0;
+    }
+  }
+}
+
+inline int64_t lp_ranges(int64_t hw) { return cdiv64(hw, LP_THREADS); }
+
 inline unsigned lw_blocks(int64_t items) {
   const int64_t b = cdiv64(items, LW_THREADS);
   return (unsigned)(b < LW_MAX_BLOCKS ? b : LW_MAX_BLOCKS);
@@ -249,6 +340,40 @@ int32_t gn_mse_loss_weighted(gn_ctx* ctx, const void* pred, const void* target, 
                        wsum, (f16*)dpred, (float*)workspace, (long)pixels, C, ld_pred, ld_target, tvec, gscale2);
   GN_LAUNCH_CHECK();
   hipLaunchKernelGGL(mse_weighted_final_kernel, dim3(1), dim3(64), 0, ctx->stream, (const float*)workspace, wsum, loss_out, LW_LOSS_BLOCKS, C);
+  GN_LAUNCH_CHECK();
+  return GN_OK;
+}
+
+int64_t gn_mse_loss_parts_workspace_bytes(int32_t B, int32_t h, int32_t w) {
+  if (B <= 0 || h <= 0 || w <= 0) return 0;
+  return (int64_t)B * lp_ranges((int64_t)h * w) * 3 * (int64_t)sizeof(double);
+}
+
+int32_t gn_mse_loss_parts(gn_ctx* ctx, const void* pred, const void* target, const void* mask, const int32_t* bucket, double* table, void* workspace,
+                          int32_t B, int32_t h, int32_t w, int32_t C, int32_t ld_pred, int32_t ld_target, int32_t H, int32_t W, int32_t ld_m,
+                          int32_t n_buckets) {
+  GN_REQUIRE(ctx && pred && target && bucket && table && workspace, "gn_mse_loss_parts: null argument");
+  GN_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0 && ld_pred > 0 && ld_target > 0,
+             "gn_mse_loss_parts: B (%d), h (%d), w (%d), C (%d), ld_pred (%d), ld_target (%d) must be positive", B, h, w, C, ld_pred, ld_target);
+  GN_REQUIRE(C <= ld_pred && C <= ld_target, "gn_mse_loss_parts: C (%d) exceeds ld_pred (%d) or ld_target (%d)", C, ld_pred, ld_target);
+  GN_REQUIRE(n_buckets >= 1, "gn_mse_loss_parts: n_buckets (%d) must be at least 1", n_buckets);
+  int F = 1;
+  if (mask) {
+    GN_REQUIRE(H > 0 && W > 0 && ld_m > 0, "gn_mse_loss_parts: H (%d), W (%d), ld_m (%d) must be positive with a mask", H, W, ld_m);
+    GN_REQUIRE(H % h == 0 && W % w == 0 && H / h == W / w && H / h <= 16,
+               "gn_mse_loss_parts: H / h (%d / %d) and W / w (%d / %d) must be one whole factor in 1 .. 16", H, h, W, w);
+    F = H / h;
+  }
+  GN_REQUIRE(((uintptr_t)pred & 1) == 0 && ((uintptr_t)target & 1) == 0 && ((uintptr_t)mask & 1) == 0 && ((uintptr_t)bucket & 3) == 0 &&
+                 ((uintptr_t)table & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
+             "gn_mse_loss_parts: pred / target / mask must be 2-byte, bucket 4-byte, table and workspace 8-byte aligned");
+  const int64_t hw = (int64_t)h * w, ranges = lp_ranges(hw);
+  GN_REQUIRE(B * ranges <= 0x7FFFFFFF, "gn_mse_loss_parts: B * h * w (%ld) too large", (long)(B * hw));
+  hipLaunchKernelGGL(mse_parts_partial_kernel, dim3((unsigned)(B * ranges)), dim3(LP_THREADS), 0, ctx->stream, (const f16*)pred, (const f16*)target,
+                     (const uint16_t*)mask, (double*)workspace, (long)hw, (int)ranges, w, C, ld_pred, ld_target, H, W, (long)ld_m, F);
+  GN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mse_parts_final_kernel, dim3(1), dim3(LP_THREADS), 0, ctx->stream, (double*)workspace, bucket, table, B, (int)ranges, n_buckets,
+                     (double)(F * F), (double)hw);
   GN_LAUNCH_CHECK();
   return GN_OK;
 }

@@ -1,12 +1,14 @@
 """Host-side control flow around ``ControlNetTrainer`` that diffusion/train_controlnet_genima.py keeps in ``main``: the learning-rate
 schedule (``get_scheduler``, :1206-1213), checkpoint rotation under ``--checkpoints_total_limit`` (:1416-1457), ``--resume_from_checkpoint
-latest`` (:1281-1306) and the epoch / accumulation bookkeeping (:1196-1203, :1317-1320, :1410-1414).  No device work happens here."""
+latest`` (:1281-1306) and the epoch / accumulation bookkeeping (:1196-1203, :1317-1320, :1410-1414).  No device work happens here: the
+two loss read-outs (``TrainLoop(loss_parts_steps=)``, ``loss_validator``; not in the reference) call the trainer for theirs."""
 from __future__ import annotations
 
+import json
 import math
 import os
 import shutil
-from typing import Callable, Iterable, List, Optional
+from typing import Callable, Dict, Iterable, List, Optional, Sequence
 
 
 # ------------------------------------------------------------------------------------------------ diffusers.optimization.get_scheduler
@@ -98,17 +100,21 @@ def resolve_resume(output_dir: str, resume_from_checkpoint: Optional[str]) -> Op
 
 class TrainLoop:
     """The reference's ``for epoch ... for step, batch ...`` loop over a ``ControlNetTrainer``: accumulation-aware global step,
-    periodic ``save_state`` with rotation, resume, optional validation hook."""
+    periodic ``save_state`` with rotation, resume, optional validation hook.  ``loss_parts_steps`` (not in the reference; needs a trainer
+    with ``attach_frozen(loss_parts=N > 0)``, otherwise it does nothing): on the main process, every that many global steps, one JSON line
+    -- ``step`` and ``trainer.loss_parts_summary()`` of the micro-batches since the previous line -- goes to ``log`` and the table is reset."""
 
     def __init__(self, trainer, output_dir: str, *, max_train_steps: Optional[int] = None, num_train_epochs: int = 1,
                  checkpointing_steps: int = 500, checkpoints_total_limit: Optional[int] = None,
                  resume_from_checkpoint: Optional[str] = None, is_main_process: bool = True,
-                 validation_steps: Optional[int] = None, validate: Optional[Callable[[int], None]] = None, log=print):
+                 validation_steps: Optional[int] = None, validate: Optional[Callable[[int], None]] = None, log=print,
+                 loss_parts_steps: Optional[int] = None):
         self.trainer, self.output_dir = trainer, output_dir
         self.max_train_steps, self.num_train_epochs = max_train_steps, num_train_epochs
         self.checkpointing_steps, self.total_limit = checkpointing_steps, checkpoints_total_limit
         self.resume, self.is_main = resume_from_checkpoint, is_main_process
         self.validation_steps, self.validate, self.log = validation_steps, validate, log
+        self.loss_parts_steps = loss_parts_steps
         self.global_step = 0
 
     def run(self, dataloader: Iterable, len_dataloader: Optional[int] = None) -> int:
@@ -147,7 +153,43 @@ class TrainLoop:
                         self.log(f"Saved state to {tr.save_state(self.output_dir, self.global_step)}")
                     if self.is_main and self.validate is not None and self.validation_steps and self.global_step % self.validation_steps == 0:
                         self.validate(self.global_step)
+                    if self.is_main and self.loss_parts_steps and self.global_step % self.loss_parts_steps == 0 and getattr(tr, "loss_parts", 0) > 0:
+                        self.log(json.dumps(dict(step=self.global_step, **tr.loss_parts_summary(reset=True))))
                 self.last_loss = loss
                 if self.global_step >= max_steps:
                     return self.global_step
         return self.global_step
+
+
+# ------------------------------------------------------------------------------------------------ held-out loss at fixed noise
+# the timesteps the SD-Turbo call visits in 5 trailing steps (scheduler.EulerAncestralDiscreteScheduler().set_timesteps(5))
+LOSS_VALIDATOR_TIMESTEPS = (999, 799, 599, 399, 199)
+
+
+def loss_validator(trainer, batches: Sequence[Dict], *, timesteps: Sequence[int] = LOSS_VALIDATOR_TIMESTEPS, seed: int = 0, log=print):
+    """-> a ``validate(global_step)`` callable for ``TrainLoop`` (not in the reference): ``trainer.eval_loss`` over the held-out ``batches``
+    -- fixed batches, fixed noise (``seed``), the fixed ``timesteps`` grid, forward only -- summed into one table, read back once, and logged
+    as one JSON line: ``step``, ``select`` (= ``loss``, lower is better) and ``train_ops.summarize_parts``' dict with ``by_t`` per timestep.
+    The dict is also returned and appended to ``validate.history``.  Teacher-forced and at the training noise levels: comparable between
+    checkpoints of one run, not a success rate and not a score of generated images (``openloop.diffusion_validator`` is that, at 5 full
+    sampling steps per frame)."""
+    from .train_ops import summarize_parts
+
+    ts = [int(t) for t in timesteps]
+    batches = list(batches)
+
+    def validate(global_step: int) -> Dict:
+        table = None
+        for b in batches:
+            table = trainer.eval_loss(b, ts, seed=seed, table=table)
+        import torch
+        with torch.cuda.stream(trainer.E.stream):  # the copy waits for the kernels that filled the table, on the stream they ran on
+            host = table.cpu().numpy()
+        summary = summarize_parts(host,int(trainer.vae_cfg["latent_channels"]), ts)
+        line = dict(step=int(global_step), select=summary["loss"], **summary)
+        validate.history.append(line)
+        log(json.dumps(line))
+        return line
+
+    validate.history = []
+    return validate

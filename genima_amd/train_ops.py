@@ -413,6 +413,64 @@ def mse_loss_weighted(E: Engine, pred: torch.Tensor, target: torch.Tensor, weigh
     return loss, dpred
 
 
+PARTS_COLUMNS = ("S", "G", "A", "P", "n")  # a parts table's columns: marked / unmarked squared error, marked area, latent pixels, samples
+
+
+def mse_loss_parts(E: Engine, pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], bucket: torch.Tensor, table: torch.Tensor,
+                   C_valid: int) -> torch.Tensor:
+    """What a loss is made of (gn_mse_loss_parts; a read-out, no gradient): pred f16 [B, h, w, ldp], target f16 [B, h, w, ldt] (the first
+    ``C_valid`` channels valid), mask f16 [B, H, W, ld] (channel 0, H / h = W / w in 1 .. 16) or None = nothing marked, bucket int32 [B] on the
+    device.  Row ``bucket[b]`` of ``table`` (device f64 [n_buckets + 1, 5], ACCUMULATED into; a bucket out of range goes to the last row)
+    gains sample b's (squared error x marked share, x unmarked share, marked area in latent pixels, h w, 1).  -> table."""
+    if pred.dim() != 4 or tuple(target.shape[:3]) != tuple(pred.shape[:3]) or pred.dtype != F16 or target.dtype != F16:
+        raise ValueError(f"mse_loss_parts: pred / target must be f16 [B, h, w, ld] of one size, got {tuple(pred.shape)} {pred.dtype} / {tuple(target.shape)} {target.dtype}")
+    B, h, w, ldp = pred.shape
+    if bucket.dtype != torch.int32 or bucket.numel() != B or not bucket.is_cuda:
+        raise ValueError(f"mse_loss_parts: bucket must be int32 [{B}] on the device, got {tuple(bucket.shape)} {bucket.dtype} on {bucket.device}")
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[0] < 2 or table.shape[1] != 5 or not table.is_contiguous() or not table.is_cuda:
+        raise ValueError(f"mse_loss_parts: table must be a contiguous device f64 [n_buckets + 1, 5], got {tuple(table.shape)} {table.dtype}")
+    if mask is not None and (mask.dim() != 4 or mask.shape[0] != B or mask.dtype != F16):
+        raise ValueError(f"mse_loss_parts: mask must be f16 [{B}, H, W, ld], got {tuple(mask.shape)} {mask.dtype}")
+    H, W, ld_m = (int(s) for s in mask.shape[1:]) if mask is not None else (0, 0, 0)
+    ws = E._workspace(int(E.lib.gn_mse_loss_parts_workspace_bytes(B, h, w)))
+    check(E.lib.gn_mse_loss_parts(E._ctx, _ptr(pred), _ptr(target), _ptr(mask) if mask is not None else None, _ptr(bucket), _ptr(table), _ptr(ws), B, h, w,
+                                  int(C_valid), ldp, target.shape[-1], H, W, ld_m, table.shape[0] - 1), "gn_mse_loss_parts")
+    return table
+
+
+def summarize_parts(table_host, C: int, edges) -> dict:
+    """A parts table on the HOST (numpy [rows + 1, 5], columns ``PARTS_COLUMNS``, the last row = samples whose bucket was out of range) ->
+    the read-out.  ``edges``: rows + 1 ascending timestep bounds (row k covers t_lo = edges[k] .. t_hi = edges[k + 1] - 1), or rows single
+    timesteps (row k is ``t`` = edges[k]).  Touches no device.
+        loss = (sum S + sum G) / (C sum P), loss_sphere = sum S / (C sum A), loss_background = sum G / (C (sum P - sum A)),
+        sphere_area = sum A / sum P, n = samples, dropped = samples in the extra row (their error is in none of the sums)
+    and ``by_t``: the same three losses and n per row.  A loss whose denominator is 0 is None, never 0."""
+    import numpy as np
+
+    tab = np.asarray(table_host, dtype=np.float64)
+    if tab.ndim != 2 or tab.shape[1] != 5 or tab.shape[0] < 2:
+        raise ValueError(f"summarize_parts: table must be [rows + 1, 5], got {tab.shape}")
+    rows = tab.shape[0] - 1
+    edges = [int(e) for e in edges]
+    if len(edges) not in (rows, rows + 1):
+        raise ValueError(f"summarize_parts: {rows} rows need {rows} timesteps or {rows + 1} bounds, got {len(edges)}")
+    C = float(C)
+
+    def ratio(num, den):
+        return float(num / den) if den > 0.0 else None
+
+    def losses(S, G, A, P):
+        return dict(loss=ratio(S + G, C * P), loss_sphere=ratio(S, C * A), loss_background=ratio(G, C * (P - A)))
+
+    by_t = []
+    for k in range(rows):
+        S, G, A, P, n = (float(v) for v in tab[k])
+        where = dict(t=edges[k]) if len(edges) == rows else dict(t_lo=edges[k], t_hi=edges[k + 1] - 1)
+        by_t.append(dict(where, n=int(n), **losses(S, G, A, P)))
+    S, G, A, P, n = (float(v) for v in tab[:rows].sum(axis=0))
+    return dict(n=int(n), **losses(S, G, A, P), sphere_area=ratio(A, P), dropped=int(tab[rows, 4]), by_t=by_t)
+
+
 def sumsq(E: Engine, x: torch.Tensor, out: torch.Tensor):
     ws = E._workspace(8192)
     check(E.lib.gn_sumsq_f32(E._ctx, _ptr(x), x.numel(), _ptr(out), _ptr(ws)), "gn_sumsq_f32")

@@ -910,12 +910,16 @@ class ControlNetTrainer:
         return len(ws)
 
     # ---- forward + backward: fills self.cn.grad (loss-scaled) and returns the device loss scalar
-    def forward_backward(self, latents8, noise8, t_dev, sqrt_ac, sqrt_1mac, ctx, cond8, c_valid: int = 4, added=None, early=None, loss_weight=None):
+    def forward_backward(self, latents8, noise8, t_dev, sqrt_ac, sqrt_1mac, ctx, cond8, c_valid: int = 4, added=None, early=None, loss_weight=None,
+                         loss_parts=None):
         """latents8 / noise8: f16 [B, h, w, 8] (channels >= c_valid zero); t_dev f32 [B] timesteps; sqrt_ac / sqrt_1mac f32 [B]
         (DDPMScheduler.add_noise coefficients); ctx f16 [B, L, D] prompt states; cond8 f16 [B, H, W, 8] conditioning image in [0, 1];
         added = (text_embeds f16 [B, P], time_ids f32 [B, 6]) for the SDXL family (train_controlnet_sdxl_genima.py:1448-1471).
         ``loss_weight`` (not in the reference; ``attach_frozen(sphere_loss_weight=)``) = (weight f32 [B, h, w], wsum f64 [1] = its sum, both on
-        the device): the loss is the weighted mean sum(weight (pred - target)^2) / (c_valid wsum) instead of the plain mean.  None: the reference's."""
+        the device): the loss is the weighted mean sum(weight (pred - target)^2) / (c_valid wsum) instead of the plain mean.  None: the reference's.
+        ``loss_parts`` (not in the reference; ``attach_frozen(loss_parts=)``) = (mask f16 [B, H, W, 8] or None, bucket int32 [B], both on the
+        device): behind the loss launch, the UNWEIGHTED squared error of this micro-batch is added to the trainer's parts table
+        (gn_mse_loss_parts); loss and gradient are untouched.  None: nothing is launched."""
         E = self.E
         g = Graph(E)
         # ``early`` = (noisy latents, unet_frozen_front's result) already produced on the front stream (train_step)
@@ -951,6 +955,8 @@ class ControlNetTrainer:
             loss, dpred = T.mse_loss(E, pred.t, target, c_valid, grad_scale=self.loss_scale / self.grad_accum)
         else:
             loss, dpred = T.mse_loss_weighted(E, pred.t, target, loss_weight[0], loss_weight[1], c_valid, grad_scale=self.loss_scale / self.grad_accum)
+        if loss_parts is not None:
+            T.mse_loss_parts(E, pred.t, target, loss_parts[0], loss_parts[1], self._loss_parts_table(), c_valid)
         pred.cell[0] = dpred
         buckets = self.allreduce if hasattr(self.allreduce, "begin") else None
         if buckets is not None and self._will_sync():  # exchange only the LAST micro-batch's (accumulated) gradient
@@ -1065,8 +1071,13 @@ class ControlNetTrainer:
         self.last["pred"] = rec["pred"]
         return rec["loss"]
 
-    def step(self, latents8, noise8, t_dev, sqrt_ac, sqrt_1mac, ctx, cond8, added=None, early=None, loss_weight=None) -> torch.Tensor:
-        if loss_weight is not None:  # forward_backward's (weight, wsum): eager only
+    def step(self, latents8, noise8, t_dev, sqrt_ac, sqrt_1mac, ctx, cond8, added=None, early=None, loss_weight=None, loss_parts=None) -> torch.Tensor:
+        if loss_parts is not None:  # forward_backward's (mask, bucket), with or without a weighted loss: eager only
+            if self._use_graph:
+                raise ValueError("the loss parts (loss_parts > 0) are eager-only: not with the step replayed as a hipGraph")
+            loss = self.forward_backward(latents8, noise8, t_dev, sqrt_ac, sqrt_1mac, ctx, cond8, added=added, early=early, loss_weight=loss_weight,
+                                         loss_parts=loss_parts)
+        elif loss_weight is not None:  # forward_backward's (weight, wsum): eager only
             if self._use_graph:
                 raise ValueError("a weighted loss (sphere_loss_weight > 0) is eager-only: not with the step replayed as a hipGraph")
             loss = self.forward_backward(latents8, noise8, t_dev, sqrt_ac, sqrt_1mac, ctx, cond8, added=added, early=early, loss_weight=loss_weight)
@@ -1150,7 +1161,7 @@ class ControlNetTrainer:
 
     def attach_frozen(self, vae_cfg, vae_W, text_cfg, text_W, noise_scheduler, seed: int = 0, text2_cfg=None, text2_W=None,
                       augmentations: Optional[str] = None, tiny_vae: bool = False, sphere_loss_weight: float = 0.0,
-                      sphere_change_threshold: int = 30):
+                      sphere_change_threshold: int = 30, loss_parts: int = 0):
         """Frozen fp16 VAE / CLIP text tower(s) (packed weights) and the DDPMScheduler (diffusion/train_controlnet_genima.py:1038-1060;
         SDXL: the second, projection tower of train_controlnet_sdxl_genima.py:1027-1071 as ``text2_*``).  ``tiny_vae`` (the reference's
         --tiny_vae, :469-473, 1049-1050, 1324-1327; SDXL :504-508, 1077-1078, 1408-1411): the VAE is an AutoencoderTiny (taesd / taesdxl
@@ -1163,7 +1174,24 @@ class ControlNetTrainer:
         step's scale whatever the weight (no learning-rate re-tuning) and tends to the sphere-only loss as the weight grows.  The mask follows
         the shared augmentations (affine, crop).  ``self.last["sphere_fraction"]``: the marked share of the batch's pixels, a device scalar.
         Eager only (not with ``hip_graph``).  Under data parallelism each rank normalises by its OWN sum of weights: the ranks' gradients are
-        then averaged as usual, so a rank with fewer marked pixels is not down-weighted against the others."""
+        then averaged as usual, so a rank with fewer marked pixels is not down-weighted against the others.
+
+        ``loss_parts`` (NOT in the reference; 0 = off = the step's launches as they are): a read-out of what the training loss is made of.
+        With N > 0 every micro-batch's UNWEIGHTED squared error -- whatever ``sphere_loss_weight`` is, so runs with different weights compare
+        -- is split into its marked (sphere, the marking rule above) and unmarked share and by N equal timestep buckets over
+        ``num_train_timesteps`` (bucket = t * N // num_train_timesteps), and accumulated in a device table by gn_mse_loss_parts; weights,
+        gradients and losses keep their bits.  ``loss_parts_summary()`` reads it: the only copy to the host.  Eager only, ControlNet trainers
+        only.  Under data parallelism each rank keeps its OWN table of its own micro-batches: nothing is reduced across ranks."""
+        try:
+            parts_ok = not isinstance(loss_parts, bool) and int(loss_parts) == loss_parts and loss_parts >= 0
+        except (TypeError, ValueError, OverflowError):
+            parts_ok = False
+        if not parts_ok:
+            raise ValueError(f"loss_parts must be an integer >= 0 (the number of timestep buckets, 0 = off), got {loss_parts!r}")
+        if loss_parts > 0 and not self.supports_sphere_loss:
+            raise ValueError(f"{type(self).__name__} does not take loss_parts (ControlNet trainers only)")
+        if loss_parts > 0 and self._use_graph:
+            raise ValueError("loss_parts > 0 is eager-only: not with the step replayed as a hipGraph (hip_graph=True / GN_TRAIN_GRAPH)")
         if not sphere_loss_weight >= 0.0 or not math.isfinite(sphere_loss_weight):
             raise ValueError(f"sphere_loss_weight must be finite and >= 0, got {sphere_loss_weight!r}")
         if int(sphere_change_threshold) != sphere_change_threshold or sphere_change_threshold < 0:
@@ -1173,6 +1201,7 @@ class ControlNetTrainer:
         if sphere_loss_weight > 0.0 and self._use_graph:
             raise ValueError("sphere_loss_weight > 0 is eager-only: not with the step replayed as a hipGraph (hip_graph=True / GN_TRAIN_GRAPH)")
         self.sphere_loss_weight, self.sphere_change_threshold = float(sphere_loss_weight), int(sphere_change_threshold)
+        self.loss_parts, self._parts_table = int(loss_parts), None  # the table: device f64 [loss_parts + 1, 5], made at its first use
         self.vae_cfg, self.vae_W, self.text_cfg, self.text_W, self.noise_scheduler = vae_cfg, vae_W, text_cfg, text_W, noise_scheduler
         self.tiny_vae = bool(tiny_vae)
         self.text2_cfg, self.text2_W = text2_cfg, text2_W
@@ -1211,14 +1240,17 @@ class ControlNetTrainer:
                 noisy = E.add_noise(lat8, noise8, sa, s1)
                 sh, h, skips = unet_frozen_front(E, self.unet, self.unet_cfg, noisy, t_dev, ctx, added)
                 early = (noisy, sh, h, tuple(skips))
-            return lat8, noise8, t_dev, sa, s1, ctx, cond8, added, early, (lw[0] if lw else None)
-        lat8, noise8, t_dev, sa, s1, ctx, cond8, added, early, lw = self._on_front_stream(front, batch)
+            return lat8, noise8, t_dev, sa, s1, ctx, cond8, added, early, (lw[0] if lw else None), (lw[1] if len(lw) > 1 else None)
+        lat8, noise8, t_dev, sa, s1, ctx, cond8, added, early, lw, parts = self._on_front_stream(front, batch)
         if early is not None:
             early = (early[0], (early[1], early[2], list(early[3])))
-        if lw is None:
+        if lw is None and parts is None:
             loss = self.step(lat8, noise8, t_dev, sa, s1, ctx, cond8, added, early=early)
-        else:  # sphere_loss_weight > 0: the front's (weight, wsum, marked share)
+        elif parts is None:  # sphere_loss_weight > 0: the front's (weight, wsum, marked share)
             loss = self.step(lat8, noise8, t_dev, sa, s1, ctx, cond8, added, early=early, loss_weight=lw[:2])
+        else:  # loss_parts > 0: the front's (mask, bucket) as well
+            loss = self.step(lat8, noise8, t_dev, sa, s1, ctx, cond8, added, early=early, loss_weight=None if lw is None else lw[:2], loss_parts=parts)
+        if lw is not None:
             self.__dict__["_st_last"]["sphere_fraction"] = lw[2]  # (the dict behind ``last``, not the property: that would wait for this step's optimizer)
         self._steps_seen += 1
         if self._gc_freeze and self._steps_seen == 2:
@@ -1264,24 +1296,46 @@ class ControlNetTrainer:
         return out
 
     def _front(self, batch):
+        """The step's front.  -> (latents, noise, t, sqrt_ac, sqrt_1mac, prompt states, conditioning image, added), then, with
+        ``sphere_loss_weight`` > 0 or ``loss_parts`` > 0 only, (weight, wsum, marked share) or None, and with ``loss_parts`` > 0 only,
+        (mask, bucket int32 [B] on the device)."""
+        lam, nparts = getattr(self, "sphere_loss_weight", 0.0), getattr(self, "loss_parts", 0)
+        batch, x8, cond8, mask, lat8, noise8, ids = self._front_latents(batch, self._gen_dev, self._gen_cpu, lam > 0.0 or nparts > 0)
+        ntt = int(self.noise_scheduler.config.num_train_timesteps)
+        t = torch.randint(0, ntt, (x8.shape[0],), generator=self._gen_cpu)
+        sa, s1 = self.noise_scheduler.add_noise_coeffs(t)
+        ctx, added = self._front_text(batch, x8, ids)
+        out = (lat8, noise8, t, sa, s1, ctx, cond8, added)
+        if mask is None:
+            return out
+        lw = None
+        if lam > 0.0:  # pooled to the latent size the encoder actually produced (VAE or tiny_vae); everything stays on the device
+            weight, count, wsum = T.loss_weight_pool(self.E, mask, int(lat8.shape[1]), int(lat8.shape[2]), lam)
+            lw = (weight, wsum, count[0].to(F32) / float(mask.shape[0] * mask.shape[1] * mask.shape[2]))
+        if nparts <= 0:
+            return out + (lw,)
+        bucket = (t * nparts // ntt).to(torch.int32).to(self.E.device)  # uploaded beside t
+        return out + (lw, (mask, bucket))
+
+    def _front_latents(self, batch, gen_dev, gen_cpu, want_mask: bool):
+        """Upload, change mask, augmentations (``gen_cpu`` None: none), VAE encode with the posterior draw, the noise draw.
+        -> (batch on the device, target image, conditioning image, mask or None, latents, noise, input ids)."""
         E, dev = self.E, self.E.device
         if "pixel_values_u8" in batch or "frame_slots" in batch or "render_views" in batch:  # the uint8 NHWC host batch of genima_amd/data.py, or its device frame cache's: ToTensor + Normalize happen on the device
             from .data import to_device
             batch = to_device(E, batch)
         x8 = self._nhwc8(batch["pixel_values"])
         cond8 = self._nhwc8(batch["conditioning_pixel_values"])
-        lam = getattr(self, "sphere_loss_weight", 0.0)
-        # sphere_loss_weight > 0: mark where the target differs from the conditioning image BEFORE the augmentations (jitter and blur change
-        # the conditioning image alone); the mask then follows the geometry both images share
-        mask = T.change_mask(E, x8, cond8, self.sphere_change_threshold) if lam > 0.0 else None
-        if self.augmentations:  # augment_data(args, batch) (:1321): jitter + blur on the conditioning image, shared affine and crop
+        # sphere_loss_weight > 0 or loss_parts > 0: mark where the target differs from the conditioning image BEFORE the augmentations (jitter
+        # and blur change the conditioning image alone), ONCE for both; the mask then follows the geometry both images share
+        mask = T.change_mask(E, x8, cond8, self.sphere_change_threshold) if want_mask else None
+        if self.augmentations and gen_cpu is not None:  # augment_data(args, batch) (:1321): jitter + blur on the conditioning image, shared affine and crop
             from .augment import augment_data
-            aug = augment_data(E, self.augmentations, dict(pixel_values=x8, conditioning_pixel_values=cond8), self._gen_cpu,
+            aug = augment_data(E, self.augmentations, dict(pixel_values=x8, conditioning_pixel_values=cond8), gen_cpu,
                                **({} if mask is None else dict(extra=dict(sphere_mask=mask))))
             x8, cond8 = aug["pixel_values"], aug["conditioning_pixel_values"]
             mask = aug["sphere_mask"] if mask is not None else None
         ids = batch["input_ids"].to(dev, torch.int32).contiguous()
-        B = x8.shape[0]
         Cl = self.vae_cfg["latent_channels"]
         if getattr(self, "tiny_vae", False):  # the noise is then the device generator's first draw of the step, as in the reference
             lat8 = graphs.emit_taesd_encode(E, self.vae_W, self.vae_cfg, x8)
@@ -1289,11 +1343,15 @@ class ControlNetTrainer:
         else:
             mom = graphs.emit_vae_encode_moments(E, self.vae_W, self.vae_cfg, x8)
             shape = tuple(mom.shape[:-1]) + (Cl,)
-            lat8 = T.latent_sample(E, mom, torch.randn(shape, generator=self._gen_dev, device=dev, dtype=F32).to(F16), Cl,
+            lat8 = T.latent_sample(E, mom, torch.randn(shape, generator=gen_dev, device=dev, dtype=F32).to(F16), Cl,
                                    self.vae_cfg.get("scaling_factor", 0.18215))
-        noise8 = E.scale_pad(torch.randn(shape, generator=self._gen_dev, device=dev, dtype=F32).to(F16), 1.0, 8)
-        t = torch.randint(0, int(self.noise_scheduler.config.num_train_timesteps), (B,), generator=self._gen_cpu)
-        sa, s1 = self.noise_scheduler.add_noise_coeffs(t)
+        noise8 = E.scale_pad(torch.randn(shape, generator=gen_dev, device=dev, dtype=F32).to(F16), 1.0, 8)
+        return batch, x8, cond8, mask, lat8, noise8, ids
+
+    def _front_text(self, batch, x8, ids):
+        """The text tower(s) on ``_front_latents``' batch and input ids.  -> (prompt states, added conditions or None)."""
+        E, dev = self.E, self.E.device
+        B = x8.shape[0]
         added = None
         if getattr(self, "text2_W", None) is None:
             ctx = graphs.emit_clip_text(E, self.text_W, self.text_cfg, ids)
@@ -1309,8 +1367,76 @@ class ControlNetTrainer:
             E.copy4d(pen_g, ctx[:, :, dl:], (1, 1, B, L), (0, 0, L * dg, dg), (0, 0, L * (dl + dg), dl + dg), dg)
             R = float(x8.shape[1])
             added = (pooled, torch.tensor([[R, R, 0.0, 0.0, R, R]] * B, dtype=F32, device=dev))
-        if mask is not None:  # pooled to the latent size the encoder actually produced (VAE or tiny_vae); everything stays on the device
-            weight, count, wsum = T.loss_weight_pool(E, mask, int(lat8.shape[1]), int(lat8.shape[2]), lam)
-            frac = count[0].to(F32) / float(mask.shape[0] * mask.shape[1] * mask.shape[2])
-            return lat8, noise8, t, sa, s1, ctx, cond8, added, (weight, wsum, frac)
-        return lat8, noise8, t, sa, s1, ctx, cond8, added
+        return ctx, added
+
+    # ---- read-outs (not in the reference): what the training loss is made of, and a held-out loss at fixed noise
+    def _loss_parts_table(self) -> torch.Tensor:
+        n = getattr(self, "loss_parts", 0)
+        if n <= 0:
+            raise ValueError("the loss parts are off: pass attach_frozen(..., loss_parts=N) with N > 0 timestep buckets")
+        if self._parts_table is None:
+            with torch.cuda.stream(self.E.stream):
+                self._parts_table = torch.zeros((n + 1, 5), dtype=torch.float64, device=self.E.device)
+        return self._parts_table
+
+    def _parts_edges(self) -> List[int]:
+        """Row k of the training table holds the timesteps with t * N // T == k: t from ceil(k T / N) up to ceil((k + 1) T / N) - 1."""
+        n, ntt = self.loss_parts, int(self.noise_scheduler.config.num_train_timesteps)
+        return [-(-k * ntt // n) for k in range(n + 1)]
+
+    def loss_parts_summary(self, reset: bool = True) -> dict:
+        """What the micro-batches since the last reset were made of (``attach_frozen(loss_parts=N)``): ONE copy of the device table to the
+        host (it waits for the steps issued so far), then ``train_ops.summarize_parts`` -- ``loss``, ``loss_sphere``, ``loss_background``
+        (the unweighted mean squared error over all / the marked / the unmarked share of the latent pixels), ``sphere_area``, ``n`` samples,
+        ``dropped``, and ``by_t`` per timestep bucket ``t_lo .. t_hi``.  ``reset``: zero the table behind the copy.  Every micro-batch of an
+        accumulated step counts; under data parallelism the table is THIS rank's."""
+        table = self._loss_parts_table()
+        with torch.cuda.stream(self.E.stream):
+            host = table.cpu()
+            if reset:
+                table.zero_()
+        return T.summarize_parts(host.numpy(), int(self.vae_cfg["latent_channels"]), self._parts_edges())
+
+    def eval_loss(self, batch, timesteps: Sequence[int], *, seed: int = 0, table: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A held-out loss that compares between checkpoints: the batch (any form ``train_step`` takes) WITHOUT augmentations, the posterior
+        draw and ONE noise tensor from a device generator of its own seeded with ``seed`` (nothing is drawn from the training generators),
+        VAE encode, text tower(s) and the change mask once; then for k, t in enumerate(timesteps) the whole batch noised to t, ControlNet +
+        UNet FORWARD only, and gn_mse_loss_parts with bucket k for every sample (``v_prediction``: the step's target rule).
+        -> the device f64 [len(timesteps) + 1, 5] table (``table``: accumulate into this one instead of a fresh one); read it with
+        ``train_ops.summarize_parts(table.cpu().numpy(), latent_channels, timesteps)``.  Teacher-forced: the network sees the true latents
+        noised to t, not its own samples.  Weights, gradient, moments, optimizer and scaler state, the micro-batch counter, both training
+        generators and ``last`` are left as they are; no gradient exchange is started.  Works whatever ``loss_parts`` is.  Eager only,
+        ControlNet trainers only."""
+        if not self.supports_sphere_loss:
+            raise ValueError(f"{type(self).__name__} has no eval_loss (ControlNet trainers only)")
+        if self._use_graph:
+            raise ValueError("eval_loss is eager-only: not on a trainer that replays its step as a hipGraph (hip_graph=True / GN_TRAIN_GRAPH)")
+        ntt = int(self.noise_scheduler.config.num_train_timesteps)
+        ts = [int(t) for t in timesteps]
+        if not ts or any(t != u or not 0 <= t < ntt for t, u in zip(ts, timesteps)):
+            raise ValueError(f"eval_loss: timesteps must be integers in 0 .. {ntt - 1}, at least one, got {list(timesteps)!r}")
+        E, dev = self.E, self.E.device
+        with torch.cuda.stream(E.stream):
+            if table is None:
+                table = torch.zeros((len(ts) + 1, 5), dtype=torch.float64, device=dev)
+            elif tuple(table.shape) != (len(ts) + 1, 5) or table.dtype != torch.float64:
+                raise ValueError(f"eval_loss: table must be f64 [{len(ts) + 1}, 5], got {tuple(table.shape)} {table.dtype}")
+            gen = torch.Generator(device=dev).manual_seed(int(seed))
+            batch, x8, cond8, mask, lat8, noise8, ids = self._front_latents(batch, gen, None, True)
+            ctx, added = self._front_text(batch, x8, ids)
+            ctx_pad, L = pad_context(ctx), ctx.shape[1]
+            B, Cl = x8.shape[0], int(self.vae_cfg["latent_channels"])
+            for k, t in enumerate(ts):
+                tt = torch.full((B,), t, dtype=torch.long)
+                sa, s1 = (c.to(dev) for c in self.noise_scheduler.add_noise_coeffs(tt))
+                t_dev = tt.to(dev, F32)
+                noisy = E.add_noise(lat8, noise8, sa, s1)
+                g = Graph(E)  # the step's own forward; its tape is dropped unwalked
+                down, mid = t_controlnet(g, self.cn, self.cn_cfg, noisy, t_dev, ctx_pad, L, cond8, added)
+                pred = t_unet(g, self.unet, self.unet_cfg, noisy, t_dev, ctx, ctx_pad, L, down, mid, added)
+                target = noise8
+                if getattr(self, "prediction_type", "epsilon") == "v_prediction":
+                    target = E.add_noise(noise8, lat8, sa, -s1)
+                T.mse_loss_parts(E, pred.t, target, mask, torch.full((B,), k, dtype=torch.int32, device=dev), table, Cl)
+                g.tape.clear()
+        return table

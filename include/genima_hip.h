@@ -690,6 +690,22 @@ int32_t gn_loss_weight_pool(gn_ctx* ctx, const void* mask, int32_t ld_m, float* 
  * fixed-order two-stage reduction (the same workspace).  dpred may be NULL.  With weight == 1 and wsum == pixels, dpred has gn_mse_loss's bits. */
 int32_t gn_mse_loss_weighted(gn_ctx* ctx, const void* pred, const void* target, const float* weight, const double* wsum, void* dpred, float* loss_out,
                              void* workspace, int64_t pixels, int32_t C, int32_t ld_pred, int32_t ld_target, float grad_scale);
+/* gn_mse_loss_parts: what a loss is made of -- a READ-OUT (ControlNetTrainer's loss_parts / eval_loss), never a loss: it produces no gradient.
+ * pred f16 [B][h][w][ld_pred], target f16 [B][h][w][ld_target] (the first C channels valid); mask f16 [B][H][W][ld_m] (channel 0 is read,
+ * F = H / h = W / w in 1 .. 16) or NULL = nothing marked (H, W, ld_m are then ignored); bucket int32 [B] in device memory; table f64
+ * [n_buckets + 1][5], 8-byte aligned, ACCUMULATED into (the caller zeroes it); workspace: gn_mse_loss_parts_workspace_bytes(B, h, w),
+ * 8-byte aligned.  Per latent pixel p of sample b: n_p = the mask pixels of its F x F block whose channel 0 is != 0, s_p = n_p / (F F) in
+ * f64, d = (float)pred - (float)target (one f32 subtraction), e_p = sum_{c < C} (double)d (double)d in f64.  Per sample:
+ *   S_b = sum_p s_p e_p,  G_b = sum_p (1 - s_p) e_p,  A_b = (sum_p n_p) / (F F) (the count is kept as an integer),  P_b = h w
+ * and row bucket[b] of the table gains (S_b, G_b, A_b, P_b, 1), b = 0 .. B - 1 in that order by one thread; a bucket[b] outside
+ * 0 .. n_buckets - 1 goes to the extra last row.  Two stages in a fixed order (contiguous ranges of 256 pixels through a fixed lane tree,
+ * then the ranges in index order), no floating-point atomics: every run gives the same bits.  Never synchronises.  Refused before the
+ * first launch (nothing is written): a NULL pointer other than mask, a size <= 0, C > ld_pred or C > ld_target, n_buckets < 1, a
+ * misaligned pointer, and with a mask H % h, W % w, H / h != W / w or F > 16. */
+int64_t gn_mse_loss_parts_workspace_bytes(int32_t B, int32_t h, int32_t w);
+int32_t gn_mse_loss_parts(gn_ctx* ctx, const void* pred, const void* target, const void* mask, const int32_t* bucket, double* table, void* workspace,
+                          int32_t B, int32_t h, int32_t w, int32_t C, int32_t ld_pred, int32_t ld_target, int32_t H, int32_t W, int32_t ld_m,
+                          int32_t n_buckets);
 int32_t gn_sumsq_f32(gn_ctx* ctx, const float* x, int64_t n, float* out, void* workspace);
 /* global-norm clipping after loss-scale removal (accelerator.clip_grad_norm_, diffusion/train_controlnet_genima.py:1403-1405):
  * norm = sqrt(sumsq[0]) * inv_scale; clip[0] = min(1, max_norm / (norm + 1e-6)); clip[1] = norm; clip[2] = 1 when non-finite
