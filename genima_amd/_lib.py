@@ -249,6 +249,7 @@ SIGNATURES = {
     "gn_replay_render": (_I32, [_P, C.POINTER(ReplayRenderDesc)]),
     "gn_openloop_image_metrics": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_openloop_sphere_metrics": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "gn_openloop_orientation": (_I32, [_P] * 14 + [_I32] * 14),
     "gn_openloop_action_metrics": (_I32, [_P, _P, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_openloop_exec_actions": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_openloop_exec_metrics": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32]),

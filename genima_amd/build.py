@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libgenima_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm_pp.hip", "gemm_ppp.hip", "gemm_s3.hip", "gemm_tn.hip", "attention.hip", "attention_stream.hip", "attention_pwg.hip", "attention_bwd.hip", "attention_fp8.hip", "norm.hip", "elementwise.hip", "backward.hip", "optim8.hip", "augment.hip", "fp8.hip", "comm.hip", "act_train.hip", "pack.hip", "tblock.hip", "conv_gn.hip", "conv_patch.hip", "taesd.hip", "render.hip", "ensemble.hip", "replay.hip", "replay_render.hip", "openloop.hip", "loss_weight.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_pp.hip", "gemm_ppp.hip", "gemm_s3.hip", "gemm_tn.hip", "attention.hip", "attention_stream.hip", "attention_pwg.hip", "attention_bwd.hip", "attention_fp8.hip", "norm.hip", "elementwise.hip", "backward.hip", "optim8.hip", "augment.hip", "fp8.hip", "comm.hip", "act_train.hip", "pack.hip", "tblock.hip", "conv_gn.hip", "conv_patch.hip", "taesd.hip", "render.hip", "ensemble.hip", "replay.hip", "replay_render.hip", "openloop.hip", "openloop_orient.hip", "loss_weight.hip"]
 # -amdgpu-mfma-vgpr-form: gfx950's register file is unified, so keep MFMA accumulators in VGPRs -- the softmax / epilogue VALU
 # then works on them in place instead of through v_accvgpr_read/write copies (400 of them per attention tile otherwise).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
@@ -25,9 +25,10 @@ _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]  # measured: helps attention
 # mode fuses in the backend whatever a source-level `#pragma clang fp contract(off)` says)
 # render.hip, replay_render.hip: likewise -- their blend is numpy's unfused f64 multiply / multiply / add, compared bit for bit
 # openloop.hip: likewise -- its joint sum is stated as one f32 subtraction, multiplication and addition per term
+# openloop_orient.hip: likewise -- it draws with render_common.h, and its candidates' pixels are compared with render.hip's bit for bit
 # (gn_openloop_exec_actions replays ensemble.hip's rule bit for bit, so it is compiled IN ensemble.hip, under that file's flags, not here)
 # loss_weight.hip: likewise -- the mask's byte rule and the pooled weight are stated one rounded f32 operation at a time
-EXTRA_FLAGS = {"optim8.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"], "replay_render.hip": ["-ffp-contract=off"], "openloop.hip": ["-ffp-contract=off"], "loss_weight.hip": ["-ffp-contract=off"],"attention.hip": _VGPR_FORM, "attention_stream.hip": _VGPR_FORM, "attention_pwg.hip": _VGPR_FORM, "attention_bwd.hip": _VGPR_FORM, "attention_fp8.hip": _VGPR_FORM}
+EXTRA_FLAGS = {"optim8.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"], "replay_render.hip": ["-ffp-contract=off"], "openloop.hip": ["-ffp-contract=off"], "openloop_orient.hip": ["-ffp-contract=off"], "loss_weight.hip": ["-ffp-contract=off"],"attention.hip": _VGPR_FORM, "attention_stream.hip": _VGPR_FORM, "attention_pwg.hip": _VGPR_FORM, "attention_bwd.hip": _VGPR_FORM, "attention_fp8.hip": _VGPR_FORM}
 
 
 def _hipcc() -> str:
@@ -61,7 +62,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "attention_common.h", "attention_dropout.h", "ensemble_common.h", "gn_bridge.h", "image_convert.h", "render_common.h", "replay_common.h")] + [os.path.join(HERE, "..", "include", "genima_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "attention_common.h", "attention_dropout.h", "ensemble_common.h", "gn_bridge.h", "image_convert.h", "openloop_common.h", "render_common.h", "replay_common.h")] + [os.path.join(HERE, "..", "include", "genima_hip.h")]
     # the objects are only as good as the flags they were built with: a probe build (GN_HIPCC_EXTRA=-DGN_PP_ABLATIONS ..., some of which give wrong
     # results on purpose) must never be reused by the next normal build, nor the other way round -- the flag set is stamped beside the objects
     stamp = os.path.join(objdir, ".flags")

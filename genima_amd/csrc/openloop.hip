@@ -26,29 +26,9 @@
 // batch: the thread walks the at most 8 views twice -- once to sum the normal equations of the closest point to the used rays, once for the
 // residuals at the solved point -- and rebuilds each ray from the tables both times instead of keeping eight of them in scratch.  All f64, no
 // contraction (this file's flag), the 3x3 system through its adjugate in one written order; the thread stores its own eight values.
-#include "common.h"
+#include "openloop_common.h"
 
 namespace {
-
-constexpr int OL_THREADS = 256;
-
-typedef const __attribute__((address_space(1))) uint8_t* ol_gptr8;  // global_load, not flat_load
-typedef const __attribute__((address_space(1))) uint32_t* ol_gptr32;
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t ol_dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
-}
-// common.h's wave_sum on unsigned integers: every lane gets the wave's total; all 64 lanes must be active
-__device__ __forceinline__ uint32_t ol_wave_sum(uint32_t v) {
-  v += ol_dpp<0xB1>(v);
-  v += ol_dpp<0x4E>(v);
-  v += ol_dpp<0x141>(v);
-  v += ol_dpp<0x140>(v);
-  const int b = (int)v;
-  return ((uint32_t)__builtin_amdgcn_readlane(b, 0) + (uint32_t)__builtin_amdgcn_readlane(b, 16)) +
-         ((uint32_t)__builtin_amdgcn_readlane(b, 32) + (uint32_t)__builtin_amdgcn_readlane(b, 48));
-}
 
 struct ol_acc {
   uint32_t v[5];  // se_in, n_in, se_out, n_out, wrap_sq
@@ -122,10 +102,7 @@ __global__ __launch_bounds__(OL_THREADS) void openloop_image_kernel(const uint8_
   }
 }
 
-constexpr int OL_WIN_MAX = 256;  // a window's longest side
 constexpr int OL_SPH_COLS = 17;
-
-__device__ __forceinline__ int ol_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(OL_THREADS) void openloop_sphere_kernel(const uint8_t* __restrict__ gen, const uint8_t* __restrict__ gt,
                                                                      const uint8_t* __restrict__ cond, const uint8_t* __restrict__ occupied,
@@ -395,12 +372,8 @@ int32_t gn_openloop_sphere_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_
   GN_REQUIRE(((uintptr_t)win & 3) == 0 && ((uintptr_t)win_host & 3) == 0 && ((uintptr_t)sph_out & 7) == 0,
              "gn_openloop_sphere_metrics: win must be 4-byte and sph_out 8-byte aligned");
   if (win_host) {
-    for (int64_t i = 0; i < (int64_t)B * V * S; ++i) {
-      const int32_t* q = win_host + i * 4;
-      GN_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[2] >= q[0] && q[3] >= q[1] && q[2] <= W && q[3] <= H && q[2] - q[0] <= OL_WIN_MAX && q[3] - q[1] <= OL_WIN_MAX,
-                 "gn_openloop_sphere_metrics: window %ld = (%d, %d, %d, %d) must lie inside the %d x %d image with x0 <= x1, y0 <= y1 and at most %d per side",
-                 (long)i, q[0], q[1], q[2], q[3], W, H, OL_WIN_MAX);
-    }
+    const int32_t rc = ol_check_windows("gn_openloop_sphere_metrics", win_host, (int64_t)B * V * S, W, H);
+    if (rc != GN_OK) return rc;
   }
   if (n_valid == 0) return GN_OK;
   hipLaunchKernelGGL(openloop_sphere_kernel, dim3((unsigned)S, (unsigned)V, (unsigned)n_valid), dim3(OL_THREADS), 0, ctx->stream, gen, gt, cond, occupied, win,

@@ -1501,6 +1501,44 @@ class Engine:
               "gn_openloop_sphere_metrics")
         return out
 
+    def openloop_orientation(self, gen, gt, occupied, win, cams, spheres, tex_index, count, atlas, rot, out, *, samples: int = 4, shift=None,
+                             row0: int = 0, n_valid: Optional[int] = None, win_host=None):
+        """``gn_openloop_orientation``: ``gen`` / ``gt`` / ``occupied`` / ``win`` / ``win_host`` as ``openloop_sphere_metrics`` takes them,
+        ``cams`` f32 [B * V, 18], ``spheres`` f32 [B * V, S, 16], ``tex_index`` int32 [B * V, S], ``count`` int32 [B * V], ``atlas`` uint8
+        [T, th, tw, 4] and ``samples`` as ``render_spheres`` takes them, ``rot`` f32 [K, 9] on the device (K candidate rotations in the
+        sphere's own frame, ``openloop.orientation_candidates``), ``shift`` int32 [B * V, S, 2] on the device or None (where ``gen`` is read
+        relative to the window) -> rows ``row0 .. row0 + n_valid - 1`` of ``out`` int64 [rows, V, S, K, 4] = per candidate the squared error of
+        the re-drawn sphere against ``gen`` and its pixel count, the same against ``gt`` and its count; samples ``b >= n_valid`` (default B)
+        write nothing.  Eager engines only."""
+        if self.record:
+            raise RuntimeError("openloop_orientation is an eager op: the result rows change from batch to batch")
+        if rot.dim() != 2 or win.dim() != 3 or atlas.dim() != 4 or atlas.shape[3] != 4 or out.dim() != 5:
+            raise GenimaHipError("openloop_orientation: rot must be f32 [K, 9], win int32 [B * V, S, 4], atlas uint8 [T, th, tw, 4] and out int64 [rows, V, S, K, 4]")
+        H, W = int(gt.shape[1]), int(gt.shape[2])
+        tiled = gen.dim() == 4
+        B = int(gen.shape[0])
+        V = 4 if tiled else int(gen.shape[1])
+        S, K, rows = int(win.shape[1]), int(rot.shape[0]), int(out.shape[0])
+        for t, dt, shape in ((gen, torch.uint8, (B, 2 * H, 2 * W, 3) if tiled else (B, V, H, W, 3)), (gt, torch.uint8, (B * V, H, W, 3)),
+                             (occupied, torch.uint8, (B * V, H, W)), (win, torch.int32, (B * V, S, 4)), (cams, torch.float32, (B * V, 18)),
+                             (spheres, torch.float32, (B * V, S, 16)), (tex_index, torch.int32, (B * V, S)), (count, torch.int32, (B * V,)),
+                             (atlas, torch.uint8, tuple(atlas.shape)), (rot, torch.float32, (K, 9)), (shift, torch.int32, (B * V, S, 2)),
+                             (out, torch.int64, (rows, V, S, K, 4))):
+            if t is shift and t is None:
+                continue
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                raise GenimaHipError(f"openloop_orientation: a contiguous device tensor {dt} {shape} expected")
+        hp = None
+        if win_host is not None:
+            if not (str(win_host.dtype) == "int32" and win_host.flags.c_contiguous and win_host.shape == (B * V, S, 4)):
+                raise GenimaHipError(f"openloop_orientation: a contiguous int32 host copy {(B * V, S, 4)} expected, got {win_host.dtype} {win_host.shape}")
+            hp = win_host.ctypes.data
+        check(self.lib.gn_openloop_orientation(self._ctx, _ptr(gen), _ptr(gt), _ptr(occupied), _ptr(win), hp, _ptr(cams), _ptr(spheres), _ptr(tex_index),
+                                               _ptr(count), _ptr(atlas), _ptr(rot), _ptr(shift), _ptr(out), B, V, H, W, S, K, int(atlas.shape[0]),
+                                               int(atlas.shape[1]), int(atlas.shape[2]), int(samples), int(tiled), int(row0),
+                                               B if n_valid is None else int(n_valid), rows), "gn_openloop_orientation")
+        return out
+
     def openloop_action_metrics(self, a_hat, actions, out, *, joint_scale=None, row0: int = 0, n_valid: Optional[int] = None):
         """``gn_openloop_action_metrics``: ``a_hat`` f16 [B, T, >= A] (any row pitch and sample stride: ``act_tiled``'s view of the padded
         chunk is taken as it is) against ``actions`` f32 [B, T, A] -> rows ``row0 .. row0 + n_valid - 1`` of ``out`` f32 [rows, T, 2] =

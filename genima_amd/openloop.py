@@ -27,6 +27,11 @@ here.  What a demo tree does give is, for every transition, t
   error in metres and the cross-view residuals (do the four tiles agree on one arm pose?), for the generated image and for the ground-truth
   render, whose row is the floor of the method.
 
+* optionally, which ORIENTATION the generated spheres show: ``orientation=K`` re-draws every true sphere at K candidate rotations about its own
+  z axis and sums the squared error of each against the generated window -- ``gn_openloop_orientation`` -- so ``orientation_summary()`` can say
+  at which angle the generated stripes fit best and how sharply.  The stripe texture is the only place the image carries a joint's rotation;
+  every other sphere score is blind to it.
+
 ``OpenLoopEval(agent, None, ...)`` is the diffusion-only mode (no controller exists while the ControlNet is being fine-tuned):
 ``diffusion_validator`` makes a ``train_loop.TrainLoop`` ``validate`` callable of it.
 
@@ -61,6 +66,64 @@ EXEC_COLUMNS = ("joint_l1", "gripper", "jump", "demo_jump")  # gn_openloop_exec_
 POINT_COLUMNS = ("n_views", "x", "y", "z", "err_m", "ray_rms_m", "reproj_rms_px", "det")  # gn_openloop_triangulate's eight values per (transition, group, kind)
 POINT_KINDS = ("generated", "ground_truth")
 MAX_GROUPS = 8  # gn_openloop_triangulate's bound on G
+
+
+ORIENTATION_COLUMNS = ("se_gen", "n_gen", "se_gt", "n_gt")  # gn_openloop_orientation's four values per (transition, camera, sphere, candidate)
+MAX_CANDIDATES = 64  # gn_openloop_orientation's bound on K
+SHIFT_FOUND_MASS = 0.5  # OpenLoopEval(orientation=): a sphere below this mass ratio is compared unshifted (summary()'s default found_mass)
+
+
+def orientation_candidates(K: int = 37, span_deg: float = 180.0, axis=(0, 0, 1)):
+    """``-> (angles_deg f64 [K], rot f32 [K, 9])``: the candidate rotations of ``gn_openloop_orientation``.  The angles are evenly spaced over
+    ``[-span_deg / 2, span_deg / 2]``; K is odd, so 0 is on the grid.  Row k is the Rodrigues rotation by ``angles_deg[k]`` about ``axis``
+    (normalised here) in f64, rounded once to f32, row-major; the 0 row is the exact identity.  The default axis is the sphere frame's z: the
+    axis a revolute joint turns about in the simulator's joint frames, and the texture's projection axis."""
+    K, span = int(K), float(span_deg)
+    if not 1 <= K <= MAX_CANDIDATES or K % 2 == 0:
+        raise ValueError(f"orientation_candidates: K = {K} must be odd and lie in [1, {MAX_CANDIDATES}]")
+    if not 0.0 <= span <= 360.0 or (K > 1 and span == 0.0):
+        raise ValueError(f"orientation_candidates: span_deg = {span_deg} must lie in (0, 360]")
+    a = np.asarray(axis, np.float64).reshape(-1)
+    if a.shape != (3,) or not np.isfinite(a).all() or not np.linalg.norm(a) > 0.0:
+        raise ValueError(f"orientation_candidates: axis = {axis!r} must be a non-zero 3-vector")
+    a = a / np.linalg.norm(a)
+    mid = (K - 1) // 2
+    angles = (np.arange(K, dtype=np.float64) - mid) * (span / (K - 1) if K > 1 else 0.0)
+    cross = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    rot = np.empty((K, 3, 3), np.float64)
+    for k, t in enumerate(np.deg2rad(angles)):
+        rot[k] = np.cos(t) * np.eye(3) + np.sin(t) * cross + (1.0 - np.cos(t)) * np.outer(a, a)
+    rot[mid] = np.eye(3)
+    return angles, np.ascontiguousarray(rot.reshape(K, 9).astype(np.float32))
+
+
+def _orientation_option(orientation):
+    """``None | K | dict(K=, span_deg=, axis=)`` -> None or ``orientation_candidates``' keyword arguments."""
+    if orientation is None:
+        return None
+    if isinstance(orientation, dict):
+        extra = set(orientation) - {"K", "span_deg", "axis"}
+        if extra:
+            raise ValueError(f"OpenLoopEval: orientation takes K, span_deg and axis, got {sorted(extra)}")
+        return dict(orientation)
+    if isinstance(orientation, bool) or not isinstance(orientation, (int, np.integer)):
+        raise ValueError(f"OpenLoopEval: orientation is None, the number of candidates K or dict(K=, span_deg=, axis=), got {orientation!r}")
+    return {"K": int(orientation)}
+
+
+def parse_orientation(text: str):
+    """``K[,span]`` -> ``dict(K=, span_deg=)``: ``"37"`` -> 37 candidates over 180 degrees, ``"25,60"`` -> 25 over 60.  The command lines'
+    ``--orientation``."""
+    parts = [p.strip() for p in str(text).split(",")]
+    try:
+        if not 1 <= len(parts) <= 2:
+            raise ValueError
+        out = {"K": int(parts[0])}
+        if len(parts) > 1:
+            out["span_deg"] = float(parts[1])
+    except ValueError:
+        raise ValueError(f"orientation setting {text!r}: K[,span] expected, K an odd integer and span in degrees") from None
+    return out
 
 
 def sphere_groups(spheres, count, windows):
@@ -134,14 +197,24 @@ class OpenLoopResult:
     ``points``: None, or f64 [N, G, 2, 8] (``POINT_COLUMNS``; kind 0 the generated image, kind 1 the ground-truth render): each drawn sphere
     triangulated from the views that found it -- ``gn_openloop_triangulate`` -- with ``point_slots`` int32 [N, G, V] (the slot of each view
     that shows group g, or -1), ``point_centres`` f64 [N, G, 3] (the true centres) and ``cams`` f32 [N, V, 18] (the camera tables), as
-    ``sphere_groups`` and the evaluator made them.  ``summary()`` does not read them; ``triangulation_summary()`` does."""
+    ``sphere_groups`` and the evaluator made them.  ``summary()`` does not read them; ``triangulation_summary()`` does.
+
+    ``orientation``: None, or int64 [N, V, S, K, 4] (``ORIENTATION_COLUMNS``): per sphere and candidate rotation the squared error of the true
+    sphere re-drawn at that rotation against the generated window and against the ground-truth render, each with its pixel count --
+    ``gn_openloop_orientation`` -- with ``orientation_angles`` f64 [K], the candidates' angles in degrees (ascending, 0 among them).
+    ``summary()`` does not read them; ``orientation_summary()`` does."""
 
     def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int,
-                 spheres=None, windows=None, executions=None, chunks=None, points=None, point_slots=None, point_centres=None, cams=None):
+                 spheres=None, windows=None, executions=None, chunks=None, points=None, point_slots=None, point_centres=None, cams=None,
+                 orientation=None, orientation_angles=None):
         if (spheres is None) != (windows is None):
             raise ValueError("OpenLoopResult: spheres and windows come together (the score needs the windows' diagonals)")
         if points is not None and (windows is None or point_slots is None or point_centres is None or cams is None):
             raise ValueError("OpenLoopResult: points come with windows, point_slots, point_centres and cams (the 3D score's penalty needs them)")
+        if orientation is not None and (spheres is None or orientation_angles is None or len(orientation_angles) != orientation.shape[3]):
+            raise ValueError("OpenLoopResult: orientation comes with spheres and one angle per candidate (which spheres are drawn and found)")
+        self.orientation = orientation
+        self.orientation_angles = None if orientation_angles is None else np.asarray(orientation_angles, np.float64)
         self.image, self.actions, self.spheres, self.windows = image, actions, spheres, windows
         self.executions, self.chunks = executions, chunks
         self.points, self.point_slots, self.point_centres, self.cams = points, point_slots, point_centres, cams
@@ -345,12 +418,83 @@ class OpenLoopResult:
             out["per_task"] = {t: self._triangulation_block(self.task == i) for i, t in enumerate(self.tasks)}
         return out
 
+    def orientation_scores(self, found_mass: float = 0.5, min_pixels: int = 50) -> Dict[str, np.ndarray]:
+        """Per sphere, [N, V, S], in numpy f64.  ``readable`` (bool): the ground-truth cost curve ``se_gt / n_gt`` over the candidates is not
+        flat (max > min); a flat curve means the sphere's own texture is not visible in its window (it is hidden behind a neighbour), so no
+        rotation of it changes a pixel.  ``scored`` (bool): drawn, found (mass ratio >= ``found_mass``), readable and at least ``min_pixels``
+        pixels in ``n_gen``.  Over the generated curve ``se_gen / n_gen`` of a scored sphere, NaN elsewhere: ``err_deg`` = |the angle at the
+        first argmin|, ``contrast`` = 1 - min / mean (0: the orientation is not in the image), ``at_edge`` (1.0 where the argmin is the first
+        or the last candidate).  ``floor_deg``: ``err_deg`` of the ground-truth curve for every drawn, readable sphere, NaN elsewhere -- 0 by
+        construction, since the identity candidate reproduces the ground truth."""
+        O = self.orientation.astype(np.float64)
+        ang, K = self.orientation_angles, self.orientation.shape[3]
+        nan = np.full(O.shape[:4], np.nan)
+        cg = np.divide(O[..., 0], O[..., 1], out=nan.copy(), where=O[..., 1] > 0)
+        ct = np.divide(O[..., 2], O[..., 3], out=nan.copy(), where=O[..., 3] > 0)
+        drawn = self.sphere_drawn()
+        readable = (O[..., 3] > 0).all(axis=-1) & (self.orientation[..., 2].max(axis=-1) > self.orientation[..., 2].min(axis=-1))
+        with np.errstate(invalid="ignore"):
+            found = self.sphere_mass_ratio() >= found_mass
+        scored = drawn & found & readable & (self.orientation[..., 0, 1] >= max(1, int(min_pixels)))
+        cg, ct = np.where(scored[..., None], cg, 0.0), np.where((drawn & readable)[..., None], ct, 0.0)  # no NaN reaches an argmin
+        ig, it = np.argmin(cg, axis=-1), np.argmin(ct, axis=-1)
+        cmin, cmean = cg.min(axis=-1), cg.mean(axis=-1)
+        contrast = 1.0 - np.divide(cmin, cmean, out=np.ones(cmin.shape), where=cmean > 0)
+        return {"readable": readable, "scored": scored, "found": found, "err_deg": np.where(scored, np.abs(ang[ig]), np.nan),
+                "contrast": np.where(scored, contrast, np.nan), "at_edge": np.where(scored, ((ig == 0) | (ig == K - 1)).astype(np.float64), np.nan),
+                "floor_deg": np.where(drawn & readable, np.abs(ang[it]), np.nan)}
+
+    def _orientation_block(self, sc: Dict[str, np.ndarray], rows: np.ndarray) -> Dict:
+        ang = self.orientation_angles
+        step = float(ang[1] - ang[0]) if len(ang) > 1 else 0.0
+        half = 0.5 * float(ang[-1] - ang[0])
+        drawn = self.sphere_drawn() & rows[:, None, None]
+
+        def block(sel):  # sel: bool over [N, V, S], the drawn spheres of one camera or of all
+            s = sel & sc["scored"]
+            err = sc["err_deg"][s]
+            floor = sc["floor_deg"][sel & sc["readable"]]
+            return {"n_scored": int(s.sum()), "n_unreadable": int((sel & ~sc["readable"]).sum()), "err_deg": _mean(err),
+                    "err_median_deg": float(np.median(err)) if err.size else None,
+                    "within_step": float((err <= step * (1.0 + 1e-12)).mean()) if err.size else None, "contrast": _mean(sc["contrast"][s]),
+                    "at_edge": _mean(sc["at_edge"][s]), "floor_deg": float(floor.max()) if floor.size else None}
+
+        per = {c: block(drawn & (np.arange(len(self.cameras)) == v)[None, :, None]) for v, c in enumerate(self.cameras)}
+        out: Dict = {k: {c: per[c][k] for c in self.cameras} for k in ("n_scored", "n_unreadable", "err_deg", "err_median_deg", "within_step", "contrast",
+                                                                           "at_edge", "floor_deg")}
+        out["overall"] = block(drawn)
+        counted = drawn & sc["readable"] & (sc["scored"] | ~sc["found"])
+        out["score_deg"] = float(np.where(sc["scored"], sc["err_deg"], half)[counted].mean()) if counted.any() else None
+        return out
+
+    def orientation_summary(self, found_mass: float = 0.5, min_pixels: int = 50) -> Optional[Dict]:
+        """None without ``orientation``; else, in numpy f64 over ``orientation_scores(found_mass, min_pixels)``: per camera and under
+        ``overall`` ``n_scored``, ``n_unreadable`` (drawn spheres with a flat ground-truth curve), the mean and median ``err_deg`` /
+        ``err_median_deg``, ``within_step`` (the share of scored spheres within one grid step of 0), the mean ``contrast``, the ``at_edge``
+        share (the best candidate is an end of the searched range: the true minimum may lie outside it) and ``floor_deg``, the largest error
+        of the ground-truth curve over the drawn readable spheres: it is 0, or the read-out is broken.  ``score_deg``, lower is better: the
+        mean of ``err_deg`` over the drawn, readable spheres, a sphere that was not found counting as half the searched span (a found
+        sphere with fewer than ``min_pixels`` pixels is left out).  ``angles_deg``: the candidates.  ``per_task``: the same per task when
+        there is more than one.  It says whether the IMAGE carries the orientation; it does not measure whether the controller reads the
+        stripes, a stripe pattern that repeats under a half turn cannot be told from its twin, and like every score here it is teacher-forced
+        and not a success rate."""
+        if self.orientation is None:
+            return None
+        sc = self.orientation_scores(found_mass, min_pixels)
+        out = self._orientation_block(sc, np.ones(len(self), bool))
+        out["angles_deg"] = self.orientation_angles.tolist()
+        if len(self.tasks) > 1:
+            out["per_task"] = {t: self._orientation_block(sc, self.task == i) for i, t in enumerate(self.tasks)}
+        return out
+
     def to_json(self, path: str) -> Dict:
         s = self.summary()
         if self.executions is not None:
             s = dict(s, executions=self.execution_summary())  # a key of its own: summary() itself is as it was
         if self.points is not None:
             s = dict(s, spheres_3d=self.triangulation_summary())
+        if self.orientation is not None:
+            s = dict(s, orientation=self.orientation_summary())
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as f:
             json.dump(s, f, indent=1)
@@ -397,6 +541,13 @@ class OpenLoopEval:
     least this share of the ground truth's; ``tri_min_det``: rays that cross worse than this are left unsolved.  It needs a diffusion agent;
     with False nothing changes: the same launches, the same tables, the same bits.
 
+    ``orientation``: None, the number of candidates K, or ``dict(K=, span_deg=, axis=)`` (``orientation_candidates``' arguments): also read the
+    orientation the generated spheres show.  Per batch, after the sphere metrics, the shift of every sphere is computed on the device from
+    that batch's rows of the sphere table -- the difference of the generated and the true centroid (columns 1..3 and 5..7) in f64, rounded to
+    the nearest integer pixel; 0 where either mass is 0 or the mass ratio is below ``SHIFT_FOUND_MASS`` -- and ``gn_openloop_orientation``
+    fills the batch's rows of an int64 [N, V, S, K, 4] table, which rides in the same device-to-host copy (``OpenLoopResult.orientation``,
+    ``orientation_summary()``).  It needs a diffusion agent; with None nothing changes: the same launches, the same tables, the same bits.
+
     Per batch, on the device: ``DeviceReplay.sample`` (the frames, proprioception, normalised action chunk, task tokens) -> ``gn_render_spheres``
     over the frames (``full``, ``occupied``) -> the four views on the 2x2 canvas -> the pipeline (``harness.make_prompt`` ids, one generator
     seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image, sphere and action scores -> the controller again on ``full`` -> its action
@@ -406,7 +557,7 @@ class OpenLoopEval:
     def __init__(self, diffusion_agent, controller, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None,
                  batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
                  change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None, triangulate: bool = False,
-                 tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6):
+                 tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6, orientation=None):
         from .render import load_atlas, load_traj, sphere_windows
 
         if controller is None:
@@ -449,6 +600,12 @@ class OpenLoopEval:
                 raise ValueError("OpenLoopEval: triangulate places the generated spheres; without a diffusion agent nothing is generated")
             if not self.tri_min_ratio >= 0.0 or not self.tri_min_det > 0.0:
                 raise ValueError(f"OpenLoopEval: tri_min_ratio = {tri_min_ratio} must be >= 0 and tri_min_det = {tri_min_det} > 0")
+        self.orientation_angles = self.orientation_rot = None
+        orient = _orientation_option(orientation)
+        if orient is not None:
+            if diffusion_agent is None:
+                raise ValueError("OpenLoopEval: orientation reads the generated spheres; without a diffusion agent nothing is generated")
+            self.orientation_angles, self.orientation_rot = orientation_candidates(**orient)  # uploaded below, once the device is known
         self.change_threshold = int(change_threshold)
         self.agent, self.controller, self.cameras, self.V = diffusion_agent, controller, tuple(cameras), len(cameras)
         if diffusion_agent is not None and self.V != 4:
@@ -496,6 +653,8 @@ class OpenLoopEval:
                 self.point_slots_host, self.point_centres_host = sphere_groups(tab["spheres"], tab["count"], self.windows_host)
                 self.point_slots, self.point_centres = (torch.from_numpy(a).to(dev) for a in (self.point_slots_host, self.point_centres_host))
                 self.cams_host = np.ascontiguousarray(tab["cams"])
+        if self.orientation_rot is not None:
+            self.orientation_rot = torch.from_numpy(self.orientation_rot).to(dev)
         self.samples = int(render_cfg.samples)
         self.step_index, self.episode_index = step, ep_of.copy()
         names = [_task_of(ep, d) for ep, d in zip(episodes, rp.descriptions)]
@@ -529,7 +688,7 @@ class OpenLoopEval:
         full = torch.empty((B * V, H, W, 3), dtype=torch.uint8, device=E.device)
         occupied = torch.empty((B * V, H, W), dtype=torch.uint8, device=E.device)
         E.render_spheres(v["cams"], v["spheres"], v["tex_index"], v["count"], self.atlas, H, W, self.samples, bg=frames, full=full, occupied=occupied)
-        batch["full"], batch["occupied"] = full, occupied
+        batch["full"], batch["occupied"], batch["views"] = full, occupied, v
         if self.windows is not None:
             batch["windows"] = self.windows.index_select(0, sel).reshape(B * V, -1, 4).contiguous()
         if V == 4:  # view v -> the tile at row v / 2, column v % 2 (tiling.CROP_ORDER): layout only
@@ -574,6 +733,8 @@ class OpenLoopEval:
                 tabs["generated"] = act()
             tabs["image"] = torch.zeros((N, self.V, 5), dtype=torch.int64, device=dev)
             tabs["spheres"] = torch.zeros((N, self.V, int(self.windows.shape[2]), 17), dtype=torch.int64, device=dev)
+            if self.orientation_rot is not None:
+                tabs["orientation"] = torch.zeros((N, self.V, int(self.windows.shape[2]), int(self.orientation_rot.shape[0]), 4), dtype=torch.int64, device=dev)
         if self.executions is not None:  # every scored chunk, as the controller's head wrote it
             tabs["chunks"] = {k: torch.zeros((N, T, self.A), dtype=torch.float16, device=dev) for k in ("generated", "oracle") if k in tabs}
         return tabs
@@ -607,6 +768,22 @@ class OpenLoopEval:
         return self.E.openloop_triangulate(tabs["spheres"], self.windows, self.views["cams"], self.point_slots, self.point_centres,
                                            min_ratio=self.tri_min_ratio, min_det=self.tri_min_det, slot_host=self.point_slots_host, win_host=self.windows_host)
 
+    def sphere_shifts(self, sph_rows: torch.Tensor, B: int) -> torch.Tensor:
+        """``sph_rows`` int64 [n, V, S, 17], a batch's finished rows of the sphere table -> int32 [B * V, S, 2] = (dx, dy), where
+        ``gn_openloop_orientation`` reads the generated image relative to each window: ``rint`` of the generated minus the true centroid in
+        f64; 0 where either mass is 0, where the mass ratio is below ``SHIFT_FOUND_MASS`` and in the rows past ``n`` (the padding of a last
+        batch).  Device tensors; nothing is read back."""
+        t = sph_rows.to(torch.float64)
+        gm, tm = t[..., 1], t[..., 5]
+        ok = (gm > 0) & (tm > 0) & (gm >= SHIFT_FOUND_MASS * tm)
+        one = torch.ones_like(gm)
+        gm, tm = torch.where(ok, gm, one), torch.where(ok, tm, one)
+        d = torch.stack([t[..., 2] / gm - t[..., 6] / tm, t[..., 3] / gm - t[..., 7] / tm], dim=-1)
+        d = torch.where(ok[..., None], torch.round(d), torch.zeros_like(d)).clamp_(-127.0, 127.0).to(torch.int32)  # torch.round: half to even, rint
+        out = torch.zeros((B,) + tuple(d.shape[1:]), dtype=torch.int32, device=d.device)
+        out[: d.shape[0]] = d
+        return out.view(B * d.shape[1], d.shape[2], 2)
+
     def run_batch(self, start: int, tabs, generator) -> None:
         """One evaluator batch: steps 1 - 7 for transitions ``start ..``, everything on the device, nothing read back."""
         if self.controller is not None:
@@ -623,6 +800,11 @@ class OpenLoopEval:
                 self.E.openloop_image_metrics(gen, batch["full"], batch["occupied"], tabs["image"], row0=start, n_valid=n_valid)
                 self.E.openloop_sphere_metrics(gen, batch["full"], batch["images_u8"].view(B * self.V, self.H, self.W, 3), batch["occupied"],
                                                batch["windows"], tabs["spheres"], threshold=self.change_threshold, row0=start, n_valid=n_valid)
+                if "orientation" in tabs:
+                    v = batch["views"]
+                    self.E.openloop_orientation(gen, batch["full"], batch["occupied"], batch["windows"], v["cams"], v["spheres"], v["tex_index"], v["count"],
+                                                self.atlas, self.orientation_rot, tabs["orientation"], samples=self.samples,
+                                                shift=self.sphere_shifts(tabs["spheres"][start: start + n_valid], B), row0=start, n_valid=n_valid)
                 if self.controller is not None:
                     self._score_actions(a_hat, batch, tabs["generated"], start, n_valid)  # before the oracle pass overwrites the program's chunk
                     self._keep_chunk(a_hat, tabs, "generated", start, n_valid)
@@ -641,6 +823,8 @@ class OpenLoopEval:
         points = self.triangulate_spheres(tabs)
         if points is not None:  # f64, straight after the int64 tables: the 8-byte tables stay together, ahead of everything narrower that follows
             flat.append(points)
+        if "orientation" in tabs:  # int64: another 8-byte table, ahead of everything narrower
+            flat.append(tabs["orientation"])
         n_before = len(flat)
         execs = self.replay_executions(tabs)
         if execs is not None:  # appended: 4-byte tables first, the f16 chunk tables last (every table then starts on its own type's grid)
@@ -672,10 +856,12 @@ class OpenLoopEval:
                 actions[name] = {"norm": out[k], "rad": out[k + 1]}
                 k += 2
         image, spheres = (out[k], out[k + 1]) if "image" in tabs else (None, None)
+        orient = out[k + 2 + (points is not None)] if "orientation" in tabs else None
         return OpenLoopResult(image, actions, self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1, self.H, self.W,
                               spheres=spheres, windows=self.windows_host if spheres is not None else None, executions=executions, chunks=chunks,
                               points=out[k + 2] if points is not None else None, point_slots=self.point_slots_host,
-                              point_centres=self.point_centres_host, cams=self.cams_host)
+                              point_centres=self.point_centres_host, cams=self.cams_host, orientation=orient,
+                              orientation_angles=self.orientation_angles if orient is not None else None)
 
 
 def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None,
@@ -716,7 +902,7 @@ VALIDATION_JSONL = "validation.jsonl"
 
 def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, out_dir=None, tokenizer=None, batch_size: int = 8,
                         num_inference_steps: int = 5, seed: int = 0, engine=None, triangulate: bool = False, tri_min_ratio: float = 0.5,
-                        tri_min_det: float = 1e-6):
+                        tri_min_det: float = 1e-6, orientation=None):
     """-> a ``validate(global_step)`` callable for ``train_loop.TrainLoop``: each call wraps ``make_pipe()`` (for instance
     ``validation.validation_pipeline(..., trainer, "euler_discrete")`` over the trainer's current weights) as the agent of a diffusion-only
     ``OpenLoopEval`` on held-out demos and returns ``{"step", "select", "found_rate", "shift_px", "mass_ratio", "spread_ratio", "colour_l1",
@@ -727,13 +913,18 @@ def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CA
 
     ``triangulate``: the evaluator's option; the dict then gains ``err_3d_mm`` (the mean 3D error of the generated spheres,
     ``triangulation_summary()["generated"]["err_mm"]``) and ``excess_mm`` (what of it is the model's own); ``tri_min_ratio`` and
-    ``tri_min_det`` are the evaluator's and are read only with it.  ``select`` stays what it is."""
+    ``tri_min_det`` are the evaluator's and are read only with it.  ``select`` stays what it is.
+
+    ``orientation``: the evaluator's option (None, K or a dict); the dict then gains ``orient_err_deg``, the mean orientation error of the
+    scored spheres (``orientation_summary()["overall"]["err_deg"]``; None where none was scored)."""
     import types
 
     state: Dict = {}
     # the three options reach the evaluator only when triangulate is on: with it off OpenLoopEval is called with exactly the arguments it was
     # called with before the option existed (tests/test_sphere_metrics_cpu.py compares them), so the default path cannot have changed
     tri = dict(triangulate=True, tri_min_ratio=tri_min_ratio, tri_min_det=tri_min_det) if triangulate else {}
+    if orientation is not None:  # likewise: only when it is on
+        tri["orientation"] = orientation
 
     def validate(global_step: int) -> Dict:
         agent = types.SimpleNamespace(pipe=make_pipe())
@@ -751,6 +942,8 @@ def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CA
         if triangulate:
             s3 = res.triangulation_summary()
             line.update(err_3d_mm=s3["generated"]["err_mm"], excess_mm=s3["excess_mm"])
+        if orientation is not None:
+            line.update(orient_err_deg=res.orientation_summary()["overall"]["err_deg"])
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, VALIDATION_JSONL), "a") as f:

@@ -910,6 +910,38 @@ int32_t gn_openloop_sphere_metrics(gn_ctx* ctx, const uint8_t* gen, const uint8_
                                    const int32_t* win_host, uint64_t* sph_out, int32_t B, int32_t V, int32_t H, int32_t W, int32_t S, int32_t tiled,
                                    int32_t threshold, int32_t row0, int32_t n_valid, int32_t rows);
 
+/* gn_openloop_orientation: which orientation the generated spheres show.  The stripe texture is the only place the image carries a joint's
+ * rotation (the hit point goes through the sphere's own frame, m = Rs^T Rc, into the texture), so per (sample b < n_valid, view v, sphere
+ * slot s < S, candidate k < K) the TRUE sphere is re-drawn with its rotation turned by R_k and compared with the generated window (row0,
+ * n_valid, rows as above: sample b writes the S * K * 4 values of each of its views into row row0 + b).
+ *   gen, gt, occupied, win, win_host, tiled   as gn_openloop_sphere_metrics takes them: the same window clamp, the same optional host check
+ *   cams      f32 [B * V][18], spheres f32 [B * V][S][16], tex_index int32 [B * V][S], count int32 [B * V], atlas uint8 [T][th][tw][4]
+ *             (4-byte aligned), samples in {1, 4}: gn_render_spheres' per-view inputs; count and tex_index are clamped as the renderer
+ *             clamps them (count into [0, S], tex_index into [0, T - 1])
+ *   rot       f32 [K][9], DEVICE memory, 4-byte aligned, 1 <= K <= 64: K rotations R_k in the sphere's OWN frame, row-major.  Candidate k of
+ *             sphere s is the view's sphere table with only sphere s's rotation Rs (pose elements [i * 4 + l], i, l < 3) replaced by
+ *               Rs_k[i][l] = (float)((double)Rs[i][0] * R_k[0][l] + (double)Rs[i][1] * R_k[1][l] + (double)Rs[i][2] * R_k[2][l]),
+ *             the sum added left to right without fused multiply-add.  Every other sphere, the centre, the radius, the factor and the
+ *             texture stay, so occlusion is the real one, and an identity R_k reproduces the ground-truth pose.  A slot s >= count is not
+ *             drawn: all its candidates are the unchanged view
+ *   shift     int32 [B * V][S][2] = (dx, dy), DEVICE memory, 4-byte aligned, or NULL (= 0): gen is read at (x + dx, y + dy), so a generated
+ *             sphere that sits a few pixels off is compared texture against texture.  The kernel clamps each component into [-127, 127]; a
+ *             shifted position outside the view's own H x W (its own tile, when tiled) drops that pixel from the gen sums only
+ *   ori_out   uint64 [rows][V][S][K][4], 8-byte aligned.  Over the window's pixels with occupied != 0 (a silhouette does not depend on the
+ *             rotation, so every candidate sums over the same set), with c the candidate's rendered colour at the pixel -- gn_render_spheres'
+ *             raw render before any composite, bit for bit (the two kernels share the drawing code and the compile flags):
+ *     [0]     sum over the 3 channels of (c - gen)^2 over the pixels whose shifted position is inside;  [1] the number of those pixels
+ *     [2]     sum over the 3 channels of (c - gt)^2;  [3] the number of pixels in [2]
+ *   One workgroup owns one (window, candidate) and stores its four values itself (no atomics, no zeroing pass: an empty window stores four
+ *   zeros), so every run gives the same bits.  A column stays below 65 536 * 195 075 = 1.3e10.  Refused, launching nothing and leaving
+ *   ori_out as it was: a NULL pointer other than win_host / shift, the bounds gn_openloop_sphere_metrics puts on B, V, H, W, S, tiled, row0,
+ *   n_valid and rows, B * V > 65535, K outside [1, 64], samples not 1 or 4, T, th or tw <= 0, a misaligned pointer, and a window that fails
+ *   win_host's check.  n_valid == 0 is accepted and does nothing.  Eager only. */
+int32_t gn_openloop_orientation(gn_ctx* ctx, const uint8_t* gen, const uint8_t* gt, const uint8_t* occupied, const int32_t* win, const int32_t* win_host,
+                                const float* cams, const float* spheres, const int32_t* tex_index, const int32_t* count, const uint8_t* atlas,
+                                const float* rot, const int32_t* shift, uint64_t* ori_out, int32_t B, int32_t V, int32_t H, int32_t W, int32_t S, int32_t K,
+                                int32_t T, int32_t th, int32_t tw, int32_t samples, int32_t tiled, int32_t row0, int32_t n_valid, int32_t rows);
+
 /* Open-loop scores of an execution mode (execution_horizon h, temporal_agg, m): what gn_action_ensemble would have executed at every step of
  * every held-out episode, replayed from the chunks an evaluation computes anyway.  Observations are teacher-forced, so a rollout with horizon h
  * uses exactly the chunks of the transitions at steps 0, h, 2h, ... of each episode.

@@ -21,9 +21,13 @@ With ``--triangulate`` it times whole runs of two evaluators that alternate in t
 -- and the ``gn_openloop_triangulate`` launch over the run's whole table by device events.  The expectation checked there: one small launch
 and N * G * 128 more bytes in the final copy do not show next to the diffusion calls.
 
+With ``--orientation`` it times whole runs of two evaluators that alternate in the same way -- one without and one with ``orientation=37``
+-- and reports both per transition, the difference as a share of the run without it, and the ``gn_openloop_orientation`` launch over one
+batch at K = 37 by device events (the shifts are those of the batch's own sphere table).
+
 Prints one JSON line; needs an MI355X.
 
-    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid] [--triangulate]
+    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid] [--triangulate] [--orientation]
         [--sphere_textures tests/golden/sphere_textures] [--out profiles/openloop_b8.json]
 """
 import argparse
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--sphere_textures", default=os.path.join(HERE, "tests", "golden", "sphere_textures"))
     ap.add_argument("--exec_grid", action="store_true", help="also time whole runs without and with the 8-setting execution grid, and the two replay launches")
     ap.add_argument("--triangulate", action="store_true", help="also time whole runs without and with triangulate=True, and the triangulation launch")
+    ap.add_argument("--orientation", action="store_true", help="also time whole runs without and with orientation=37, and the orientation launch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -189,6 +194,34 @@ def main():
         t_out = ev_tri.triangulate_spheres(tt)
         launches["triangulate_us"] = lambda: E.openloop_triangulate(tt["spheres"], ev_tri.windows, ev_tri.views["cams"], ev_tri.point_slots, ev_tri.point_centres,
                                                                     t_out, min_ratio=ev_tri.tri_min_ratio, min_det=ev_tri.tri_min_det)
+    if args.orientation:
+        ev_ori = OpenLoopEval(dagent, controller, eps, cams, render_cfg=rcfg, stats=(P.action_stats(demos), P.proprio_stats(demos)), tokenizer=tokens,
+                              batch_size=B, engine=E, orientation=37)
+        runs = {"run_without_orientation": ev.run, "run_with_orientation": ev_ori.run}
+        rms = {k: [] for k in runs}
+        for i in range(args.warmup + args.reps):
+            for k, fn in runs.items():
+                E.synchronize()
+                t = time.perf_counter()
+                fn()  # ends in its device-to-host copy
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    rms[k].append((time.perf_counter() - t) * 1e3)
+        for k in runs:
+            res[k] = stats(rms[k])
+            res[k + "_ms_per_transition"] = round(res[k]["median_ms"] / ev.N, 4)
+        res["orientation_minus_plain_ms"] = round(res["run_with_orientation"]["median_ms"] - res["run_without_orientation"]["median_ms"], 4)
+        res["orientation_share_of_run"] = round(res["orientation_minus_plain_ms"] / res["run_without_orientation"]["median_ms"], 5)
+        res["run_without_orientation_spread_ms"] = round(res["run_without_orientation"]["max_ms"] - res["run_without_orientation"]["min_ms"], 4)
+        res["orientation_candidates"] = int(ev_ori.orientation_rot.shape[0])
+        res["orientation_extra_copy_bytes"] = int(ev_ori.N * ev_ori.V * ev_ori.windows.shape[2] * ev_ori.orientation_rot.shape[0] * 32)
+        ot = ev_ori._tables()
+        ev_ori.run_batch(0, ot, gen)  # fills the batch's rows of the sphere table: the shifts below are a real batch's
+        o_shift = ev_ori.sphere_shifts(ot["spheres"][:B], B)
+        launches["orientation_us"] = lambda: E.openloop_orientation(out_img, batch["full"], batch["occupied"], batch["windows"], v["cams"], v["spheres"],
+                                                                    v["tex_index"], v["count"], ev.atlas, ev_ori.orientation_rot, ot["orientation"],
+                                                                    samples=ev.samples, shift=o_shift)
+        launches["sphere_shifts_us"] = lambda: ev_ori.sphere_shifts(ot["spheres"][:B], B)
     for name, launch in launches.items():
         us = []
         for _ in range(5):

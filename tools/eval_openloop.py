@@ -18,6 +18,10 @@ diffusion checkpoint alone (no ``--controller_snapshot`` / ``--stats_dir`` neede
 ``--triangulate`` also triangulates every drawn sphere across the four views (``gn_openloop_triangulate``) and adds, under ``spheres_3d``,
 the 3D error in millimetres and the cross-view residuals of the generated image beside those of the ground-truth render, the floor of the
 method (``OpenLoopResult.triangulation_summary``; ``--tri_min_ratio`` / ``--tri_min_det`` set which views and which crossings count).
+``--orientation K[,span]`` (``37``, ``25,60``) also reads the orientation the generated spheres show: every true sphere is re-drawn at K
+rotations about its own z axis over ``span`` degrees (default 180) and compared with the generated window (``gn_openloop_orientation``); under
+``orientation`` the summary then carries the angular error, its contrast and ``floor_deg``, the same read-out of the ground-truth render,
+which is 0 (``OpenLoopResult.orientation_summary``).
 Open-loop error is not a success rate: every chunk is predicted from a demo state, nothing is executed and no error compounds."""
 import argparse
 import json
@@ -57,6 +61,8 @@ def parse(argv=None):
     ap.add_argument("--triangulate", action="store_true", help="also triangulate the drawn spheres across the views: the 3D error in mm and the cross-view residuals")
     ap.add_argument("--tri_min_ratio", type=float, default=0.5, help="a view counts for the generated image when its mass is at least this share of the ground truth's")
     ap.add_argument("--tri_min_det", type=float, default=1e-6, help="rays that cross worse than this (det(A) / (trace(A) / 3)^3) are left unsolved")
+    ap.add_argument("--orientation", default=None, metavar="K[,span]",
+                    help="also read the orientation the generated spheres show: K (odd, at most 64) candidate rotations over span degrees (default 180)")
     ap.add_argument("--out", default="openloop.json")
     a = ap.parse_args(argv)
     if not a.no_controller and not (a.controller_snapshot and a.stats_dir):
@@ -68,6 +74,14 @@ def parse(argv=None):
             ap.error("--execution replays the controller's chunks: it cannot be combined with --no_controller")
         try:
             a.execution = [parse_execution(e) for e in a.execution]
+        except ValueError as err:
+            ap.error(str(err))
+    if a.orientation is not None:
+        from genima_amd.openloop import orientation_candidates, parse_orientation
+
+        try:
+            a.orientation = parse_orientation(a.orientation)
+            orientation_candidates(**a.orientation)
         except ValueError as err:
             ap.error(str(err))
     return a
@@ -110,7 +124,7 @@ def main(argv=None):
     ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=stats, tokenizer=tokenizer, batch_size=a.batch_size,
                       num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed, change_threshold=a.change_threshold,
                       action_sequence=a.action_sequence, executions=a.execution, triangulate=a.triangulate, tri_min_ratio=a.tri_min_ratio,
-                      tri_min_det=a.tri_min_det)
+                      tri_min_det=a.tri_min_det, orientation=a.orientation)
     print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
     summary = ev.run().to_json(a.out)
     print(json.dumps(summary, indent=1))
