@@ -37,6 +37,76 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+# ---- the checks the eager data and scoring ops share (gather_u8_to_f16 .. render_spheres)
+_ROWS_CHANGE = "the result rows change from batch to batch"
+_SCORES_TABLES = "it scores tables that a run has filled"
+
+
+def _eager_only(engine, who: str, why: str) -> None:
+    if engine.record:
+        raise RuntimeError(f"{who} is an eager op: {why}")
+
+
+def _expect(who: str, t, dtype, shape, optional: bool = False) -> None:
+    """An eager op's tensor argument: on the device, of ``dtype``, contiguous and of ``shape``; None only where it is ``optional``."""
+    if t is None and optional:
+        return
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise GenimaHipError(f"{who}: a contiguous device tensor {dtype} {shape} expected")
+
+
+def _expect_each(who: str, specs, optional: bool = False) -> None:
+    for t, dtype, shape in specs:
+        _expect(who, t, dtype, shape, optional)
+
+
+def _host_int32(who: str, h, shape):
+    """The optional int32 numpy copy of a device table -> its address for the library's own checks, or None."""
+    if h is None:
+        return None
+    if not (str(h.dtype) == "int32" and h.flags.c_contiguous and h.shape == tuple(shape)):
+        raise GenimaHipError(f"{who}: a contiguous int32 host copy {tuple(shape)} expected, got {h.dtype} {h.shape}")
+    return h.ctypes.data
+
+
+def _image_layout(who: str, gen, gt, occupied):
+    """``gen`` uint8, tiled [B, 2H, 2W, 3] (V = 4) or per view [B, V, H, W, 3], ``gt`` uint8 [B * V, H, W, 3] and ``occupied`` uint8
+    [B * V, H, W], checked -> ``(tiled, B, V, H, W)``."""
+    H, W = int(gt.shape[1]), int(gt.shape[2])
+    tiled = gen.dim() == 4
+    B, V = int(gen.shape[0]), 4 if tiled else int(gen.shape[1])
+    _expect_each(who, ((gen, torch.uint8, (B, 2 * H, 2 * W, 3) if tiled else (B, V, H, W, 3)), (gt, torch.uint8, (B * V, H, W, 3)),
+                       (occupied, torch.uint8, (B * V, H, W))))
+    return tiled, B, V, H, W
+
+
+def _replay_index(who: str, idx, N: int, device):
+    """-> the batch's indices as a device int32 [B] tensor: one is used as it is (the kernel clamps it), host integers are checked and uploaded."""
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda):
+        host = torch.as_tensor(idx).reshape(-1).to(torch.int64)
+        if host.numel() == 0 or bool((host < 0).any()) or bool((host >= N).any()):
+            raise GenimaHipError(f"{who}: transition indices must lie in [0, {N}), got {host.tolist()}")
+        idx = host.to(torch.int32).to(device, non_blocking=True)
+    _expect(who, idx, torch.int32, (idx.numel(),))
+    return idx
+
+
+def _replay_outputs(who: str, out, device, B: int, frames: int, H: int, W: int, fs: int, S: int, T: int, A: int, N: int, lang_tokens, episode,
+                    want_u8: bool, want_draws: Optional[bool] = None):
+    """A replay batch's outputs (images, images_u8, low_dim_state, action, tokens and, unless ``want_draws`` is None, replay_render's bg_layer
+    and blend), allocated where ``out`` is None and checked either way with the token tables they go with -> ``(out, N_ep, L_tok)``."""
+    N_ep, L_tok = (int(lang_tokens.shape[0]), int(lang_tokens.shape[1])) if lang_tokens is not None else (0, 0)
+    specs = [(F16, (B, frames, H, W, 8), True), (torch.uint8, (B, frames, H, W, 3), want_u8), (torch.float32, (B, fs, S), True),
+             (torch.float32, (B, T, A), True), (torch.int32, (B, L_tok), lang_tokens is not None)]
+    if want_draws is not None:
+        specs += [(torch.int32, (B, frames), want_draws), (torch.float64, (B, frames), want_draws)]
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=device) if want else None for dt, shape, want in specs)
+    _expect_each(who, [(lang_tokens, torch.int32, (N_ep, L_tok)), (episode, torch.int32, (N,))] + [(t, dt, shape) for t, (dt, shape, _) in zip(out, specs)],
+                 optional=True)
+    return out, N_ep, L_tok
+
+
 TUNE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_tune_gfx950.json")
 _tune_cache: Optional[dict] = None
 _tune_dirty = [False]
@@ -1356,9 +1426,8 @@ class Engine:
         """``image_u8_to_f16`` over frames that lie anywhere on the device: ``ptrs`` is a DEVICE int64 [B] tensor of the addresses of uint8
         [H, W, 3] frames (4-byte aligned, repeats allowed) -> f16 [B, H, W, cpad], one launch.  Eager engines only (a recorded program would
         replay the addresses of one batch)."""
-        if self.record:
-            raise RuntimeError("gather_u8_to_f16 is an eager op: the frame addresses change from batch to batch")
-        assert ptrs.is_cuda and ptrs.dtype == torch.int64 and ptrs.dim() == 1 and ptrs.is_contiguous()
+        _eager_only(self, "gather_u8_to_f16", "the frame addresses change from batch to batch")
+        _expect("gather_u8_to_f16", ptrs, torch.int64, (ptrs.numel(),))
         H, W = int(frame_shape[0]), int(frame_shape[1])
         out = torch.empty((ptrs.numel(), H, W, cpad), dtype=F16, device=self.device)
         check(self.lib.gn_gather_u8_to_f16(self._ctx, _ptr(ptrs), _ptr(out), ptrs.numel(), H * W, cpad, float(mul), float(add)), "gn_gather_u8_to_f16")
@@ -1372,30 +1441,16 @@ class Engine:
         [B, V * fs, H, W, 3] or None, low_dim_state f32 [B, fs, S], action f32 [B, T, A], tokens int32 [B, L_tok] or None -- with
         ``lang_tokens`` int32 [N_ep, L_tok] and ``episode`` int32 [N]); ``out``: the same five to write into.  Eager engines
         only (a recorded program would replay the indices of one batch)."""
-        if self.record:
-            raise RuntimeError("replay_gather is an eager op: the batch indices change from call to call")
+        who = "replay_gather"
+        _eager_only(self, who, "the batch indices change from call to call")
         N_obs, S = int(qpos.shape[0]), int(qpos.shape[1])
         N, A = int(action.shape[0]), int(action.shape[1])
         H, W = int(frame_shape[0]), int(frame_shape[1])
-        for t, dt, shape in ((frame_ptr, torch.int64, (N_obs * V,)), (qpos, torch.float32, (N_obs, S)), (action, torch.float32, (N, A)), (obs_index, torch.int32, (N,)),
-                             (first_obs, torch.int32, (N,)), (last_tr, torch.int32, (N,))):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
-        if not (isinstance(idx, torch.Tensor) and idx.is_cuda):
-            host = torch.as_tensor(idx).reshape(-1).to(torch.int64)
-            if host.numel() == 0 or bool((host < 0).any()) or bool((host >= N).any()):
-                raise GenimaHipError(f"replay_gather: transition indices must lie in [0, {N}), got {host.tolist()}")
-            idx = host.to(torch.int32).to(self.device, non_blocking=True)
-        assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+        _expect_each(who, ((frame_ptr, torch.int64, (N_obs * V,)), (qpos, torch.float32, (N_obs, S)), (action, torch.float32, (N, A)),
+                           (obs_index, torch.int32, (N,)), (first_obs, torch.int32, (N,)), (last_tr, torch.int32, (N,))))
+        idx = _replay_index(who, idx, N, self.device)
         B = idx.numel()
-        if out is None:
-            out = (torch.empty((B, V * fs, H, W, 8), dtype=F16, device=self.device),
-                   torch.empty((B, V * fs, H, W, 3), dtype=torch.uint8, device=self.device) if want_u8 else None,
-                   torch.empty((B, fs, S), dtype=torch.float32, device=self.device), torch.empty((B, T, A), dtype=torch.float32, device=self.device),
-                   torch.empty((B, lang_tokens.shape[1]), dtype=torch.int32, device=self.device) if lang_tokens is not None else None)
-        img, img8, low, act, tok = out
-        N_ep, L_tok = (int(lang_tokens.shape[0]), int(lang_tokens.shape[1])) if lang_tokens is not None else (0, 0)
-        for t, dt, shape in ((lang_tokens, torch.int32, (N_ep, L_tok)), (episode, torch.int32, (N,)), (tok, torch.int32, (B, L_tok)), (img, F16, (B, V * fs, H, W, 8)), (img8, torch.uint8, (B, V * fs, H, W, 3)), (low, torch.float32, (B, fs, S)), (act, torch.float32, (B, T, A))):
-            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape), (dt, shape)
+        (img, img8, low, act, tok), N_ep, L_tok = _replay_outputs(who, out, self.device, B, V * fs, H, W, fs, S, T, A, N, lang_tokens, episode, want_u8)
         d = _lib.ReplayGatherDesc(frame_ptr=_ptr(frame_ptr), qpos=_ptr(qpos), action=_ptr(action), obs_index=_ptr(obs_index), first_obs=_ptr(first_obs),
                                   last_tr=_ptr(last_tr), idx=_ptr(idx), images=_ptr(img), images_u8=_ptr(img8), low_dim_state=_ptr(low), action_out=_ptr(act),
                                   lang_tokens=_ptr(lang_tokens), episode=_ptr(episode), tokens_out=_ptr(tok), pixels=H * W, N_obs=N_obs, B=B, V=V, fs=fs, T=T,
@@ -1413,37 +1468,20 @@ class Engine:
         the textures and blends.  -> (images f16 [B, V * fs, H, W, 8], images_u8 or None, low_dim_state, action, tokens or None, bg_layer
         int32 [B, V * fs] or None, blend f64 [B, V * fs] or None -- the last two with ``want_draws``); ``out``: the same seven to write
         into.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("replay_render is an eager op: the batch indices and the draw change from call to call")
+        who = "replay_render"
+        _eager_only(self, who, "the batch indices and the draw change from call to call")
         N_obs, S = int(qpos.shape[0]), int(qpos.shape[1])
         N, A = int(action.shape[0]), int(action.shape[1])
         n_sph = int(spheres.shape[1])
         NB, H, W = int(bank.shape[0]), int(bank.shape[1]), int(bank.shape[2])
-        for t, dt, shape in ((cams, torch.float32, (N_obs * V, 18)), (spheres, torch.float32, (N_obs * V, n_sph, 16)), (tex_index, torch.int32, (N_obs * V, n_sph)),
-                             (count, torch.int32, (N_obs * V,)), (bank, torch.uint8, (NB, H, W, 3)), (qpos, torch.float32, (N_obs, S)), (action, torch.float32, (N, A)),
-                             (obs_index, torch.int32, (N,)), (first_obs, torch.int32, (N,)), (last_tr, torch.int32, (N,))):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
-        assert atlas.is_cuda and atlas.dtype == torch.uint8 and atlas.is_contiguous() and atlas.dim() == 4 and atlas.shape[3] == 4
-        if not (isinstance(idx, torch.Tensor) and idx.is_cuda):
-            host = torch.as_tensor(idx).reshape(-1).to(torch.int64)
-            if host.numel() == 0 or bool((host < 0).any()) or bool((host >= N).any()):
-                raise GenimaHipError(f"replay_render: transition indices must lie in [0, {N}), got {host.tolist()}")
-            idx = host.to(torch.int32).to(self.device, non_blocking=True)
-        assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+        _expect_each(who, ((cams, torch.float32, (N_obs * V, 18)), (spheres, torch.float32, (N_obs * V, n_sph, 16)), (tex_index, torch.int32, (N_obs * V, n_sph)),
+                           (count, torch.int32, (N_obs * V,)), (bank, torch.uint8, (NB, H, W, 3)), (qpos, torch.float32, (N_obs, S)), (action, torch.float32, (N, A)),
+                           (obs_index, torch.int32, (N,)), (first_obs, torch.int32, (N,)), (last_tr, torch.int32, (N,)),
+                           (atlas, torch.uint8, tuple(atlas.shape[:3]) + (4,))))
+        idx = _replay_index(who, idx, N, self.device)
         B = idx.numel()
-        if out is None:
-            out = (torch.empty((B, V * fs, H, W, 8), dtype=F16, device=self.device),
-                   torch.empty((B, V * fs, H, W, 3), dtype=torch.uint8, device=self.device) if want_u8 else None,
-                   torch.empty((B, fs, S), dtype=torch.float32, device=self.device), torch.empty((B, T, A), dtype=torch.float32, device=self.device),
-                   torch.empty((B, lang_tokens.shape[1]), dtype=torch.int32, device=self.device) if lang_tokens is not None else None,
-                   torch.empty((B, V * fs), dtype=torch.int32, device=self.device) if want_draws else None,
-                   torch.empty((B, V * fs), dtype=torch.float64, device=self.device) if want_draws else None)
-        img, img8, low, act, tok, layer, blend = out
-        N_ep, L_tok = (int(lang_tokens.shape[0]), int(lang_tokens.shape[1])) if lang_tokens is not None else (0, 0)
-        for t, dt, shape in ((lang_tokens, torch.int32, (N_ep, L_tok)), (episode, torch.int32, (N,)), (tok, torch.int32, (B, L_tok)), (img, F16, (B, V * fs, H, W, 8)),
-                             (img8, torch.uint8, (B, V * fs, H, W, 3)), (low, torch.float32, (B, fs, S)), (act, torch.float32, (B, T, A)),
-                             (layer, torch.int32, (B, V * fs)), (blend, torch.float64, (B, V * fs))):
-            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape), (dt, shape)
+        (img, img8, low, act, tok, layer, blend), N_ep, L_tok = _replay_outputs(who, out, self.device, B, V * fs, H, W, fs, S, T, A, N, lang_tokens, episode,
+                                                                                  want_u8, bool(want_draws))
         seed = int(seed)
         d = _lib.ReplayRenderDesc(cams=_ptr(cams), spheres=_ptr(spheres), tex_index=_ptr(tex_index), count=_ptr(count), atlas=_ptr(atlas), bank=_ptr(bank),
                                   qpos=_ptr(qpos), action=_ptr(action), obs_index=_ptr(obs_index), first_obs=_ptr(first_obs), last_tr=_ptr(last_tr), idx=_ptr(idx),
@@ -1460,16 +1498,11 @@ class Engine:
         against ``gt`` uint8 [B * V, H, W, 3] under ``occupied`` uint8 [B * V, H, W] (``render_spheres``' ``full`` / ``occupied``) -> rows
         ``row0 .. row0 + n_valid - 1`` of ``out`` int64 [rows, V, 5] = (se_in, n_in, se_out, n_out, wrap_sq), zeroed and summed by the
         call; samples ``b >= n_valid`` (default B) write nothing.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("openloop_image_metrics is an eager op: the result rows change from batch to batch")
-        H, W = int(gt.shape[1]), int(gt.shape[2])
-        tiled = gen.dim() == 4
-        B = int(gen.shape[0])
-        V = 4 if tiled else int(gen.shape[1])
+        who = "openloop_image_metrics"
+        _eager_only(self, who, _ROWS_CHANGE)
+        tiled, B, V, H, W = _image_layout(who, gen, gt, occupied)
         rows = int(out.shape[0])
-        for t, dt, shape in ((gen, torch.uint8, (B, 2 * H, 2 * W, 3) if tiled else (B, V, H, W, 3)), (gt, torch.uint8, (B * V, H, W, 3)),
-                             (occupied, torch.uint8, (B * V, H, W)), (out, torch.int64, (rows, V, 5))):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
+        _expect(who, out, torch.int64, (rows, V, 5))
         check(self.lib.gn_openloop_image_metrics(self._ctx, _ptr(gen), _ptr(gt), _ptr(occupied), _ptr(out), B, V, H, W, int(tiled), int(row0),
                                                  B if n_valid is None else int(n_valid), rows), "gn_openloop_image_metrics")
         return out
@@ -1481,21 +1514,12 @@ class Engine:
         ``row0 .. row0 + n_valid - 1`` of ``out`` int64 [rows, V, S, 17], each window's values stored by its own workgroup; samples
         ``b >= n_valid`` (default B) write nothing.  ``win_host``: an int32 numpy copy of ``win``; with it bad windows are refused, without it
         the kernel clamps them.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("openloop_sphere_metrics is an eager op: the result rows change from batch to batch")
-        H, W = int(gt.shape[1]), int(gt.shape[2])
-        tiled = gen.dim() == 4
-        B = int(gen.shape[0])
-        V = 4 if tiled else int(gen.shape[1])
+        who = "openloop_sphere_metrics"
+        _eager_only(self, who, _ROWS_CHANGE)
+        tiled, B, V, H, W = _image_layout(who, gen, gt, occupied)
         S, rows = int(win.shape[1]), int(out.shape[0])
-        for t, dt, shape in ((gen, torch.uint8, (B, 2 * H, 2 * W, 3) if tiled else (B, V, H, W, 3)), (gt, torch.uint8, (B * V, H, W, 3)),
-                             (cond, torch.uint8, (B * V, H, W, 3)), (occupied, torch.uint8, (B * V, H, W)), (win, torch.int32, (B * V, S, 4)),
-                             (out, torch.int64, (rows, V, S, 17))):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, (dt, shape)
-        hp = None
-        if win_host is not None:
-            assert str(win_host.dtype) == "int32" and win_host.flags.c_contiguous and win_host.shape == (B * V, S, 4), win_host.shape
-            hp = win_host.ctypes.data
+        _expect_each(who, ((cond, torch.uint8, (B * V, H, W, 3)), (win, torch.int32, (B * V, S, 4)), (out, torch.int64, (rows, V, S, 17))))
+        hp = _host_int32(who, win_host, (B * V, S, 4))
         check(self.lib.gn_openloop_sphere_metrics(self._ctx, _ptr(gen), _ptr(gt), _ptr(cond), _ptr(occupied), _ptr(win), hp, _ptr(out), B, V, H, W, S,
                                                   int(tiled), int(threshold), int(row0), B if n_valid is None else int(n_valid), rows),
               "gn_openloop_sphere_metrics")
@@ -1510,29 +1534,17 @@ class Engine:
         relative to the window) -> rows ``row0 .. row0 + n_valid - 1`` of ``out`` int64 [rows, V, S, K, 4] = per candidate the squared error of
         the re-drawn sphere against ``gen`` and its pixel count, the same against ``gt`` and its count; samples ``b >= n_valid`` (default B)
         write nothing.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("openloop_orientation is an eager op: the result rows change from batch to batch")
+        who = "openloop_orientation"
+        _eager_only(self, who, _ROWS_CHANGE)
         if rot.dim() != 2 or win.dim() != 3 or atlas.dim() != 4 or atlas.shape[3] != 4 or out.dim() != 5:
             raise GenimaHipError("openloop_orientation: rot must be f32 [K, 9], win int32 [B * V, S, 4], atlas uint8 [T, th, tw, 4] and out int64 [rows, V, S, K, 4]")
-        H, W = int(gt.shape[1]), int(gt.shape[2])
-        tiled = gen.dim() == 4
-        B = int(gen.shape[0])
-        V = 4 if tiled else int(gen.shape[1])
+        tiled, B, V, H, W = _image_layout(who, gen, gt, occupied)
         S, K, rows = int(win.shape[1]), int(rot.shape[0]), int(out.shape[0])
-        for t, dt, shape in ((gen, torch.uint8, (B, 2 * H, 2 * W, 3) if tiled else (B, V, H, W, 3)), (gt, torch.uint8, (B * V, H, W, 3)),
-                             (occupied, torch.uint8, (B * V, H, W)), (win, torch.int32, (B * V, S, 4)), (cams, torch.float32, (B * V, 18)),
-                             (spheres, torch.float32, (B * V, S, 16)), (tex_index, torch.int32, (B * V, S)), (count, torch.int32, (B * V,)),
-                             (atlas, torch.uint8, tuple(atlas.shape)), (rot, torch.float32, (K, 9)), (shift, torch.int32, (B * V, S, 2)),
-                             (out, torch.int64, (rows, V, S, K, 4))):
-            if t is shift and t is None:
-                continue
-            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
-                raise GenimaHipError(f"openloop_orientation: a contiguous device tensor {dt} {shape} expected")
-        hp = None
-        if win_host is not None:
-            if not (str(win_host.dtype) == "int32" and win_host.flags.c_contiguous and win_host.shape == (B * V, S, 4)):
-                raise GenimaHipError(f"openloop_orientation: a contiguous int32 host copy {(B * V, S, 4)} expected, got {win_host.dtype} {win_host.shape}")
-            hp = win_host.ctypes.data
+        _expect_each(who, ((win, torch.int32, (B * V, S, 4)), (cams, torch.float32, (B * V, 18)), (spheres, torch.float32, (B * V, S, 16)),
+                           (tex_index, torch.int32, (B * V, S)), (count, torch.int32, (B * V,)), (atlas, torch.uint8, tuple(atlas.shape)), (rot, torch.float32, (K, 9)),
+                           (out, torch.int64, (rows, V, S, K, 4))))
+        _expect(who, shift, torch.int32, (B * V, S, 2), optional=True)
+        hp = _host_int32(who, win_host, (B * V, S, 4))
         check(self.lib.gn_openloop_orientation(self._ctx, _ptr(gen), _ptr(gt), _ptr(occupied), _ptr(win), hp, _ptr(cams), _ptr(spheres), _ptr(tex_index),
                                                _ptr(count), _ptr(atlas), _ptr(rot), _ptr(shift), _ptr(out), B, V, H, W, S, K, int(atlas.shape[0]),
                                                int(atlas.shape[1]), int(atlas.shape[2]), int(samples), int(tiled), int(row0),
@@ -1544,14 +1556,14 @@ class Engine:
         chunk is taken as it is) against ``actions`` f32 [B, T, A] -> rows ``row0 .. row0 + n_valid - 1`` of ``out`` f32 [rows, T, 2] =
         (sum_j joint_scale[j] |a_hat[j] - actions[j]| over the A - 1 joints, gripper flag).  ``joint_scale``: f32 [A - 1] or None (= 1).
         Eager engines only."""
-        if self.record:
-            raise RuntimeError("openloop_action_metrics is an eager op: the result rows change from batch to batch")
+        who = "openloop_action_metrics"
+        _eager_only(self, who, _ROWS_CHANGE)
         B, T, A = (int(s) for s in actions.shape)
         rows = int(out.shape[0])
-        assert a_hat.is_cuda and a_hat.dtype == F16 and a_hat.dim() == 3 and a_hat.shape[0] == B and a_hat.shape[1] >= T and a_hat.shape[2] >= A
-        assert a_hat.stride(2) == 1 or a_hat.shape[2] == 1
-        for t, shape in ((actions, (B, T, A)), (joint_scale, (A - 1,)), (out, (rows, T, 2))):
-            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape), shape
+        if not (a_hat.is_cuda and a_hat.dtype == F16 and a_hat.dim() == 3 and a_hat.shape[0] == B and a_hat.shape[1] >= T and a_hat.shape[2] >= A
+                and (a_hat.stride(2) == 1 or a_hat.shape[2] == 1)):
+            raise GenimaHipError(f"{who}: a_hat must be f16 [{B}, >= {T}, >= {A}] on the device with unit column stride")
+        _expect_each(who, ((actions, torch.float32, (B, T, A)), (joint_scale, torch.float32, (A - 1,)), (out, torch.float32, (rows, T, 2))), optional=True)
         check(self.lib.gn_openloop_action_metrics(self._ctx, _ptr(a_hat), a_hat.stride(1), a_hat.stride(0), _ptr(actions), _ptr(joint_scale), _ptr(out),
                                                   B, T, A, int(row0), B if n_valid is None else int(n_valid), rows), "gn_openloop_action_metrics")
         return out
@@ -1559,16 +1571,13 @@ class Engine:
     @staticmethod
     def _first_tr_host(who: str, first_tr_host, N: int):
         """The optional host copy of ``first_tr``: with it an entry outside ``0 .. n`` is refused before anything is launched."""
-        if first_tr_host is None:
-            return
         import numpy as np
 
-        h = np.asarray(first_tr_host)
-        if h.dtype != np.int32 or h.shape != (N,):
-            raise GenimaHipError(f"{who}: first_tr_host must be int32 [{N}], got {h.dtype} {h.shape}")
-        bad = np.nonzero((h < 0) | (h > np.arange(N)))[0]
+        if _host_int32(who, first_tr_host, (N,)) is None:
+            return
+        bad = np.nonzero((first_tr_host < 0) | (first_tr_host > np.arange(N)))[0]
         if bad.size:
-            raise GenimaHipError(f"{who}: first_tr[{int(bad[0])}] = {int(h[bad[0]])} must lie in 0 .. {int(bad[0])}")
+            raise GenimaHipError(f"{who}: first_tr[{int(bad[0])}] = {int(first_tr_host[bad[0]])} must lie in 0 .. {int(bad[0])}")
 
     def openloop_exec_actions(self, chunks, first_tr, h: int, temporal_agg: bool = False, m: float = 0.01, *, A: Optional[int] = None, out=None,
                               n_calls=None, first_tr_host=None):
@@ -1577,8 +1586,7 @@ class Engine:
         ``(h, temporal_agg, m)`` executes at every transition, bit for bit what ``action_ensemble`` returns when it is called every ``h`` steps
         of each episode.  ``n_calls``: int32 [N] or None, the number of calls averaged.  ``first_tr_host``: an int32 numpy copy of
         ``first_tr``; with it an entry outside ``0 .. n`` is refused, without it the kernel clamps.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("openloop_exec_actions is an eager op: it scores tables that a run has filled")
+        _eager_only(self, "openloop_exec_actions", _SCORES_TABLES)
         if chunks.dim() != 3 or chunks.dtype != F16 or not chunks.is_cuda or chunks.stride(2) != 1 or chunks.stride(0) != chunks.shape[1] * chunks.stride(1):
             raise GenimaHipError("openloop_exec_actions: chunks must be f16 [N, T, ld] on the device with contiguous rows of one pitch")
         N, T = int(chunks.shape[0]), int(chunks.shape[1])
@@ -1587,9 +1595,8 @@ class Engine:
             raise GenimaHipError(f"openloop_exec_actions: A = {A} columns asked of chunks that hold {int(chunks.shape[2])}")
         if out is None:
             out = torch.empty((N, A), dtype=torch.float32, device=chunks.device)
-        for t, dt, shape in ((first_tr, torch.int32, (N,)), (out, torch.float32, (N, A)), (n_calls, torch.int32, (N,))):
-            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
-                raise GenimaHipError(f"openloop_exec_actions: a contiguous device tensor {dt} {shape} expected")
+        _expect_each("openloop_exec_actions", ((first_tr, torch.int32, (N,)), (out, torch.float32, (N, A))))
+        _expect("openloop_exec_actions", n_calls, torch.int32, (N,), optional=True)
         self._first_tr_host("openloop_exec_actions", first_tr_host, N)
         check(self.lib.gn_openloop_exec_actions(self._ctx, _ptr(chunks), _ptr(first_tr), _ptr(out), _ptr(n_calls), N, T, A, int(chunks.stride(1)), int(h),
                                                 int(bool(temporal_agg)), float(m)), "gn_openloop_exec_actions")
@@ -1600,17 +1607,15 @@ class Engine:
         demo action of each transition -> ``out`` f32 [N, 4] = (joint L1 sum over the A - 1 joints, gripper flag, executed jump from the step
         before, the demo's jump; both jumps 0 at an episode's first step).  ``joint_scale``: f32 [A - 1] or None (= 1).  ``first_tr`` /
         ``first_tr_host`` as ``openloop_exec_actions`` takes them.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("openloop_exec_metrics is an eager op: it scores tables that a run has filled")
+        _eager_only(self, "openloop_exec_metrics", _SCORES_TABLES)
         if exec_actions.dim() != 2:
             raise GenimaHipError("openloop_exec_metrics: exec_actions must be f32 [N, A]")
         N, A = (int(s) for s in exec_actions.shape)
         if out is None:
             out = torch.empty((N, 4), dtype=torch.float32, device=exec_actions.device)
-        for t, dt, shape, optional in ((exec_actions, torch.float32, (N, A), False), (demo, torch.float32, (N, A), False), (first_tr, torch.int32, (N,), False),
-                                       (joint_scale, torch.float32, (A - 1,), True), (out, torch.float32, (N, 4), False)):
-            if (t is None and not optional) or (t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape)):
-                raise GenimaHipError(f"openloop_exec_metrics: a contiguous device tensor {dt} {shape} expected")
+        _expect_each("openloop_exec_metrics", ((exec_actions, torch.float32, (N, A)), (demo, torch.float32, (N, A)), (first_tr, torch.int32, (N,)),
+                                               (out, torch.float32, (N, 4))))
+        _expect("openloop_exec_metrics", joint_scale, torch.float32, (A - 1,), optional=True)
         self._first_tr_host("openloop_exec_metrics", first_tr_host, N)
         check(self.lib.gn_openloop_exec_metrics(self._ctx, _ptr(exec_actions), _ptr(demo), _ptr(first_tr), _ptr(joint_scale), _ptr(out), N, A),
               "gn_openloop_exec_metrics")
@@ -1623,24 +1628,18 @@ class Engine:
         closest to their rays, its distance to ``centre``, the RMS ray and reprojection residuals and the conditioning; NaN in columns 1 .. 6
         where fewer than two views found the sphere or the rays are parallel within ``min_det``.  ``slot_host`` / ``win_host``: int32 numpy
         copies; with them a bad table is refused, without them the kernel reads a slot outside [0, S) as -1.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("openloop_triangulate is an eager op: it scores tables that a run has filled")
+        who = "openloop_triangulate"
+        _eager_only(self, who, _SCORES_TABLES)
         if sph.dim() != 4 or slot.dim() != 3:
             raise GenimaHipError("openloop_triangulate: sph must be int64 [N, V, S, 17] and slot int32 [N, G, V]")
         N, V, S = (int(s) for s in sph.shape[:3])
         G = int(slot.shape[1])
         if out is None:
             out = torch.empty((N, G, 2, 8), dtype=torch.float64, device=sph.device)
-        for t, dt, shape in ((sph, torch.int64, (N, V, S, 17)), (win, torch.int32, (N, V, S, 4)), (cams, torch.float32, (N, V, 18)),
-                             (slot, torch.int32, (N, G, V)), (centre, torch.float64, (N, G, 3)), (out, torch.float64, (N, G, 2, 8))):
-            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
-                raise GenimaHipError(f"openloop_triangulate: a contiguous device tensor {dt} {shape} expected")
-        hp = []
-        for h, shape in ((slot_host, (N, G, V)), (win_host, (N, V, S, 4))):
-            if h is not None and not (str(h.dtype) == "int32" and h.flags.c_contiguous and h.shape == shape):
-                raise GenimaHipError(f"openloop_triangulate: a contiguous int32 host copy {shape} expected, got {h.dtype} {h.shape}")
-            hp.append(None if h is None else h.ctypes.data)
-        check(self.lib.gn_openloop_triangulate(self._ctx, _ptr(sph), _ptr(win), _ptr(cams), _ptr(slot), _ptr(centre), hp[0], hp[1], _ptr(out),
+        _expect_each(who, ((sph, torch.int64, (N, V, S, 17)), (win, torch.int32, (N, V, S, 4)), (cams, torch.float32, (N, V, 18)),
+                           (slot, torch.int32, (N, G, V)), (centre, torch.float64, (N, G, 3)), (out, torch.float64, (N, G, 2, 8))))
+        check(self.lib.gn_openloop_triangulate(self._ctx, _ptr(sph), _ptr(win), _ptr(cams), _ptr(slot), _ptr(centre),
+                                               _host_int32(who, slot_host, (N, G, V)), _host_int32(who, win_host, (N, V, S, 4)), _ptr(out),
                                                float(min_ratio), float(min_det), N, V, S, G), "gn_openloop_triangulate")
         return out
 
@@ -1649,19 +1648,16 @@ class Engine:
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):
         """``gn_render_spheres`` over device tensors (genima_amd/render.py builds them): cams f32 [B, 18], spheres f32 [B, S, 16], tex_index
         int32 [B, S], count int32 [B], atlas uint8 [T, th, tw, 4], blend f64 [B], bg_frames int64 [n_tiled] (addresses of tiled uint8 frames, instead of bg); the outputs that are given are written.  Eager engines only."""
-        if self.record:
-            raise RuntimeError("render_spheres is an eager op: the poses change from batch to batch")
+        who = "render_spheres"
+        _eager_only(self, who, "the poses change from batch to batch")
         B, S = int(spheres.shape[0]), int(spheres.shape[1])
-        for t, dt, shape in ((cams, torch.float32, (B, 18)), (spheres, torch.float32, (B, S, 16)), (tex_index, torch.int32, (B, S)),
-                             (count, torch.int32, (B,)), (atlas, torch.uint8, None), (blend, torch.float64, (B,)), (tile_index, torch.int32, (B,)),
-                             (bg_frames, torch.int64, (n_tiled,))):
-            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and (shape is None or tuple(t.shape) == shape)), (dt, shape)
-        assert atlas.dim() == 4 and atlas.shape[3] == 4
         flat, tiled = (B, H, W, 3), (n_tiled, 2 * H, 2 * W)
-        for t, dt, shape in ((bg, torch.uint8, tiled + (3,) if bg_tiled else flat), (bg2, torch.uint8, tiled + (3,) if bg_tiled else flat),
-                             (full, torch.uint8, flat), (rnd, torch.uint8, flat), (occupied, torch.uint8, (B, H, W)),
-                             (full_f16, F16, tiled + (8,)), (rnd_f16, F16, tiled + (8,))):
-            assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape), (dt, shape)
+        _expect(who, atlas, torch.uint8, tuple(atlas.shape[:3]) + (4,))
+        _expect_each(who, ((cams, torch.float32, (B, 18)), (spheres, torch.float32, (B, S, 16)), (tex_index, torch.int32, (B, S)), (count, torch.int32, (B,)),
+                           (blend, torch.float64, (B,)), (tile_index, torch.int32, (B,)), (bg_frames, torch.int64, (n_tiled,)),
+                           (bg, torch.uint8, tiled + (3,) if bg_tiled else flat), (bg2, torch.uint8, tiled + (3,) if bg_tiled else flat),
+                           (full, torch.uint8, flat), (rnd, torch.uint8, flat), (occupied, torch.uint8, (B, H, W)),
+                           (full_f16, F16, tiled + (8,)), (rnd_f16, F16, tiled + (8,))), optional=True)
         d = _lib.RenderDesc(cams=_ptr(cams), spheres=_ptr(spheres), tex_index=_ptr(tex_index), count=_ptr(count), atlas=_ptr(atlas), bg=_ptr(bg),
                             bg2=_ptr(bg2), blend=_ptr(blend), tile_index=_ptr(tile_index), bg_frames=_ptr(bg_frames), full=_ptr(full), rnd=_ptr(rnd), occupied=_ptr(occupied),
                             full_f16=_ptr(full_f16), rnd_f16=_ptr(rnd_f16), B=B, S=S, H=int(H), W=int(W), T=int(atlas.shape[0]),

@@ -62,6 +62,11 @@ def _mean(x) -> Optional[float]:
     return float(x.mean()) if x.size else None
 
 
+def _ratio(a, b, fill=np.nan) -> np.ndarray:
+    """``a / b`` where ``b > 0``, ``fill`` elsewhere."""
+    return np.divide(a, b, out=np.full(np.shape(a), fill), where=b > 0)
+
+
 EXEC_COLUMNS = ("joint_l1", "gripper", "jump", "demo_jump")  # gn_openloop_exec_metrics' four values per transition
 POINT_COLUMNS = ("n_views", "x", "y", "z", "err_m", "ray_rms_m", "reproj_rms_px", "det")  # gn_openloop_triangulate's eight values per (transition, group, kind)
 POINT_KINDS = ("generated", "ground_truth")
@@ -226,12 +231,10 @@ class OpenLoopResult:
 
     def sphere_rmse(self) -> np.ndarray:
         """f64 [N, V]: ``sqrt(se_in / (3 n_in))``, NaN where ``n_in`` is 0 (no sphere drawn: the last two steps of a trajectory)."""
-        se, n = self.image[..., 0].astype(np.float64), self.image[..., 1].astype(np.float64)
-        return np.sqrt(np.divide(se, 3.0 * n, out=np.full(se.shape, np.nan), where=n > 0))
+        return np.sqrt(_ratio(self.image[..., 0].astype(np.float64), 3.0 * self.image[..., 1].astype(np.float64)))
 
     def background_rmse(self) -> np.ndarray:
-        se, n = self.image[..., 2].astype(np.float64), self.image[..., 3].astype(np.float64)
-        return np.sqrt(np.divide(se, 3.0 * n, out=np.full(se.shape, np.nan), where=n > 0))
+        return np.sqrt(_ratio(self.image[..., 2].astype(np.float64), 3.0 * self.image[..., 3].astype(np.float64)))
 
     def wrapped_mse(self) -> np.ndarray:
         """f64 [N]: the reference's validation ``mse`` (numpy's wrapping uint8 arithmetic) of the whole tiled image."""
@@ -248,9 +251,7 @@ class OpenLoopResult:
     def _moments(self, o: int):
         """-> (mass, centroid x, centroid y, radial RMS spread) of the four sums at columns o .. o + 3; NaN where the mass is 0."""
         m = self._col(o)
-        nan = np.full(m.shape, np.nan)
-        cx, cy = (np.divide(self._col(o + k), m, out=nan.copy(), where=m > 0) for k in (1, 2))
-        r2 = np.divide(self._col(o + 3), m, out=nan.copy(), where=m > 0)
+        cx, cy, r2 = (_ratio(self._col(o + k), m) for k in (1, 2, 3))
         with np.errstate(invalid="ignore"):
             return m, cx, cy, np.sqrt(np.maximum(0.0, r2 - cx * cx - cy * cy))
 
@@ -260,19 +261,31 @@ class OpenLoopResult:
         return np.hypot(gx - tx, gy - ty)
 
     def sphere_mass_ratio(self) -> np.ndarray:
-        g, t = self._col(1), self._col(5)
-        return np.divide(g, t, out=np.full(g.shape, np.nan), where=t > 0)
+        return _ratio(self._col(1), self._col(5))
 
     def sphere_spread_ratio(self) -> np.ndarray:
         """Generated over true radial RMS spread; NaN where either mass is 0 or the true spread is 0 (a one-pixel target)."""
-        sg, st = self._moments(1)[3], self._moments(5)[3]
-        return np.divide(sg, st, out=np.full(sg.shape, np.nan), where=st > 0)
+        return _ratio(self._moments(1)[3], self._moments(5)[3])
 
     def sphere_colour_l1(self) -> np.ndarray:
         """Mean over the channels of |sum gen_c - sum gt_c| / n_occ over the window's occupied pixels; NaN where undrawn or n_occ is 0."""
         n = self._col(9)
         d = np.abs(self.spheres[..., 11:14] - self.spheres[..., 14:17]).astype(np.float64).mean(axis=-1)
-        return np.where(self.sphere_drawn(), np.divide(d, n, out=np.full(n.shape, np.nan), where=n > 0), np.nan)
+        return np.where(self.sphere_drawn(), _ratio(d, n), np.nan)
+
+    def _per_camera(self, drawn: np.ndarray, block) -> Dict:
+        """``block(sel) -> dict`` over ``drawn`` (bool [n, V, S]) restricted to each camera in turn -> ``{key: {camera: value}}`` for every key
+        of the block, and the block over all of ``drawn`` under ``overall``."""
+        per = {c: block(drawn & (np.arange(len(self.cameras)) == v)[None, :, None]) for v, c in enumerate(self.cameras)}
+        overall = block(drawn)
+        return dict({k: {c: per[c][k] for c in self.cameras} for k in overall}, overall=overall)
+
+    def _over_tasks(self, block, **extra) -> Dict:
+        """``block(rows) -> dict`` over all transitions, then ``extra``, then the block per task under ``per_task`` when there is more than one."""
+        out = dict(block(np.ones(len(self), bool)), **extra)
+        if len(self.tasks) > 1:
+            out["per_task"] = {t: block(self.task == i) for i, t in enumerate(self.tasks)}
+        return out
 
     def _sphere_summary(self, rows: np.ndarray, found_mass: float) -> Dict:
         drawn = self.sphere_drawn()[rows]
@@ -287,9 +300,7 @@ class OpenLoopResult:
             return {"n_drawn": n, "found_rate": float((mass[sel] >= found_mass).mean()) if n else None, "shift_px": _mean(shift[sel]),
                     "mass_ratio": _mean(mass[sel]), "spread_ratio": _mean(spread[sel]), "colour_l1": _mean(colour[sel])}
 
-        per = {c: block(drawn & (np.arange(len(self.cameras)) == v)[None, :, None]) for v, c in enumerate(self.cameras)}
-        out = {k: {c: per[c][k] for c in self.cameras} for k in ("n_drawn", "found_rate", "shift_px", "mass_ratio", "spread_ratio", "colour_l1")}
-        out["overall"] = block(drawn)
+        out = self._per_camera(drawn, block)
         out["score"] = float(scored[drawn].mean()) if drawn.any() else None
         return out
 
@@ -320,11 +331,7 @@ class OpenLoopResult:
         ``found_rate`` (the share of drawn spheres whose mass ratio is at least ``found_mass``) and the means of the shift in pixels, the mass
         ratio, the spread ratio and the colour L1; ``score``, lower is better: the mean over the drawn spheres of the shift, a sphere without
         generated mass counting as half the diagonal of its window.  Like every score here it is not a success rate."""
-        out = self._summary(np.ones(len(self), bool), found_mass)
-        out["cameras"], out["tasks"] = self.cameras, self.tasks
-        if len(self.tasks) > 1:
-            out["per_task"] = {t: self._summary(self.task == i, found_mass) for i, t in enumerate(self.tasks)}
-        return out
+        return self._over_tasks(lambda rows: self._summary(rows, found_mass), cameras=self.cameras, tasks=self.tasks)
 
     def _execution_block(self, tabs: Dict, h: int, rows: np.ndarray) -> Dict:
         J = float(self.joints)
@@ -354,15 +361,11 @@ class OpenLoopResult:
         when there is more than one.  Open-loop like every score here: each chunk was predicted from a demo state."""
         if self.executions is None:
             return None
-        every, out = np.ones(len(self), bool), []
+        out = []
         for ex in self.executions:
             h = int(ex["h"])
             d = {"h": h, "temporal_agg": bool(ex["temporal_agg"]), "m": float(ex["m"]), "K": int(ex["K"]), "calls_per_step": 1.0 / h}
-            kinds = [k for k in ("generated", "oracle") if k in ex]
-            for k in kinds:
-                d[k] = self._execution_block(ex[k], h, every)
-            if len(self.tasks) > 1:
-                d["per_task"] = {t: {k: self._execution_block(ex[k], h, self.task == i) for k in kinds} for i, t in enumerate(self.tasks)}
+            d.update(self._over_tasks(lambda rows: {k: self._execution_block(ex[k], h, rows) for k in ("generated", "oracle") if k in ex}))
             out.append(d)
         return out
 
@@ -381,8 +384,7 @@ class OpenLoopResult:
         d = self.point_centres[:, :, None, :] - pose[:, None, :, :, 3]  # c - t, [N, G, V, 3]
         z = -np.einsum("nvj,ngvj->ngv", pose[..., 2], d)  # -(R^T (c - t)).z: R's third column
         term = np.where(slots >= 0, 0.5 * diag * z / np.abs(cams[:, None, :, 0]), np.nan)
-        cnt = (slots >= 0).sum(axis=-1)
-        return np.divide(np.nansum(term, axis=-1), cnt, out=np.full((N, G), np.nan), where=cnt > 0)
+        return _ratio(np.nansum(term, axis=-1), (slots >= 0).sum(axis=-1))
 
     def _triangulation_block(self, rows: np.ndarray) -> Dict:
         P = self.points[rows]
@@ -413,10 +415,7 @@ class OpenLoopResult:
         task when there is more than one.  Teacher-forced like every score here, and not a success rate."""
         if self.points is None:
             return None
-        out = self._triangulation_block(np.ones(len(self), bool))
-        if len(self.tasks) > 1:
-            out["per_task"] = {t: self._triangulation_block(self.task == i) for i, t in enumerate(self.tasks)}
-        return out
+        return self._over_tasks(self._triangulation_block)
 
     def orientation_scores(self, found_mass: float = 0.5, min_pixels: int = 50) -> Dict[str, np.ndarray]:
         """Per sphere, [N, V, S], in numpy f64.  ``readable`` (bool): the ground-truth cost curve ``se_gt / n_gt`` over the candidates is not
@@ -428,9 +427,7 @@ class OpenLoopResult:
         construction, since the identity candidate reproduces the ground truth."""
         O = self.orientation.astype(np.float64)
         ang, K = self.orientation_angles, self.orientation.shape[3]
-        nan = np.full(O.shape[:4], np.nan)
-        cg = np.divide(O[..., 0], O[..., 1], out=nan.copy(), where=O[..., 1] > 0)
-        ct = np.divide(O[..., 2], O[..., 3], out=nan.copy(), where=O[..., 3] > 0)
+        cg, ct = _ratio(O[..., 0], O[..., 1]), _ratio(O[..., 2], O[..., 3])
         drawn = self.sphere_drawn()
         readable = (O[..., 3] > 0).all(axis=-1) & (self.orientation[..., 2].max(axis=-1) > self.orientation[..., 2].min(axis=-1))
         with np.errstate(invalid="ignore"):
@@ -439,7 +436,7 @@ class OpenLoopResult:
         cg, ct = np.where(scored[..., None], cg, 0.0), np.where((drawn & readable)[..., None], ct, 0.0)  # no NaN reaches an argmin
         ig, it = np.argmin(cg, axis=-1), np.argmin(ct, axis=-1)
         cmin, cmean = cg.min(axis=-1), cg.mean(axis=-1)
-        contrast = 1.0 - np.divide(cmin, cmean, out=np.ones(cmin.shape), where=cmean > 0)
+        contrast = 1.0 - _ratio(cmin, cmean, fill=1.0)
         return {"readable": readable, "scored": scored, "found": found, "err_deg": np.where(scored, np.abs(ang[ig]), np.nan),
                 "contrast": np.where(scored, contrast, np.nan), "at_edge": np.where(scored, ((ig == 0) | (ig == K - 1)).astype(np.float64), np.nan),
                 "floor_deg": np.where(drawn & readable, np.abs(ang[it]), np.nan)}
@@ -459,10 +456,7 @@ class OpenLoopResult:
                     "within_step": float((err <= step * (1.0 + 1e-12)).mean()) if err.size else None, "contrast": _mean(sc["contrast"][s]),
                     "at_edge": _mean(sc["at_edge"][s]), "floor_deg": float(floor.max()) if floor.size else None}
 
-        per = {c: block(drawn & (np.arange(len(self.cameras)) == v)[None, :, None]) for v, c in enumerate(self.cameras)}
-        out: Dict = {k: {c: per[c][k] for c in self.cameras} for k in ("n_scored", "n_unreadable", "err_deg", "err_median_deg", "within_step", "contrast",
-                                                                           "at_edge", "floor_deg")}
-        out["overall"] = block(drawn)
+        out = self._per_camera(drawn, block)
         counted = drawn & sc["readable"] & (sc["scored"] | ~sc["found"])
         out["score_deg"] = float(np.where(sc["scored"], sc["err_deg"], half)[counted].mean()) if counted.any() else None
         return out
@@ -481,20 +475,13 @@ class OpenLoopResult:
         if self.orientation is None:
             return None
         sc = self.orientation_scores(found_mass, min_pixels)
-        out = self._orientation_block(sc, np.ones(len(self), bool))
-        out["angles_deg"] = self.orientation_angles.tolist()
-        if len(self.tasks) > 1:
-            out["per_task"] = {t: self._orientation_block(sc, self.task == i) for i, t in enumerate(self.tasks)}
-        return out
+        return self._over_tasks(lambda rows: self._orientation_block(sc, rows), angles_deg=self.orientation_angles.tolist())
 
     def to_json(self, path: str) -> Dict:
         s = self.summary()
-        if self.executions is not None:
-            s = dict(s, executions=self.execution_summary())  # a key of its own: summary() itself is as it was
-        if self.points is not None:
-            s = dict(s, spheres_3d=self.triangulation_summary())
-        if self.orientation is not None:
-            s = dict(s, orientation=self.orientation_summary())
+        for key, extra in (("executions", self.execution_summary()), ("spheres_3d", self.triangulation_summary()), ("orientation", self.orientation_summary())):
+            if extra is not None:  # a key of its own, and only with its table: summary() itself is as it was
+                s[key] = extra
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as f:
             json.dump(s, f, indent=1)
@@ -508,6 +495,40 @@ def _task_of(ep, description: str) -> str:
         if len(parts) >= 4 and parts[-2] == "episodes" and parts[-3].startswith("variation"):
             return parts[-4]
     return description
+
+
+_NUMPY_OF = {torch.int64: np.int64, torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int32, torch.float16: np.float16}
+
+
+def readback_layout(tables: Dict[str, Optional[torch.Tensor]]) -> Dict[str, int]:
+    """name -> byte offset of each table in ``read_back``'s packed buffer, in packing order.  None entries are dropped and the rest are
+    stable-sorted by element size, widest first: the sizes are powers of two, so every table starts on a multiple of its own."""
+    offsets, o = {}, 0
+    for name in sorted((k for k, t in tables.items() if t is not None), key=lambda k: -tables[k].element_size()):
+        offsets[name] = o
+        o += tables[name].numel() * tables[name].element_size()
+    return offsets
+
+
+def read_back(tables: Dict[str, Optional[torch.Tensor]]) -> Dict[str, np.ndarray]:
+    """Named contiguous tensors of one device (None entries are dropped) -> a host copy of each under its name, with its dtype and shape, in
+    the order given.  One ``torch.cat`` of the tables' bytes, laid out as ``readback_layout`` says, and one copy to the host."""
+    offsets = readback_layout(tables)
+    if not offsets:
+        return {}
+    host = torch.cat([tables[k].reshape(-1).view(torch.uint8) for k in offsets]).cpu().numpy()
+    return {k: host[offsets[k]: offsets[k] + t.numel() * t.element_size()].view(_NUMPY_OF[t.dtype]).reshape(tuple(t.shape)).copy()
+            for k, t in tables.items() if t is not None}
+
+
+def _map_tensors(tree, fn, name: str = ""):
+    """``tree``: nested dicts and lists -> the same tree with every tensor ``t`` in it replaced by ``fn(name, t)``, ``name`` the keys and list
+    positions that lead to it joined by ``/`` (``executions/0/oracle/scores/norm``); every other leaf stays as it is."""
+    if isinstance(tree, torch.Tensor):
+        return fn(name, tree)
+    if isinstance(tree, dict):
+        return {k: _map_tensors(v, fn, f"{name}/{k}".lstrip("/")) for k, v in tree.items()}
+    return [_map_tensors(v, fn, f"{name}/{i}") for i, v in enumerate(tree)] if isinstance(tree, list) else tree
 
 
 class OpenLoopEval:
@@ -558,8 +579,35 @@ class OpenLoopEval:
                  batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
                  change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None, triangulate: bool = False,
                  tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6, orientation=None):
-        from .render import load_atlas, load_traj, sphere_windows
+        from .render import load_traj
 
+        device, engine, T = self._check_options(diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions,
+                                                triangulate, tri_min_ratio, tri_min_det, orientation)
+        self.cfg, self.batch_size = render_cfg, int(batch_size)
+        self.num_inference_steps, self.guidance_scale, self.seed = int(num_inference_steps), float(guidance_scale), int(seed)
+        H, W = int(render_cfg.image_height), int(render_cfg.image_width)
+        eps, trajs = [], []
+        for ep in episodes:
+            if isinstance(ep, (str, os.PathLike)):
+                eps.append(os.fspath(ep))
+                trajs.append(load_traj(os.path.join(os.fspath(ep), "traj.npz")))
+            else:
+                eps.append((ep[0], ep[1]) + tuple(ep[3:4]))
+                trajs.append(ep[2])
+        rp = self.replay = DeviceReplay(eps, self.cameras, engine=engine, device=device, frame_stack=1, action_sequence=T, batch_size=self.batch_size, tokenizer=tokenizer,
+                                        image_size=H if H == W and isinstance(eps[0], str) else None, stats=stats)
+        if (rp.H, rp.W) != (H, W):
+            raise ValueError(f"OpenLoopEval: the frames are {rp.H} x {rp.W}, the render config draws {H} x {W}")
+        if controller is not None and rp.A != int(controller.config["action_dim"]):
+            raise ValueError(f"OpenLoopEval: the demos' actions have {rp.A} elements, the controller's {controller.config['action_dim']}")
+        if self.executions is not None and tuple(rp.action.shape) != (rp.N, rp.A):
+            raise ValueError(f"OpenLoopEval: the replay's demo actions are {tuple(rp.action.shape)}, expected {(rp.N, rp.A)}")
+        self.E, self.N, self.H, self.W, self.T, self.A = rp.E, rp.N, H, W, rp.T, rp.A
+        self._upload(self._transition_tables(trajs, episodes), stats)
+
+    def _check_options(self, diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions, triangulate,
+                       tri_min_ratio, tri_min_det, orientation):
+        """Part one of the setup, before any device work: every option checked and kept -> ``(device, engine, T)`` for the replay."""
         if controller is None:
             if diffusion_agent is None:
                 raise ValueError("OpenLoopEval: nothing to score -- give a diffusion agent, a controller or both")
@@ -580,7 +628,7 @@ class OpenLoopEval:
                 raise ValueError(f"OpenLoopEval: action_sequence = {action_sequence} contradicts the controller's num_queries = {T}")
         if int(change_threshold) < 0:
             raise ValueError(f"OpenLoopEval: change_threshold = {change_threshold} must not be negative")
-        self.executions = self.first_tr = self.first_tr_host = None
+        self.executions = None
         if executions is not None:  # the execution modes to replay over the chunks, checked as GenimaACT.set_execution checks them
             from .act import check_ensemble_m, execution_slots
 
@@ -594,7 +642,6 @@ class OpenLoopEval:
                 h, K = execution_slots(T, ex[0], bool(ex[1]))
                 self.executions.append({"h": int(h), "temporal_agg": bool(ex[1]), "m": check_ensemble_m(ex[2] if len(ex) > 2 else 0.01), "K": int(K)})
         self.triangulate, self.tri_min_ratio, self.tri_min_det = bool(triangulate), float(tri_min_ratio), float(tri_min_det)
-        self.point_slots = self.point_slots_host = self.point_centres = self.point_centres_host = self.cams_host = None
         if self.triangulate:
             if diffusion_agent is None:
                 raise ValueError("OpenLoopEval: triangulate places the generated spheres; without a diffusion agent nothing is generated")
@@ -605,35 +652,20 @@ class OpenLoopEval:
         if orient is not None:
             if diffusion_agent is None:
                 raise ValueError("OpenLoopEval: orientation reads the generated spheres; without a diffusion agent nothing is generated")
-            self.orientation_angles, self.orientation_rot = orientation_candidates(**orient)  # uploaded below, once the device is known
-        self.change_threshold = int(change_threshold)
-        self.agent, self.controller, self.cameras, self.V = diffusion_agent, controller, tuple(cameras), len(cameras)
+            self.orientation_angles, self.orientation_rot = orientation_candidates(**orient)  # on the host until _upload
+        self.agent, self.controller, self.cameras, self.V, self.change_threshold = diffusion_agent, controller, tuple(cameras), len(cameras), int(change_threshold)
         if diffusion_agent is not None and self.V != 4:
             raise ValueError(f"OpenLoopEval: the 2x2 canvas takes exactly four cameras, got {self.V}")
-        self.cfg, self.batch_size = render_cfg, int(batch_size)
-        self.num_inference_steps, self.guidance_scale, self.seed = int(num_inference_steps), float(guidance_scale), int(seed)
-        H, W = int(render_cfg.image_height), int(render_cfg.image_width)
-        eps, trajs = [], []
-        for ep in episodes:
-            if isinstance(ep, (str, os.PathLike)):
-                eps.append(os.fspath(ep))
-                trajs.append(load_traj(os.path.join(os.fspath(ep), "traj.npz")))
-            else:
-                eps.append((ep[0], ep[1]) + tuple(ep[3:4]))
-                trajs.append(ep[2])
-        self.replay = DeviceReplay(eps, self.cameras, engine=engine, device=device, frame_stack=1, action_sequence=T, batch_size=self.batch_size, tokenizer=tokenizer,
-                                   image_size=H if H == W and isinstance(eps[0], str) else None, stats=stats)
-        rp = self.replay
-        if (rp.H, rp.W) != (H, W):
-            raise ValueError(f"OpenLoopEval: the frames are {rp.H} x {rp.W}, the render config draws {H} x {W}")
-        if controller is not None and rp.A != int(controller.config["action_dim"]):
-            raise ValueError(f"OpenLoopEval: the demos' actions have {rp.A} elements, the controller's {controller.config['action_dim']}")
-        self.E, self.N, self.H, self.W, self.T, self.A = rp.E, rp.N, H, W, rp.T, rp.A
-        dev = self.E.device
-        # ---- per-transition view tables: transition n of episode e, step t, reads observation t of trajectory e
+        return device, engine, T
+
+    def _transition_tables(self, trajs, episodes) -> Dict[str, np.ndarray]:
+        """Part two, on the host: transition n of episode e, step t, reads observation t of trajectory e -> the view tables [N, V, ...] to
+        upload; the step, episode and task of every transition, the spheres' windows, the groups and the episodes' first transitions are kept."""
+        from .render import sphere_windows
         from .replay import view_tables
 
-        vt = view_tables(trajs, render_cfg, self.cameras)  # row obs * V + v over EVERY step of every trajectory
+        rp = self.replay
+        vt = view_tables(trajs, self.cfg, self.cameras)  # row obs * V + v over EVERY step of every trajectory
         starts = np.concatenate([[0], np.cumsum([len(t["gripper_open"]) for t in trajs])])
         ep_of = rp.host["episode"]
         counts = np.bincount(ep_of, minlength=rp.N_ep)  # transitions per episode
@@ -642,36 +674,37 @@ class OpenLoopEval:
             if len(t["gripper_open"]) != int(counts[e]) + 1:
                 raise ValueError(f"OpenLoopEval: episode {e} has {int(counts[e]) + 1} observations in its demo and {len(t['gripper_open'])} steps in its trajectory")
         rows = ((starts[ep_of] + step)[:, None] * self.V + np.arange(self.V)[None]).reshape(-1)
-        self.views = {k: torch.from_numpy(np.ascontiguousarray(vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:]))).to(dev) for k in vt}
-        self.atlas = torch.from_numpy(load_atlas(render_cfg.texture_dir)).to(dev)
-        self.windows = self.windows_host = None
-        if diffusion_agent is not None:  # the spheres' windows of every transition, once: int32 [N, V, S, 4], host and device
-            tab = {k: vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:]) for k in ("cams", "spheres", "count")}
-            self.windows_host = np.ascontiguousarray(sphere_windows(tab["cams"], tab["spheres"], tab["count"], H, W))
-            self.windows = torch.from_numpy(self.windows_host).to(dev)
+        views = {k: np.ascontiguousarray(vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:])) for k in vt}
+        self.windows_host = self.point_slots_host = self.point_centres_host = self.cams_host = None
+        if self.agent is not None:  # the spheres' windows of every transition, once: int32 [N, V, S, 4]
+            self.windows_host = np.ascontiguousarray(sphere_windows(views["cams"], views["spheres"], views["count"], self.H, self.W))
             if self.triangulate:  # which slot of which view shows which sphere, and where it truly is: int32 [N, G, V], f64 [N, G, 3]
-                self.point_slots_host, self.point_centres_host = sphere_groups(tab["spheres"], tab["count"], self.windows_host)
-                self.point_slots, self.point_centres = (torch.from_numpy(a).to(dev) for a in (self.point_slots_host, self.point_centres_host))
-                self.cams_host = np.ascontiguousarray(tab["cams"])
-        if self.orientation_rot is not None:
-            self.orientation_rot = torch.from_numpy(self.orientation_rot).to(dev)
-        self.samples = int(render_cfg.samples)
+                self.point_slots_host, self.point_centres_host = sphere_groups(views["spheres"], views["count"], self.windows_host)
+                self.cams_host = views["cams"]
+        # with execution modes to replay: the first transition of each one's episode
+        self.first_tr_host = np.ascontiguousarray((np.arange(rp.N) - step).astype(np.int32)) if self.executions is not None else None
         self.step_index, self.episode_index = step, ep_of.copy()
         names = [_task_of(ep, d) for ep, d in zip(episodes, rp.descriptions)]
         self.tasks = sorted(set(names))
         self.task_index = np.asarray([self.tasks.index(names[e]) for e in ep_of], np.int32)
-        # ---- scales, prompt ids
-        self.joint_std = None
-        if controller is not None:
-            self.joint_std = torch.from_numpy(np.asarray(stats[0]["std"], np.float64)[: self.A - 1].astype(np.float32)).to(dev).contiguous()
-        self.prompts = [harness.make_prompt(d) for d in rp.descriptions]
-        self.prompt_ids = torch.cat([diffusion_agent.pipe.encode_ids([p]) for p in self.prompts]) if diffusion_agent is not None else None
-        self._n_index = torch.arange(rp.N, dtype=torch.int64, device=dev)
-        if self.executions is not None:  # the first transition of each one's episode, host and device
-            self.first_tr_host = np.ascontiguousarray((np.arange(rp.N) - step).astype(np.int32))
-            self.first_tr = torch.from_numpy(self.first_tr_host).to(dev)
-            if tuple(rp.action.shape) != (rp.N, rp.A):
-                raise ValueError(f"OpenLoopEval: the replay's demo actions are {tuple(rp.action.shape)}, expected {(rp.N, rp.A)}")
+        return views
+
+    def _upload(self, views: Dict[str, np.ndarray], stats) -> None:
+        """Part three: the view tables, the atlas, a device copy of every host table that part two kept, the scales and the prompt ids."""
+        from .render import load_atlas
+
+        def up(a):
+            return None if a is None else torch.from_numpy(a).to(self.E.device)
+
+        self.views = {k: up(a) for k, a in views.items()}
+        self.atlas = up(load_atlas(self.cfg.texture_dir))
+        self.windows, self.point_slots, self.point_centres = up(self.windows_host), up(self.point_slots_host), up(self.point_centres_host)
+        self.first_tr, self.orientation_rot = up(self.first_tr_host), up(self.orientation_rot)
+        self.samples = int(self.cfg.samples)
+        self.joint_std = up(np.asarray(stats[0]["std"], np.float64)[: self.A - 1].astype(np.float32)) if self.controller is not None else None
+        self.prompts = [harness.make_prompt(d) for d in self.replay.descriptions]
+        self.prompt_ids = torch.cat([self.agent.pipe.encode_ids([p]) for p in self.prompts]) if self.agent is not None else None
+
 
     # ---- the steps of one batch (the tests recompute a batch from these inputs)
     def batch_indices(self, start: int) -> np.ndarray:
@@ -818,50 +851,19 @@ class OpenLoopEval:
         generator = torch.Generator(device=self.E.device).manual_seed(self.seed) if self.agent is not None else None
         for start in range(0, self.N, self.batch_size):
             self.run_batch(start, tabs, generator)
-        # the one device-to-host copy: every table as bytes of one buffer
-        flat = [tabs[k][m] for k in ("generated", "oracle") if k in tabs for m in ("norm", "rad")] + [tabs[k] for k in ("image", "spheres") if k in tabs]
-        points = self.triangulate_spheres(tabs)
-        if points is not None:  # f64, straight after the int64 tables: the 8-byte tables stay together, ahead of everything narrower that follows
-            flat.append(points)
-        if "orientation" in tabs:  # int64: another 8-byte table, ahead of everything narrower
-            flat.append(tabs["orientation"])
-        n_before = len(flat)
-        execs = self.replay_executions(tabs)
-        if execs is not None:  # appended: 4-byte tables first, the f16 chunk tables last (every table then starts on its own type's grid)
-            kinds = list(tabs["chunks"])
-            for d in execs:
-                for k in kinds:
-                    flat += [d[k]["actions"], d[k]["n_calls"], d[k]["scores"]["norm"], d[k]["scores"]["rad"]]
-            flat += [tabs["chunks"][k] for k in kinds]
-        host = torch.cat([t.reshape(-1).view(torch.uint8) for t in flat]).cpu().numpy()
-        np_of = {torch.int64: np.int64, torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int32, torch.float16: np.float16}
-        out, o = [], 0
-        for t in flat:
-            n = t.numel() * t.element_size()
-            out.append(host[o: o + n].view(np_of[t.dtype]).reshape(tuple(t.shape)).copy())
-            o += n
-        executions = chunks = None
-        if execs is not None:
-            executions, k = [], n_before
-            for ex in self.executions:
-                d = dict(ex)
-                for kind in kinds:
-                    d[kind] = {"actions": out[k], "n_calls": out[k + 1], "scores": {"norm": out[k + 2], "rad": out[k + 3]}}
-                    k += 4
-                executions.append(d)
-            chunks = {kind: out[k + i] for i, kind in enumerate(kinds)}
-        actions, k = {}, 0
-        for name in ("generated", "oracle"):
-            if name in tabs:
-                actions[name] = {"norm": out[k], "rad": out[k + 1]}
-                k += 2
-        image, spheres = (out[k], out[k + 1]) if "image" in tabs else (None, None)
-        orient = out[k + 2 + (points is not None)] if "orientation" in tabs else None
-        return OpenLoopResult(image, actions, self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1, self.H, self.W,
-                              spheres=spheres, windows=self.windows_host if spheres is not None else None, executions=executions, chunks=chunks,
-                              points=out[k + 2] if points is not None else None, point_slots=self.point_slots_host,
-                              point_centres=self.point_centres_host, cams=self.cams_host, orientation=orient,
-                              orientation_angles=self.orientation_angles if orient is not None else None)
+        dev = {"actions": {k: tabs[k] for k in ("generated", "oracle") if k in tabs}, "image": tabs.get("image"), "spheres": tabs.get("spheres"),
+               "points": self.triangulate_spheres(tabs), "orientation": tabs.get("orientation"), "executions": self.replay_executions(tabs),
+               "chunks": tabs.get("chunks")}
+        # the one device-to-host copy, after the last launch: every table by its name in the tree, as bytes of one buffer
+        named: Dict[str, torch.Tensor] = {}
+        _map_tensors(dev, named.__setitem__)
+        copies = read_back(named)
+        host = _map_tensors(dev, lambda name, t: copies[name])
+        return OpenLoopResult(host["image"], host["actions"], self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1,
+                              self.H, self.W, spheres=host["spheres"], windows=self.windows_host if host["spheres"] is not None else None,
+                              executions=host["executions"], chunks=host["chunks"], points=host["points"], point_slots=self.point_slots_host,
+                              point_centres=self.point_centres_host, cams=self.cams_host, orientation=host["orientation"],
+                              orientation_angles=self.orientation_angles if host["orientation"] is not None else None)
 
 
 def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None,
