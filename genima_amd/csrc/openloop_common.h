@@ -1,5 +1,5 @@
-// What the open-loop score kernels share (openloop.hip, openloop_orient.hip): the workgroup size, global-load pointer types, the integer wave
-// sum, the window clamp and the optional host check of a window table.  Both files are built with -ffp-contract=off.
+// What the open-loop score kernels share (openloop.hip, openloop_orient.hip, openloop_seeds.hip): the workgroup size, global-load pointer
+// types, the integer wave sum, the window clamp and the optional host check of a window table.  All three are built with -ffp-contract=off.
 #pragma once
 #include "common.h"
 

@@ -1643,6 +1643,46 @@ class Engine:
                                                float(min_ratio), float(min_det), N, V, S, G), "gn_openloop_triangulate")
         return out
 
+    def openloop_seed_spheres(self, sph, out=None, *, min_ratio: float = 0.5):
+        """``gn_openloop_seed_spheres``: ``sph`` int64 [R, N, V, S, 17], ``openloop_sphere_metrics``' finished table of each of R generator
+        seeds -> ``out`` f64 [N, V, S, 8]: per sphere the number of seeds that found it (generated mass at least ``min_ratio`` of the true
+        one), the bias of the seeds' mean centroid against the true one (x, y), the seeds' spread about their mean, the mean squared shift,
+        the mean and the population variance of the mass ratio and the largest squared shift; NaN in columns 1 .. 7 where no seed found it.
+        Eager engines only."""
+        who = "openloop_seed_spheres"
+        _eager_only(self, who, _SCORES_TABLES)
+        if not isinstance(sph, torch.Tensor) or sph.dim() != 5:
+            raise GenimaHipError("openloop_seed_spheres: sph must be int64 [R, N, V, S, 17]")
+        R, N, V, S = (int(s) for s in sph.shape[:4])
+        if out is None:
+            out = torch.empty((N, V, S, 8), dtype=torch.float64, device=sph.device)
+        _expect_each(who, ((sph, torch.int64, (R, N, V, S, 17)), (out, torch.float64, (N, V, S, 8))))
+        check(self.lib.gn_openloop_seed_spheres(self._ctx, _ptr(sph), _ptr(out), float(min_ratio), R, N, V, S), "gn_openloop_seed_spheres")
+        return out
+
+    def openloop_seed_actions(self, chunks, demo, out=None, *, joint_scale=None):
+        """``gn_openloop_seed_actions``: ``chunks`` f16 [R, N, T, ld] (the chunk the controller predicted from each of R seeds' images; the
+        first ``A`` columns count), ``demo`` f32 [N, T, A] (the normalised demo chunks) -> ``out`` f32 [N, T, 4] = (the joint L1 sum of the
+        SEED-MEAN chunk against the demo's, the gripper flag of the mean logit, the mean absolute deviation across the seeds, the mean of the
+        seeds' own joint L1 sums -- each seed's as ``openloop_action_metrics`` writes it).  ``joint_scale``: f32 [A - 1] or None (= 1).  Eager
+        engines only."""
+        who = "openloop_seed_actions"
+        _eager_only(self, who, _SCORES_TABLES)
+        if not isinstance(chunks, torch.Tensor) or chunks.dim() != 4 or not isinstance(demo, torch.Tensor) or demo.dim() != 3:
+            raise GenimaHipError("openloop_seed_actions: chunks must be f16 [R, N, T, ld] and demo f32 [N, T, A]")
+        R, N, T, ld = (int(s) for s in chunks.shape)
+        A = int(demo.shape[2])
+        if out is None:
+            out = torch.empty((N, T, 4), dtype=torch.float32, device=chunks.device)
+        _expect_each(who, ((chunks, F16, (R, N, T, ld)), (demo, torch.float32, (N, T, A)), (out, torch.float32, (N, T, 4))))
+        _expect(who, joint_scale, torch.float32, (A - 1,), optional=True)
+        if R < 1:
+            raise GenimaHipError("openloop_seed_actions: chunks hold no seed")
+        inv_R = float(torch.tensor(1.0 / R, dtype=torch.float64).to(torch.float32))  # rounded once, here
+        check(self.lib.gn_openloop_seed_actions(self._ctx, _ptr(chunks), ld, _ptr(demo), _ptr(joint_scale), _ptr(out), inv_R, R, N, T, A),
+              "gn_openloop_seed_actions")
+        return out
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

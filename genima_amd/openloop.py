@@ -32,6 +32,12 @@ here.  What a demo tree does give is, for every transition, t
   at which angle the generated stripes fit best and how sharply.  The stripe texture is the only place the image carries a joint's rotation;
   every other sphere score is blind to it.
 
+* optionally, how much of all that is the SEED: ``seeds=R`` repeats the generation with R generator seeds, keeps the tables per seed and
+  reduces over the seed axis on the device -- ``gn_openloop_seed_spheres`` (per sphere: the bias of the seeds' mean centroid, their spread
+  about it) and ``gn_openloop_seed_actions`` (the error of the seed-mean chunk beside the mean of the seeds' errors) -- so ``seed_summary()``
+  can give every score's seed-to-seed standard deviation, the noise floor a checkpoint difference has to beat, and say whether a sphere that
+  lands off is wrong on average or wrong at random.
+
 ``OpenLoopEval(agent, None, ...)`` is the diffusion-only mode (no controller exists while the ControlNet is being fine-tuned):
 ``diffusion_validator`` makes a ``train_loop.TrainLoop`` ``validate`` callable of it.
 
@@ -76,6 +82,21 @@ MAX_GROUPS = 8  # gn_openloop_triangulate's bound on G
 ORIENTATION_COLUMNS = ("se_gen", "n_gen", "se_gt", "n_gt")  # gn_openloop_orientation's four values per (transition, camera, sphere, candidate)
 MAX_CANDIDATES = 64  # gn_openloop_orientation's bound on K
 SHIFT_FOUND_MASS = 0.5  # OpenLoopEval(orientation=): a sphere below this mass ratio is compared unshifted (summary()'s default found_mass)
+
+
+SEED_SPHERE_COLUMNS = ("k", "bias_x", "bias_y", "spread", "shift_sq", "mass_ratio", "mass_ratio_var", "worst_sq")  # gn_openloop_seed_spheres' eight per sphere
+SEED_ACTION_COLUMNS = ("seed_mean_l1", "gripper", "spread", "mean_of_seeds_l1")  # gn_openloop_seed_actions' four values per (transition, chunk position)
+MAX_SEEDS = 64  # the bound of both on R
+# the scalars of diffusion_validator's line, by name: seed_summary() scores each of them per seed
+VALIDATOR_SCALARS = ("select", "found_rate", "shift_px", "mass_ratio", "spread_ratio", "colour_l1", "sphere_rmse", "background_rmse", "wrapped_mse")
+
+
+def _across(values) -> Dict:
+    """One score over the seeds -> ``{"values", "mean", "std", "min", "max"}``; ``std`` is the sample standard deviation (ddof = 1).  A None
+    (the score does not exist for that seed: nothing drawn, nothing found) is left out of the four statistics."""
+    v = np.asarray([x for x in values if x is not None], np.float64)
+    return {"values": list(values), "mean": float(v.mean()) if v.size else None, "std": float(v.std(ddof=1)) if v.size > 1 else None,
+            "min": float(v.min()) if v.size else None, "max": float(v.max()) if v.size else None}
 
 
 def orientation_candidates(K: int = 37, span_deg: float = 180.0, axis=(0, 0, 1)):
@@ -207,11 +228,22 @@ class OpenLoopResult:
     ``orientation``: None, or int64 [N, V, S, K, 4] (``ORIENTATION_COLUMNS``): per sphere and candidate rotation the squared error of the true
     sphere re-drawn at that rotation against the generated window and against the ground-truth render, each with its pixel count --
     ``gn_openloop_orientation`` -- with ``orientation_angles`` f64 [K], the candidates' angles in degrees (ascending, 0 among them).
-    ``summary()`` does not read them; ``orientation_summary()`` does."""
+    ``summary()`` does not read them; ``orientation_summary()`` does.
+
+    ``seeds``: None, or the list of the R generator seeds a run was repeated with.  With it ``seed_tables``: ``{"image": int64 [R, N, V, 5],
+    "spheres": int64 [R, N, V, S, 17]}`` and, with a controller, ``"generated": {"norm" | "rad": f32 [R, N, T, 2]}``, ``"chunks"`` f16
+    [R, N, T, A] and ``"demo"`` f32 [N, T, A] (the normalised demo chunks) -- slice 0 of each IS ``image`` / ``spheres`` /
+    ``actions["generated"]``; ``seed_spheres`` f64 [N, V, S, 8] (``SEED_SPHERE_COLUMNS``, ``gn_openloop_seed_spheres``) and ``seed_actions``
+    ``{"norm" | "rad": f32 [N, T, 4]}`` (``SEED_ACTION_COLUMNS``, ``gn_openloop_seed_actions``; None without a controller).  ``summary()`` and
+    the other read-outs describe the first seed and read none of these; ``seed_summary()`` does."""
 
     def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int,
                  spheres=None, windows=None, executions=None, chunks=None, points=None, point_slots=None, point_centres=None, cams=None,
-                 orientation=None, orientation_angles=None):
+                 orientation=None, orientation_angles=None, seeds=None, seed_tables=None, seed_spheres=None, seed_actions=None):
+        if seeds is not None and (seed_tables is None or seed_spheres is None or windows is None or len(seeds) != len(seed_tables["spheres"])):
+            raise ValueError("OpenLoopResult: seeds come with seed_tables, seed_spheres and windows, one slice per seed")
+        self.seeds = None if seeds is None else [int(s) for s in seeds]
+        self.seed_tables, self.seed_spheres, self.seed_actions = (seed_tables, seed_spheres, seed_actions) if seeds is not None else (None, None, None)
         if (spheres is None) != (windows is None):
             raise ValueError("OpenLoopResult: spheres and windows come together (the score needs the windows' diagonals)")
         if points is not None and (windows is None or point_slots is None or point_centres is None or cams is None):
@@ -477,9 +509,87 @@ class OpenLoopResult:
         sc = self.orientation_scores(found_mass, min_pixels)
         return self._over_tasks(lambda rows: self._orientation_block(sc, rows), angles_deg=self.orientation_angles.tolist())
 
+    def validator_scalars(self, found_mass: float = 0.5) -> Dict:
+        """The scalars of ``diffusion_validator``'s line (``VALIDATOR_SCALARS``) from ``summary(found_mass)``: ``select`` is the sphere
+        ``score``, the five sphere fields its ``overall`` block, the two RMSEs the means over all cameras."""
+        im = self.summary(found_mass)["image"]
+        sp = im["spheres"]
+        return {"select": sp["score"], "found_rate": sp["overall"]["found_rate"], "shift_px": sp["overall"]["shift_px"],
+                "mass_ratio": sp["overall"]["mass_ratio"], "spread_ratio": sp["overall"]["spread_ratio"], "colour_l1": sp["overall"]["colour_l1"],
+                "sphere_rmse": _mean(self.sphere_rmse()), "background_rmse": _mean(self.background_rmse()), "wrapped_mse": im["wrapped_mse"]}
+
+    def seed_result(self, r: int) -> "OpenLoopResult":
+        """The tables of seed ``r`` alone as a result of their own: what a run without ``seeds`` and with ``seed = seeds[r]`` returns in
+        ``image``, ``spheres`` and ``actions["generated"]`` (no oracle row, none of the optional tables)."""
+        st = self.seed_tables
+        acts = {"generated": {u: t[r] for u, t in st["generated"].items()}} if "generated" in st else {}
+        return OpenLoopResult(st["image"][r], acts, self.episode, self.step, self.task, self.tasks, self.cameras, self.joints, self.H, self.W,
+                              spheres=st["spheres"][r], windows=self.windows)
+
+    def _seed_sphere_block(self, sel: np.ndarray) -> Dict:
+        """``sel``: bool [N, V, S] -> the spread block over the selected spheres that at least two seeds found."""
+        t = self.seed_spheres
+        sel = sel & (t[..., 0] >= 2)
+        n = int(sel.sum())
+        if not n:
+            return {"n": 0, "found_all_rate": None, "bias_px": None, "spread_px": None, "rms_shift_px": None, "variance_share": None,
+                    "mass_ratio_std": None, "worst_px": None}
+        q = t[sel]
+        shift = float(q[:, 4].sum())
+        return {"n": n, "found_all_rate": float((q[:, 0] == len(self.seeds)).mean()), "bias_px": float(np.hypot(q[:, 1], q[:, 2]).mean()),
+                "spread_px": float(np.sqrt(q[:, 3].mean())), "rms_shift_px": float(np.sqrt(q[:, 4].mean())),
+                "variance_share": float(q[:, 3].sum() / shift) if shift > 0 else None, "mass_ratio_std": float(np.sqrt(q[:, 6].mean())),
+                "worst_px": float(np.sqrt(q[:, 7].max()))}
+
+    def seed_summary(self, found_mass: float = 0.5) -> Optional[Dict]:
+        """None without ``seeds``; else, in numpy f64:
+
+        ``seeds``: the seed values.  ``scores``: per scalar of the validator's line (``VALIDATOR_SCALARS``; ``select`` is the sphere
+        ``score``) and, with a controller, ``joint_l1_norm`` / ``joint_l1_rad`` / ``gripper_acc`` of ``generated``: ``{"values": [R], "mean",
+        "std", "min", "max"}`` -- ``values[r]`` is ``summary(found_mass)``'s own code on seed r's tables, so ``values[0]`` is the number
+        ``summary()`` reports, and ``std`` (ddof = 1) is the noise floor a difference between two checkpoints has to beat.
+
+        ``spheres``: ``overall`` and ``per_camera`` over the spheres at least two seeds found (``seed_spheres[..., 0] >= 2``, the evaluator's
+        ``seed_min_ratio`` deciding "found"): ``n``, ``found_all_rate`` (the share every seed found), ``bias_px`` (the mean distance of the
+        seeds' mean centroid from the true one), ``spread_px`` (the RMS distance of a seed's centroid from the seeds' mean), ``rms_shift_px``
+        (the RMS distance from the true centroid; ``rms_shift_px^2 = RMS(bias)^2 + spread_px^2``), ``variance_share`` = sum spread / sum
+        squared shift: 0 means every seed is wrong in the same way (bias: train more), 1 means the seeds scatter about the truth (noise: the
+        seed matters), ``mass_ratio_std`` (the RMS over the spheres of the seeds' standard deviation of the mass ratio) and ``worst_px``, the
+        largest shift of any seed.
+
+        ``actions`` (with a controller), per unit ``norm`` / ``rad``, per joint: ``mean_of_seeds`` (the seeds' own joint L1, averaged),
+        ``seed_mean`` (the joint L1 of the chunk averaged over the seeds), ``gain`` = 1 - seed_mean / mean_of_seeds: what executing the mean
+        of R sampled chunks would buy, ``spread`` (the mean absolute deviation of a joint across the seeds) and ``gripper_acc_seed_mean``.
+
+        Teacher-forced like every score here: a seed spread is not a success rate, and ``gain`` is what averaging buys open loop, on demo
+        states -- nothing is executed."""
+        if self.seeds is None:
+            return None
+        per = [self.seed_result(r) for r in range(len(self.seeds))]
+        scalars = [p.validator_scalars(found_mass) for p in per]
+        scores = {k: _across([s[k] for s in scalars]) for k in VALIDATOR_SCALARS}
+        if "generated" in self.seed_tables:
+            rows = np.ones(len(self), bool)
+            gen = [p._summary(rows, found_mass)["generated"] for p in per]
+            scores.update({k: _across([g[k] for g in gen]) for k in ("joint_l1_norm", "joint_l1_rad", "gripper_acc")})
+        out: Dict = {"seeds": list(self.seeds), "scores": scores}
+        everything = np.ones(self.seed_spheres.shape[:3], bool)
+        out["spheres"] = {"overall": self._seed_sphere_block(everything),
+                          "per_camera": {c: self._seed_sphere_block(everything & (np.arange(len(self.cameras)) == v)[None, :, None])
+                                         for v, c in enumerate(self.cameras)}}
+        if self.seed_actions is not None:
+            J, out["actions"] = float(self.joints), {}
+            for unit, t in self.seed_actions.items():
+                t = t.astype(np.float64)
+                each, mean = _mean(t[..., 3] / J), _mean(t[..., 0] / J)
+                out["actions"][unit] = {"mean_of_seeds": each, "seed_mean": mean, "gain": 1.0 - mean / each if each else None,
+                                        "spread": _mean(t[..., 2] / J), "gripper_acc_seed_mean": _mean(t[..., 1])}
+        return out
+
     def to_json(self, path: str) -> Dict:
         s = self.summary()
-        for key, extra in (("executions", self.execution_summary()), ("spheres_3d", self.triangulation_summary()), ("orientation", self.orientation_summary())):
+        for key, extra in (("executions", self.execution_summary()), ("spheres_3d", self.triangulation_summary()), ("orientation", self.orientation_summary()),
+                           ("seeds", self.seed_summary())):
             if extra is not None:  # a key of its own, and only with its table: summary() itself is as it was
                 s[key] = extra
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -569,6 +679,18 @@ class OpenLoopEval:
     fills the batch's rows of an int64 [N, V, S, K, 4] table, which rides in the same device-to-host copy (``OpenLoopResult.orientation``,
     ``orientation_summary()``).  It needs a diffusion agent; with None nothing changes: the same launches, the same tables, the same bits.
 
+    ``seeds``: None, or the number R in [2, 64] of generator seeds to repeat the generation with: how much of a score is the checkpoint and how
+    much the noise draw.  ``run()`` then makes R device generators seeded ``seed + r``; per batch the targets are made once and, for r in order,
+    the pipeline runs with generator r, then ``act_tiled`` and the image / sphere / action scores, into seed r's rows of tables with a leading
+    seed axis (each seed's chunk is copied out of the program's output buffer before the next ``act_tiled`` overwrites it); the oracle pass
+    runs once, and the batch's normalised demo chunk is kept.  Seed 0's slices ARE ``image`` / ``spheres`` / ``actions["generated"]`` /
+    ``chunks["generated"]``, so ``summary()``, ``triangulate``, ``orientation`` and ``executions`` describe the first seed, exactly as a run
+    without ``seeds`` and the same ``seed`` does.  After the last batch ``gn_openloop_seed_spheres`` runs once (``seed_min_ratio``: a seed
+    found a sphere when its mass is at least this share of the true one) and, with a controller, ``gn_openloop_seed_actions`` twice
+    (normalised, radians); their outputs and the seed tables ride in the same device-to-host copy (``OpenLoopResult.seed_tables`` /
+    ``.seed_spheres`` / ``.seed_actions``, ``seed_summary()``).  It needs a diffusion agent and costs R generations per transition; with None
+    nothing changes: the same launches, the same tables, the same bits.
+
     Per batch, on the device: ``DeviceReplay.sample`` (the frames, proprioception, normalised action chunk, task tokens) -> ``gn_render_spheres``
     over the frames (``full``, ``occupied``) -> the four views on the 2x2 canvas -> the pipeline (``harness.make_prompt`` ids, one generator
     seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image, sphere and action scores -> the controller again on ``full`` -> its action
@@ -578,11 +700,11 @@ class OpenLoopEval:
     def __init__(self, diffusion_agent, controller, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None,
                  batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
                  change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None, triangulate: bool = False,
-                 tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6, orientation=None):
+                 tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6, orientation=None, seeds: Optional[int] = None, seed_min_ratio: float = 0.5):
         from .render import load_traj
 
         device, engine, T = self._check_options(diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions,
-                                                triangulate, tri_min_ratio, tri_min_det, orientation)
+                                                triangulate, tri_min_ratio, tri_min_det, orientation, seeds, seed_min_ratio)
         self.cfg, self.batch_size = render_cfg, int(batch_size)
         self.num_inference_steps, self.guidance_scale, self.seed = int(num_inference_steps), float(guidance_scale), int(seed)
         H, W = int(render_cfg.image_height), int(render_cfg.image_width)
@@ -606,7 +728,7 @@ class OpenLoopEval:
         self._upload(self._transition_tables(trajs, episodes), stats)
 
     def _check_options(self, diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions, triangulate,
-                       tri_min_ratio, tri_min_det, orientation):
+                       tri_min_ratio, tri_min_det, orientation, seeds=None, seed_min_ratio=0.5):
         """Part one of the setup, before any device work: every option checked and kept -> ``(device, engine, T)`` for the replay."""
         if controller is None:
             if diffusion_agent is None:
@@ -653,6 +775,15 @@ class OpenLoopEval:
             if diffusion_agent is None:
                 raise ValueError("OpenLoopEval: orientation reads the generated spheres; without a diffusion agent nothing is generated")
             self.orientation_angles, self.orientation_rot = orientation_candidates(**orient)  # on the host until _upload
+        self.seeds, self.seed_min_ratio = None, float(seed_min_ratio)
+        if seeds is not None:
+            if isinstance(seeds, bool) or not isinstance(seeds, (int, np.integer)) or not 2 <= int(seeds) <= MAX_SEEDS:
+                raise ValueError(f"OpenLoopEval: seeds is None or the number of generator seeds R, an integer in [2, {MAX_SEEDS}], got {seeds!r}")
+            if diffusion_agent is None:
+                raise ValueError("OpenLoopEval: seeds repeats the generation with other noise; without a diffusion agent nothing is generated")
+            if not self.seed_min_ratio >= 0.0:
+                raise ValueError(f"OpenLoopEval: seed_min_ratio = {seed_min_ratio} must be >= 0")
+            self.seeds = int(seeds)
         self.agent, self.controller, self.cameras, self.V, self.change_threshold = diffusion_agent, controller, tuple(cameras), len(cameras), int(change_threshold)
         if diffusion_agent is not None and self.V != 4:
             raise ValueError(f"OpenLoopEval: the 2x2 canvas takes exactly four cameras, got {self.V}")
@@ -770,11 +901,53 @@ class OpenLoopEval:
                 tabs["orientation"] = torch.zeros((N, self.V, int(self.windows.shape[2]), int(self.orientation_rot.shape[0]), 4), dtype=torch.int64, device=dev)
         if self.executions is not None:  # every scored chunk, as the controller's head wrote it
             tabs["chunks"] = {k: torch.zeros((N, T, self.A), dtype=torch.float16, device=dev) for k in ("generated", "oracle") if k in tabs}
+        if self.seeds is not None:
+            self._seed_tables(tabs)
         return tabs
 
+    def _seed_tables(self, tabs) -> None:
+        """With ``seeds=R``: the generated tables get a leading seed axis -- ``tabs["seed"]`` holds them whole, ``tabs["per_seed"][r]`` seed
+        r's slices under the names ``run_batch`` scores into -- and seed 0's slices take the place of the tables ``_tables`` made: the
+        existing names ARE the first seed."""
+        dev, N, T, R = self.E.device, self.N, self.T, self.seeds
+        whole = {"image": torch.zeros((R,) + tuple(tabs["image"].shape), dtype=torch.int64, device=dev),
+                 "spheres": torch.zeros((R,) + tuple(tabs["spheres"].shape), dtype=torch.int64, device=dev)}
+        if self.controller is not None:
+            whole["generated"] = {unit: torch.zeros((R, N, T, 2), dtype=torch.float32, device=dev) for unit in ("norm", "rad")}
+            whole["chunks"] = torch.zeros((R, N, T, self.A), dtype=torch.float16, device=dev)
+            whole["demo"] = torch.zeros((N, T, self.A), dtype=torch.float32, device=dev)
+        per = []
+        for r in range(R):
+            t = {"image": whole["image"][r], "spheres": whole["spheres"][r]}
+            if self.controller is not None:
+                t["generated"] = {unit: whole["generated"][unit][r] for unit in ("norm", "rad")}
+                t["chunks"] = {"generated": whole["chunks"][r]}
+            per.append(t)
+        if "orientation" in tabs:  # the orientation of the first seed's spheres only
+            per[0]["orientation"] = tabs["orientation"]
+        tabs["image"], tabs["spheres"] = per[0]["image"], per[0]["spheres"]
+        if self.controller is not None:
+            tabs["generated"] = per[0]["generated"]
+            if "chunks" in tabs:
+                tabs["chunks"]["generated"] = per[0]["chunks"]["generated"]
+        tabs["seed"], tabs["per_seed"] = whole, per
+
     def _keep_chunk(self, a_hat, tabs, kind: str, row0: int, n_valid: int):
-        if "chunks" in tabs:
+        if kind in tabs.get("chunks", {}):
             tabs["chunks"][kind][row0: row0 + n_valid].copy_(a_hat[:n_valid, : self.T, : self.A])
+
+    def seed_reductions(self, tabs):
+        """After the last batch, with ``seeds``: the two reductions over the seed axis -- one ``gn_openloop_seed_spheres`` launch over the
+        sphere tables and, with a controller, two ``gn_openloop_seed_actions`` launches over the chunks (normalised, then radians) ->
+        ``(f64 [N, V, S, 8], {"norm" | "rad": f32 [N, T, 4]} or None)`` on the device; nothing is read back."""
+        if self.seeds is None:
+            return None, None
+        whole = tabs["seed"]
+        spheres = self.E.openloop_seed_spheres(whole["spheres"], min_ratio=self.seed_min_ratio)
+        if self.controller is None:
+            return spheres, None
+        return spheres, {"norm": self.E.openloop_seed_actions(whole["chunks"], whole["demo"]),
+                         "rad": self.E.openloop_seed_actions(whole["chunks"], whole["demo"], joint_scale=self.joint_std)}
 
     def replay_executions(self, tabs) -> Optional[list]:
         """After the last batch: per setting and row kind, the executed action of every transition (``gn_openloop_exec_actions`` over the chunk
@@ -817,8 +990,28 @@ class OpenLoopEval:
         out[: d.shape[0]] = d
         return out.view(B * d.shape[1], d.shape[2], 2)
 
+    def _score_generated(self, batch, idx, generator, tabs, start: int, n_valid: int) -> None:
+        """Steps 4 - 6 for one generator: the pipeline, the controller on its image, and the image, sphere and action scores into ``tabs``."""
+        B = len(idx)
+        gen = self.generate(batch, idx, generator)
+        if self.controller is not None:
+            a_hat = self.controller.act_tiled(gen, batch["low_dim_state"], batch.get("lang_tokens"))
+        self.E.openloop_image_metrics(gen, batch["full"], batch["occupied"], tabs["image"], row0=start, n_valid=n_valid)
+        self.E.openloop_sphere_metrics(gen, batch["full"], batch["images_u8"].view(B * self.V, self.H, self.W, 3), batch["occupied"],
+                                       batch["windows"], tabs["spheres"], threshold=self.change_threshold, row0=start, n_valid=n_valid)
+        if "orientation" in tabs:
+            v = batch["views"]
+            self.E.openloop_orientation(gen, batch["full"], batch["occupied"], batch["windows"], v["cams"], v["spheres"], v["tex_index"], v["count"],
+                                        self.atlas, self.orientation_rot, tabs["orientation"], samples=self.samples,
+                                        shift=self.sphere_shifts(tabs["spheres"][start: start + n_valid], B), row0=start, n_valid=n_valid)
+        if self.controller is not None:
+            self._score_actions(a_hat, batch, tabs["generated"], start, n_valid)  # before the next pass overwrites the program's chunk
+            self._keep_chunk(a_hat, tabs, "generated", start, n_valid)
+
     def run_batch(self, start: int, tabs, generator) -> None:
-        """One evaluator batch: steps 1 - 7 for transitions ``start ..``, everything on the device, nothing read back."""
+        """One evaluator batch: steps 1 - 7 for transitions ``start ..``, everything on the device, nothing read back.  With ``seeds``,
+        ``generator`` is the list of the R generators: the targets are made once, steps 4 - 6 run per seed in order into that seed's tables
+        (seed 0's are ``tabs``' own, and only they carry an orientation table), and the oracle pass runs once."""
         if self.controller is not None:
             self._fresh_controller()
         idx = self.batch_indices(start)
@@ -826,21 +1019,14 @@ class OpenLoopEval:
         with torch.inference_mode():  # as harness.control_step runs the same two programs
             batch = self.targets(idx)
             B = len(idx)
-            if self.agent is not None:
-                gen = self.generate(batch, idx, generator)
+            if self.agent is not None and self.seeds is None:
+                self._score_generated(batch, idx, generator, tabs, start, n_valid)
+            elif self.agent is not None:
+                for r, g in enumerate(generator):
+                    # seed r's chunk leaves the program's output buffer (into its slice of the chunk table) before seed r + 1's act_tiled
+                    self._score_generated(batch, idx, g, tabs["per_seed"][r], start, n_valid)
                 if self.controller is not None:
-                    a_hat = self.controller.act_tiled(gen, batch["low_dim_state"], batch.get("lang_tokens"))
-                self.E.openloop_image_metrics(gen, batch["full"], batch["occupied"], tabs["image"], row0=start, n_valid=n_valid)
-                self.E.openloop_sphere_metrics(gen, batch["full"], batch["images_u8"].view(B * self.V, self.H, self.W, 3), batch["occupied"],
-                                               batch["windows"], tabs["spheres"], threshold=self.change_threshold, row0=start, n_valid=n_valid)
-                if "orientation" in tabs:
-                    v = batch["views"]
-                    self.E.openloop_orientation(gen, batch["full"], batch["occupied"], batch["windows"], v["cams"], v["spheres"], v["tex_index"], v["count"],
-                                                self.atlas, self.orientation_rot, tabs["orientation"], samples=self.samples,
-                                                shift=self.sphere_shifts(tabs["spheres"][start: start + n_valid], B), row0=start, n_valid=n_valid)
-                if self.controller is not None:
-                    self._score_actions(a_hat, batch, tabs["generated"], start, n_valid)  # before the oracle pass overwrites the program's chunk
-                    self._keep_chunk(a_hat, tabs, "generated", start, n_valid)
+                    tabs["seed"]["demo"][start: start + n_valid].copy_(batch["action"][:n_valid])
             if self.controller is not None:
                 a_hat = self._chunk(batch["full"].view(B, self.V, self.H, self.W, 3), batch)
                 self._score_actions(a_hat, batch, tabs["oracle"], start, n_valid)
@@ -849,21 +1035,39 @@ class OpenLoopEval:
     def run(self) -> OpenLoopResult:
         tabs = self._tables()
         generator = torch.Generator(device=self.E.device).manual_seed(self.seed) if self.agent is not None else None
+        if self.seeds is not None:  # one generator per seed, each advanced call by call as the one of a run with that seed is
+            generator = [torch.Generator(device=self.E.device).manual_seed(self.seed + r) for r in range(self.seeds)]
         for start in range(0, self.N, self.batch_size):
             self.run_batch(start, tabs, generator)
         dev = {"actions": {k: tabs[k] for k in ("generated", "oracle") if k in tabs}, "image": tabs.get("image"), "spheres": tabs.get("spheres"),
                "points": self.triangulate_spheres(tabs), "orientation": tabs.get("orientation"), "executions": self.replay_executions(tabs),
                "chunks": tabs.get("chunks")}
+        if self.seeds is not None:  # the first seed's tables travel once, inside the seed tables, and are sliced out of them on the host
+            dev["seed_spheres"], dev["seed_actions"] = self.seed_reductions(tabs)
+            dev["seed_tables"] = tabs["seed"]
+            dev["image"] = dev["spheres"] = None
+            dev["actions"] = {k: t for k, t in dev["actions"].items() if k != "generated"}
+            if dev["chunks"] is not None:
+                dev["chunks"] = {k: t for k, t in dev["chunks"].items() if k != "generated"}
         # the one device-to-host copy, after the last launch: every table by its name in the tree, as bytes of one buffer
         named: Dict[str, torch.Tensor] = {}
         _map_tensors(dev, named.__setitem__)
         copies = read_back(named)
         host = _map_tensors(dev, lambda name, t: copies[name])
+        extra = {}
+        if self.seeds is not None:
+            st = host["seed_tables"]
+            host["image"], host["spheres"] = st["image"][0], st["spheres"][0]
+            if "generated" in st:
+                host["actions"] = dict({"generated": {unit: t[0] for unit, t in st["generated"].items()}}, **host["actions"])
+                if host["chunks"] is not None:
+                    host["chunks"] = dict({"generated": st["chunks"][0]}, **host["chunks"])
+            extra = dict(seeds=[self.seed + r for r in range(self.seeds)], seed_tables=st, seed_spheres=host["seed_spheres"], seed_actions=host["seed_actions"])
         return OpenLoopResult(host["image"], host["actions"], self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1,
                               self.H, self.W, spheres=host["spheres"], windows=self.windows_host if host["spheres"] is not None else None,
                               executions=host["executions"], chunks=host["chunks"], points=host["points"], point_slots=self.point_slots_host,
                               point_centres=self.point_centres_host, cams=self.cams_host, orientation=host["orientation"],
-                              orientation_angles=self.orientation_angles if host["orientation"] is not None else None)
+                              orientation_angles=self.orientation_angles if host["orientation"] is not None else None, **extra)
 
 
 def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None,
@@ -904,7 +1108,7 @@ VALIDATION_JSONL = "validation.jsonl"
 
 def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, out_dir=None, tokenizer=None, batch_size: int = 8,
                         num_inference_steps: int = 5, seed: int = 0, engine=None, triangulate: bool = False, tri_min_ratio: float = 0.5,
-                        tri_min_det: float = 1e-6, orientation=None):
+                        tri_min_det: float = 1e-6, orientation=None, seeds: Optional[int] = None, seed_min_ratio: float = 0.5):
     """-> a ``validate(global_step)`` callable for ``train_loop.TrainLoop``: each call wraps ``make_pipe()`` (for instance
     ``validation.validation_pipeline(..., trainer, "euler_discrete")`` over the trainer's current weights) as the agent of a diffusion-only
     ``OpenLoopEval`` on held-out demos and returns ``{"step", "select", "found_rate", "shift_px", "mass_ratio", "spread_ratio", "colour_l1",
@@ -918,7 +1122,12 @@ def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CA
     ``tri_min_det`` are the evaluator's and are read only with it.  ``select`` stays what it is.
 
     ``orientation``: the evaluator's option (None, K or a dict); the dict then gains ``orient_err_deg``, the mean orientation error of the
-    scored spheres (``orientation_summary()["overall"]["err_deg"]``; None where none was scored)."""
+    scored spheres (``orientation_summary()["overall"]["err_deg"]``; None where none was scored).
+
+    ``seeds``: the evaluator's option (None or R); ``select`` and every other field stay the FIRST seed's numbers, so lines with and without
+    the option rank alike, and the dict gains ``select_mean`` and ``select_std`` (``seed_summary()["scores"]["select"]``: the mean over the
+    seeds and the seed-to-seed standard deviation, the noise floor a difference between two lines has to beat) and ``variance_share``
+    (``seed_summary()["spheres"]["overall"]``: 0 all bias, 1 all noise).  ``seed_min_ratio`` is the evaluator's and is read only with it."""
     import types
 
     state: Dict = {}
@@ -927,6 +1136,8 @@ def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CA
     tri = dict(triangulate=True, tri_min_ratio=tri_min_ratio, tri_min_det=tri_min_det) if triangulate else {}
     if orientation is not None:  # likewise: only when it is on
         tri["orientation"] = orientation
+    if seeds is not None:  # likewise
+        tri.update(seeds=seeds, seed_min_ratio=seed_min_ratio)
 
     def validate(global_step: int) -> Dict:
         agent = types.SimpleNamespace(pipe=make_pipe())
@@ -936,16 +1147,16 @@ def diffusion_validator(make_pipe, episodes, cameras: Sequence[str] = DEFAULT_CA
                                             num_inference_steps=num_inference_steps, seed=seed, engine=engine, **tri)
         ev.agent = agent
         res = ev.run()
-        im = res.summary()["image"]
-        sp = im["spheres"]
-        line = {"step": int(global_step), "select": sp["score"], "found_rate": sp["overall"]["found_rate"], "shift_px": sp["overall"]["shift_px"],
-                "mass_ratio": sp["overall"]["mass_ratio"], "spread_ratio": sp["overall"]["spread_ratio"], "colour_l1": sp["overall"]["colour_l1"],
-                "sphere_rmse": _mean(res.sphere_rmse()), "background_rmse": _mean(res.background_rmse()), "wrapped_mse": im["wrapped_mse"], "n": len(res)}
+        line = dict({"step": int(global_step)}, **res.validator_scalars(), n=len(res))
         if triangulate:
             s3 = res.triangulation_summary()
             line.update(err_3d_mm=s3["generated"]["err_mm"], excess_mm=s3["excess_mm"])
         if orientation is not None:
             line.update(orient_err_deg=res.orientation_summary()["overall"]["err_deg"])
+        if seeds is not None:
+            ss = res.seed_summary()
+            line.update(select_mean=ss["scores"]["select"]["mean"], select_std=ss["scores"]["select"]["std"],
+                        variance_share=ss["spheres"]["overall"]["variance_share"])
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, VALIDATION_JSONL), "a") as f:

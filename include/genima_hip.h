@@ -1011,6 +1011,46 @@ int32_t gn_openloop_triangulate(gn_ctx* ctx, const uint64_t* sph, const int32_t*
                                 const int32_t* slot_host, const int32_t* win_host, double* out, double min_ratio, double min_det, int32_t N, int32_t V,
                                 int32_t S, int32_t G);
 
+/* The seed axis of an open-loop evaluation: a run repeated with R generator seeds keeps its sphere table and its chunks per seed, and these two
+ * reduce over that axis -- how much of a score is the checkpoint and how much the noise draw.  One launch each over the finished tables of a
+ * run; all pointers are device memory.
+ *
+ * gn_openloop_seed_spheres, per (transition n, view v, sphere s), one thread each, everything in f64:
+ *   sph       uint64 [R][N][V][S][17], 8-byte aligned: gn_openloop_sphere_metrics' table per seed.  gen_m, sx, sy are columns 1..3 of seed r;
+ *             gt_m, tx, ty columns 5..7, the same for every seed: seed 0's are read
+ *   found     seed r is found when gen_m > 0, gt_m > 0 and gen_m >= min_ratio * gt_m (gn_openloop_triangulate's rule for the generated image)
+ *   ct = (tx / gt_m, ty / gt_m), the true centroid;  c_r = (sx / gen_m, sy / gen_m), seed r's;  q_r = gen_m / gt_m
+ *   out       f64 [N][V][S][8], 8-byte aligned, sums over the found seeds in seed order r = 0 .. R - 1:
+ *     [0]     k, the number of found seeds
+ *     [1], [2]  the bias m - ct, m = (sum c_r) / k
+ *     [3]     the spread (sum |c_r - m|^2) / k, from a second pass over the seeds (not from sum x^2 - (sum x)^2 / k)
+ *     [4]     (sum |c_r - ct|^2) / k, the mean squared shift;  |d|^2 = d.x d.x + d.y d.y
+ *     [5]     the mean of q_r, (sum q_r) / k
+ *     [6]     the population variance of q_r, (sum (q_r - [5])^2) / k, from the second pass too
+ *     [7]     max over r of |c_r - ct|^2
+ *   With k = 0 (a hidden sphere, or no seed found it) [1..7] are NaN and [0] is still written.
+ *   Refused, launching nothing and leaving out as it was: a NULL or misaligned pointer, R outside [1, 64], N < 0, V outside [2, 8], S outside
+ *   [1, 8], N * V * S * 17 >= 2^31, min_ratio < 0 or NaN.  N == 0 is accepted and does nothing.
+ *
+ * gn_openloop_seed_actions, per (transition n, chunk position t), one thread each, everything in f32:
+ *   chunks    f16 [R][N][T][ld], ld >= A the row pitch, only the first A columns are read: the chunk each seed's image made the controller predict
+ *   demo      f32 [N][T][A]: the normalised demo chunk;  joint_scale f32 [A - 1] or NULL (= 1)
+ *   inv_R     (float)(1.0 / R), rounded once on the host (any other value is refused)
+ *   With a_r[j] seed r's value widened to f32 and mean_j = (sum_r a_r[j]) * inv_R, the sum added in seed order:
+ *   out       f32 [N][T][4]:
+ *     [0] = sum over j < A - 1 of joint_scale[j] * |mean_j - demo[j]|: the error of the SEED-MEAN chunk, summed as gn_openloop_action_metrics
+ *           sums its terms (one subtraction, one multiplication, one addition per term, in index order)
+ *     [1] = 1.0 where (mean_{A-1} > 0) == (demo[A - 1] > 0.5), else 0.0: that kernel's gripper rule on the mean logit
+ *     [2] = sum over j < A - 1 of joint_scale[j] * ((sum_r |a_r[j] - mean_j|) * inv_R): the mean absolute deviation across the seeds
+ *     [3] = (sum_r e_r) * inv_R in seed order, e_r = seed r's own [0] of gn_openloop_action_metrics, computed with that kernel's operations in
+ *           its order: bit for bit the f32 seed-order mean of that kernel's output over the same chunks
+ *   Refused, launching nothing and leaving out as it was: a NULL pointer other than joint_scale, R outside [1, 64], N or T <= 0, A < 2, ld < A,
+ *   N * T > 2^24, R * N * T * ld >= 2^31, inv_R other than (float)(1.0 / R), a misaligned pointer.
+ * Both: plain loads and stores, no atomics, no zeroing pass, no fused multiply-add, no sqrt and no exp: every run gives the same bits.  Eager only. */
+int32_t gn_openloop_seed_spheres(gn_ctx* ctx, const uint64_t* sph, double* out, double min_ratio, int32_t R, int32_t N, int32_t V, int32_t S);
+int32_t gn_openloop_seed_actions(gn_ctx* ctx, const void* chunks, int32_t ld, const float* demo, const float* joint_scale, float* out, float inv_R,
+                                 int32_t R, int32_t N, int32_t T, int32_t A);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */

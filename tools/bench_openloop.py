@@ -25,9 +25,15 @@ With ``--orientation`` it times whole runs of two evaluators that alternate in t
 -- and reports both per transition, the difference as a share of the run without it, and the ``gn_openloop_orientation`` launch over one
 batch at K = 37 by device events (the shifts are those of the batch's own sphere table).
 
+With ``--seeds R`` it times whole runs of two evaluators that alternate in the same way -- one without and one with ``seeds=R`` -- and
+reports both per transition, their ratio (the expectation: about R generations beside one, less the work done once per batch -- the targets
+and the oracle pass), the bytes the seed tables add to the final copy, and the two new launches over the finished tables of a whole run by
+device events (``gn_openloop_seed_spheres``, ``gn_openloop_seed_actions`` with the joint scale).  There is no target: the cost is R
+generations and is the user's to choose.
+
 Prints one JSON line; needs an MI355X.
 
-    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid] [--triangulate] [--orientation]
+    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid] [--triangulate] [--orientation] [--seeds R]
         [--sphere_textures tests/golden/sphere_textures] [--out profiles/openloop_b8.json]
 """
 import argparse
@@ -58,6 +64,7 @@ def main():
     ap.add_argument("--exec_grid", action="store_true", help="also time whole runs without and with the 8-setting execution grid, and the two replay launches")
     ap.add_argument("--triangulate", action="store_true", help="also time whole runs without and with triangulate=True, and the triangulation launch")
     ap.add_argument("--orientation", action="store_true", help="also time whole runs without and with orientation=37, and the orientation launch")
+    ap.add_argument("--seeds", type=int, default=None, metavar="R", help="also time whole runs without and with seeds=R, and the two seed-axis launches")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -222,6 +229,37 @@ def main():
                                                                     v["tex_index"], v["count"], ev.atlas, ev_ori.orientation_rot, ot["orientation"],
                                                                     samples=ev.samples, shift=o_shift)
         launches["sphere_shifts_us"] = lambda: ev_ori.sphere_shifts(ot["spheres"][:B], B)
+    if args.seeds is not None:
+        ev_seeds = OpenLoopEval(dagent, controller, eps, cams, render_cfg=rcfg, stats=(P.action_stats(demos), P.proprio_stats(demos)), tokenizer=tokens,
+                                batch_size=B, engine=E, seeds=args.seeds)
+        runs = {"run_without_seeds": ev.run, "run_with_seeds": ev_seeds.run}
+        rms = {k: [] for k in runs}
+        for i in range(args.warmup + args.reps):
+            for k, fn in runs.items():
+                E.synchronize()
+                t = time.perf_counter()
+                fn()  # ends in its device-to-host copy
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    rms[k].append((time.perf_counter() - t) * 1e3)
+        for k in runs:
+            res[k] = stats(rms[k])
+            res[k + "_ms_per_transition"] = round(res[k]["median_ms"] / ev.N, 4)
+        res["seeds"] = int(args.seeds)
+        res["seeds_over_plain"] = round(res["run_with_seeds"]["median_ms"] / res["run_without_seeds"]["median_ms"], 4)
+        res["run_without_seeds_spread_ms"] = round(res["run_without_seeds"]["max_ms"] - res["run_without_seeds"]["min_ms"], 4)
+        st = ev_seeds._tables()
+        gens = [torch.Generator(device="cuda").manual_seed(r) for r in range(args.seeds)]
+        for start in range(0, ev_seeds.N, B):  # every batch: the launches below are timed over the finished tables of a whole run
+            ev_seeds.run_batch(start, st, gens)
+        s_sph, s_act = ev_seeds.seed_reductions(st)
+        whole = st["seed"]
+        plain_bytes = sum(t.numel() * t.element_size() for t in [st["image"], st["spheres"]] + list(st["generated"].values()))
+        seed_bytes = sum(t.numel() * t.element_size() for t in [whole["image"], whole["spheres"], whole["chunks"], whole["demo"], s_sph]
+                         + list(whole["generated"].values()) + list(s_act.values()))
+        res["seeds_extra_copy_bytes"] = int(seed_bytes - plain_bytes)
+        launches["seed_spheres_us"] = lambda: E.openloop_seed_spheres(whole["spheres"], s_sph, min_ratio=ev_seeds.seed_min_ratio)
+        launches["seed_actions_us"] = lambda: E.openloop_seed_actions(whole["chunks"], whole["demo"], s_act["rad"], joint_scale=ev_seeds.joint_std)
     for name, launch in launches.items():
         us = []
         for _ in range(5):

@@ -22,6 +22,12 @@ method (``OpenLoopResult.triangulation_summary``; ``--tri_min_ratio`` / ``--tri_
 rotations about its own z axis over ``span`` degrees (default 180) and compared with the generated window (``gn_openloop_orientation``); under
 ``orientation`` the summary then carries the angular error, its contrast and ``floor_deg``, the same read-out of the ground-truth render,
 which is 0 (``OpenLoopResult.orientation_summary``).
+``--seeds R`` (2 .. 64) repeats the generation with the generator seeds ``--seed``, ``--seed`` + 1, ... and adds, under ``seeds``, every score
+per seed with its mean and seed-to-seed standard deviation -- the noise floor a difference between two checkpoints has to beat --, per sphere
+the bias of the seeds' mean centroid beside their spread about it (``variance_share``: 0 all bias, 1 all noise) and, with a controller, the
+error of the seed-averaged chunk beside the mean of the seeds' errors (``gain``; ``OpenLoopResult.seed_summary``).  Everything outside that
+block stays the first seed's, as without the option; the run costs R generations per transition.  A seed spread is not a success rate either,
+and ``gain`` is teacher-forced: nothing executes an averaged chunk.
 Open-loop error is not a success rate: every chunk is predicted from a demo state, nothing is executed and no error compounds."""
 import argparse
 import json
@@ -63,6 +69,9 @@ def parse(argv=None):
     ap.add_argument("--tri_min_det", type=float, default=1e-6, help="rays that cross worse than this (det(A) / (trace(A) / 3)^3) are left unsolved")
     ap.add_argument("--orientation", default=None, metavar="K[,span]",
                     help="also read the orientation the generated spheres show: K (odd, at most 64) candidate rotations over span degrees (default 180)")
+    ap.add_argument("--seeds", type=int, default=None, metavar="R",
+                    help="also repeat the generation with R (2 .. 64) generator seeds, --seed .. --seed + R - 1: per-score seed spread, per-sphere bias and spread")
+    ap.add_argument("--seed_min_ratio", type=float, default=0.5, help="with --seeds: a seed found a sphere when its mass is at least this share of the ground truth's")
     ap.add_argument("--out", default="openloop.json")
     a = ap.parse_args(argv)
     if not a.no_controller and not (a.controller_snapshot and a.stats_dir):
@@ -76,6 +85,8 @@ def parse(argv=None):
             a.execution = [parse_execution(e) for e in a.execution]
         except ValueError as err:
             ap.error(str(err))
+    if a.seeds is not None and not 2 <= a.seeds <= 64:
+        ap.error(f"--seeds {a.seeds}: the number of generator seeds must lie in [2, 64]")
     if a.orientation is not None:
         from genima_amd.openloop import orientation_candidates, parse_orientation
 
@@ -124,7 +135,7 @@ def main(argv=None):
     ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=stats, tokenizer=tokenizer, batch_size=a.batch_size,
                       num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed, change_threshold=a.change_threshold,
                       action_sequence=a.action_sequence, executions=a.execution, triangulate=a.triangulate, tri_min_ratio=a.tri_min_ratio,
-                      tri_min_det=a.tri_min_det, orientation=a.orientation)
+                      tri_min_det=a.tri_min_det, orientation=a.orientation, seeds=a.seeds, seed_min_ratio=a.seed_min_ratio)
     print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
     summary = ev.run().to_json(a.out)
     print(json.dumps(summary, indent=1))
