@@ -25,6 +25,11 @@ class GenimaHipError(RuntimeError):
     pass
 
 
+def round_up(x: int, m: int) -> int:
+    """x rounded up to a multiple of m (padded leading dimensions, workspace sizes, flat-buffer offsets)."""
+    return (x + m - 1) // m * m
+
+
 class StatsSink(C.Structure):
     """gn_stats_sink: the producer side of the GroupNorm bridge (include/genima_hip.h)."""
     _fields_ = [("stats", C.c_void_p), ("cpg", C.c_int32), ("coff", C.c_int32), ("groups", C.c_int32), ("rows_per_sample", C.c_int32),

@@ -30,9 +30,10 @@ import torch
 
 from . import graphs, packing
 from . import train_ops as T
-from ._lib import ACT_NONE, ACT_RELU
+from ._lib import ACT_NONE, ACT_RELU, round_up
 from .act import IMAGENET_MEAN, IMAGENET_STD, _RESNET18, act_schema, pack_act, sine_pos_embed
 from .engine import Engine
+from .loss_scaler import LossScaler
 from .training import FrozenParams, Graph, TrainParams, Var
 
 F16, F32 = torch.float16, torch.float32
@@ -75,10 +76,6 @@ def sinusoid_table(n: int, d: int) -> torch.Tensor:
     return torch.where((torch.arange(d) % 2 == 0)[None], ang.sin(), ang.cos()).float()
 
 
-def _rup(x, m):
-    return (x + m - 1) // m * m
-
-
 _M64 = 2 ** 64 - 1
 
 
@@ -113,7 +110,8 @@ class ACTTrainer:
             raise ValueError(f"ACTTrainer: attn_dropout must be in [0, 1), got {attn_dropout!r}")
         self.E, self.cfg, self.clip_cfg, self.clip_W = E, dict(cfg), clip_cfg, clip_W
         self.lr, self.lr_backbone, self.wd, self.betas, self.eps = lr, lr_backbone, weight_decay, betas, eps
-        self.loss_scale, self.p_drop, self.p_state = float(loss_scale), dropout, state_dropout
+        self.scaler = LossScaler(loss_scale)  # read back synchronously; growth_interval None: the scale only ever halves
+        self.p_drop, self.p_state = dropout, state_dropout
         self.p_attn, self.seed, self.last_attn_seeds = float(attn_dropout), int(seed), []
         sch = act_train_schema(cfg)
         sd = {k: state_dict[k].detach().float() for k in sch}
@@ -126,7 +124,7 @@ class ACTTrainer:
                 n = 1
                 for s_ in shape:
                     n *= s_
-                self.n_backbone = max(self.n_backbone, _rup(off + n, 8))
+                self.n_backbone = max(self.n_backbone, round_up(off + n, 8))
         self._alias_mha()
         # frozen part: conv1 / layer1 with their BatchNorms folded (the inference packing), and every other BatchNorm as an affine
         self.frozen = FrozenParams(E, pack_act({k: v for k, v in sd.items() if k in act_schema(cfg)}, E.device))
@@ -139,12 +137,28 @@ class ACTTrainer:
                 shift = sd[p + ".bias"] - sd[p + ".running_mean"] * scale
                 self.bn[p] = ((scale - 1.0).to(F16)[None].contiguous().to(dev), shift.to(F16)[None].contiguous().to(dev))
         self._gen = torch.Generator(device=dev).manual_seed(seed)
-        self.opt_step, self._ss, self._clip, self.last = 0, torch.zeros(1, dtype=F32, device=dev), torch.zeros(3, dtype=F32, device=dev), {}
+        self._ss, self._clip, self.last = torch.zeros(1, dtype=F32, device=dev), torch.zeros(3, dtype=F32, device=dev), {}
         mean, std = torch.tensor(IMAGENET_MEAN), torch.tensor(IMAGENET_STD)
         g8, b8 = torch.zeros(1, 8), torch.zeros(1, 8)
         g8[0, :3], b8[0, :3] = 1.0 / std - 1.0, -mean / std
         g8[0, 3:] = -1.0  # padded channels stay exactly 0
         self._norm = (g8.to(F16).to(dev), b8.to(F16).to(dev))
+
+    @property
+    def loss_scale(self) -> float:
+        return self.scaler.scale
+
+    @loss_scale.setter
+    def loss_scale(self, value):
+        self.scaler.scale = value
+
+    @property
+    def opt_step(self) -> int:
+        return self.scaler.opt_step
+
+    @opt_step.setter
+    def opt_step(self, value):
+        self.scaler.opt_step = value
 
     def _alias_mha(self):
         """``in_proj_weight`` [3d, d] is ONE parameter: q | k (fused), v, q, k are row ranges of it -- views into the flat buffers."""
@@ -258,10 +272,10 @@ class ACTTrainer:
         d, Tq, L, A = cfg["hidden_dim"], cfg["num_queries"], cfg["latent_dim"], cfg["action_dim"]
         acts = actions[:, :Tq].to(dev, F32).contiguous()
         # ---- CVAE posterior: [CLS, proj(qpos), proj(actions)] + sinusoid table -> encoder -> latent_proj -> (mu, logvar) -> z
-        Sp, Sv = _rup(Tq + 2, 8), Tq + 2
-        qp16 = torch.zeros((B, _rup(cfg["state_dim"], 8)), dtype=F16, device=dev)
+        Sp, Sv = round_up(Tq + 2, 8), Tq + 2
+        qp16 = torch.zeros((B, round_up(cfg["state_dim"], 8)), dtype=F16, device=dev)
         qp16[:, : qpos.shape[1]] = qpos.to(dev)
-        a16 = torch.zeros((B, Tq, _rup(A, 8)), dtype=F16, device=dev)
+        a16 = torch.zeros((B, Tq, round_up(A, 8)), dtype=F16, device=dev)
         a16[..., :A] = acts
         cls = net.W["cls_embed.weight"].view(1, 1, d).expand(B, 1, d).contiguous()
 
@@ -283,7 +297,7 @@ class ACTTrainer:
             eps = torch.randn((B, L), generator=self._gen, device=dev, dtype=F32)
         eps = eps.to(dev, F32).contiguous()
         kl_w = float(cfg.get("kl_weight", 10.0))
-        z = T.cvae_sample(E, info.t, eps, L, _rup(L, 8))
+        z = T.cvae_sample(E, info.t, eps, L, round_up(L, 8))
         z_v = g.custom(z, True, lambda dz: g.acc(info, T.cvae_bwd(E, info.t, eps, dz.contiguous(), L, self.loss_scale * kl_w / B)))
         # ---- image encoder: frozen conv1 / maxpool / layer1, trainable layer2..4 with FiLM
         Fz = self.frozen.W
@@ -302,7 +316,7 @@ class ACTTrainer:
         lang = bool(cfg.get("use_lang_cond")) and task_emb is not None
         task_v = None
         if lang:
-            t16 = torch.zeros((B, _rup(cfg["lang_dim"], 8)), dtype=F16, device=dev)
+            t16 = torch.zeros((B, round_up(cfg["lang_dim"], 8)), dtype=F16, device=dev)
             t16[:, : task_emb.shape[1]] = task_emb.to(dev)
             task_v = Var(t16, needs=False)
         for j, (li, c, stride) in enumerate(_RESNET18[1:]):
@@ -329,7 +343,7 @@ class ACTTrainer:
             extra.append(g.linear(net, task_v, "task_proj.weight", "task_proj.bias").view(B, 1, d))
         n_extra = len(extra)
         N = n_extra + n_img
-        Np = _rup(N, 8)
+        Np = round_up(N, 8)
         src = self._tokens(g, extra + [img_v], Np)
         pos = torch.zeros((B, Np, d), dtype=F16, device=dev)
         pos_img = sine_pos_embed(fh, fw, d).repeat(1, V, 1).reshape(n_img, d)
@@ -343,7 +357,7 @@ class ACTTrainer:
             src = self._enc_layer(g, f"transformer.encoder.layers.{i}", src, pos_v, N)
         memory = src
         mem_pos = g.add(memory, pos_v)
-        Tp = _rup(Tq, 8)
+        Tp = round_up(Tq, 8)
         qe = torch.zeros((B, Tp, d), dtype=F16, device=dev)
         qe[:, :Tq] = net.W["query_embed.weight"][None]
 
@@ -381,13 +395,9 @@ class ACTTrainer:
         cn.sync_half()
         self._alias_mha()
         cn.zero_grad()
-        coef, norm, bad = self._clip.tolist()
-        self.last["grad_norm"] = norm
-        if bad:
-            self.loss_scale *= 0.5
-            self.opt_step -= 1
-            return False
-        return True
+        applied = self.scaler.update(self._clip)
+        self.last["grad_norm"] = self.scaler.grad_norm
+        return applied
 
     def update(self, images, qpos, task_emb, actions, eps=None) -> Dict[str, float]:
         out4 = self.forward_backward(images, qpos, task_emb, actions, eps)

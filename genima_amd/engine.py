@@ -24,17 +24,13 @@ import torch
 from . import _lib
 from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, GEMM_DMA, GEMM_PP, GEMM_PPP, GEMM_RING,
                    OUT_BATCH_TRANSPOSED, OUT_ROWMAJOR, TBLOCK_FRONT, TBLOCK_MID,
-                   TBLOCK_TAIL, AttnDesc, ConvGnDesc, ConvPatchDesc, GemmDesc, GenimaHipError, GroupNormDesc, NormOut, StatsSink, TBlockDesc, TBlockTapeSrc, attn_dropout_desc, check)
+                   TBLOCK_TAIL, AttnDesc, ConvGnDesc, ConvPatchDesc, GemmDesc, GenimaHipError, GroupNormDesc, NormOut, StatsSink, TBlockDesc, TBlockTapeSrc, attn_dropout_desc, check, round_up)
 
 F16 = torch.float16
 
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
-
-
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 # ---- the checks the eager data and scoring ops share (gather_u8_to_f16 .. render_spheres)
@@ -275,6 +271,22 @@ class Engine:
     def use_stream(self, stream: torch.cuda.Stream):
         self.stream = stream
         check(self.lib.gn_ctx_set_stream(self._ctx, C.c_void_p(stream.cuda_stream)), "gn_ctx_set_stream")
+
+    @contextlib.contextmanager
+    def on_stream(self, stream: torch.cuda.Stream, tag=False):
+        """Issue the enclosed launches on ``stream``: the engine's stream and torch's current stream (temporaries then come from that stream's
+        allocator pool) are switched to it, ``tag`` names the split-K / GroupNorm workspace to use (``_workspace``: streams that run
+        concurrently must not share one); all of it is put back on the way out, also when the body raises.  Ordering against other streams
+        (wait_stream, record_stream) stays with the caller."""
+        was = self.stream, getattr(self, "_on_side", False)
+        self.use_stream(stream)
+        self._on_side = tag
+        try:
+            with torch.cuda.stream(stream):
+                yield
+        finally:
+            self.use_stream(was[0])
+            self._on_side = was[1]
 
     class _Scope:
         def __init__(self, eng, name):
@@ -683,7 +695,7 @@ class Engine:
 
     def _workspace(self, nbytes: int) -> torch.Tensor:
         """f32 split-K / GroupNorm scratch: one shared grow-only buffer per stream (ops on one stream run in order)."""
-        n = _round_up(nbytes, 256) // 4
+        n = round_up(nbytes, 256) // 4
         # one buffer per stream: `_on_side` is False (the main stream), True (a recorded program's side stream) or a tag naming one of the
         # trainer's extra streams -- they run CONCURRENTLY with each other (the next step's front starts under the previous step's backward)
         side = getattr(self, "_on_side", False)
@@ -816,7 +828,7 @@ class Engine:
         if split_n:
             assert not transposed_out and rows_per_batch > 0 and M % rows_per_batch == 0 and 0 < split_n < N
             nb = M // rows_per_batch
-            ld2 = pad_cols if pad_cols else _round_up(rows_per_batch, 64)
+            ld2 = pad_cols if pad_cols else round_up(rows_per_batch, 64)
             if out is None:
                 out = self.buf(name, tuple(x.shape[:-1]) + (split_n,))
             if out2 is None:
@@ -826,7 +838,7 @@ class Engine:
         elif transposed_out:
             assert rows_per_batch > 0 and M % rows_per_batch == 0
             nb = M // rows_per_batch
-            ld = pad_cols if pad_cols else _round_up(rows_per_batch, 64)
+            ld = pad_cols if pad_cols else round_up(rows_per_batch, 64)
             if out is None:
                 out = self.buf(name, (nb, N, ld), zero=ld != rows_per_batch)  # only pad columns need the zeros
             d.out_mode, d.ldo, d.rows_per_batch = OUT_BATCH_TRANSPOSED, ld, rows_per_batch
@@ -874,7 +886,7 @@ class Engine:
         Cc = x.shape[-1]
         M = x.numel() // Cc
         nb = M // rows_per_batch
-        ld = _round_up(rows_per_batch, 64)
+        ld = round_up(rows_per_batch, 64)
         h = self.buf(name, x.shape)
         qk = self.buf(None if name is None else name + ".qk", tuple(x.shape[:-1]) + (2 * Cc,))
         vt = self.buf(None if name is None else name + ".vt", (nb, Cc, ld), zero=ld != rows_per_batch)
@@ -942,9 +954,9 @@ class Engine:
         Activations: per-token scales; a weight [N, K]: per-output-channel scales (quantise once, keep)."""
         K = x.shape[-1]
         rows = x.numel() // K
-        Kp = _round_up(K, 16)
+        Kp = round_up(K, 16)
         q = self.buf(None if name is None else name + ".q", tuple(x.shape[:-1]) + (Kp,), dtype=torch.uint8)
-        s = self.buf(None if name is None else name + ".s", (_round_up(rows, 4),), dtype=torch.float32)
+        s = self.buf(None if name is None else name + ".s", (round_up(rows, 4),), dtype=torch.float32)
         if self.record:
             raise GenimaHipError("quantize_fp8 is an eager op (the fp8 Linear serves the training forward, which is not recorded)")
         self._small("quantize_fp8_rows", (x, q, s), _ptr(x), x.stride(-2) if x.dim() > 1 else K, rows, K, _ptr(q), Kp, _ptr(s))
@@ -1064,7 +1076,7 @@ class Engine:
         assert w.dim() == 4 and w.is_cuda and w.dtype in (torch.float32, torch.float16) and not self.record
         w = w.contiguous()
         O, I, KH, KW = w.shape
-        out = torch.empty((_round_up(O, 8), KH * KW * _round_up(I, 8)), dtype=F16, device=self.device)
+        out = torch.empty((round_up(O, 8), KH * KW * round_up(I, 8)), dtype=F16, device=self.device)
         check(self.lib.gn_pack_conv_weight(self._ctx, _ptr(w), int(w.dtype == torch.float16), _ptr(out), O, I, KH, KW), "gn_pack_conv_weight")
         return out
 

@@ -18,12 +18,8 @@ import os
 
 import torch
 
-from ._lib import ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, ACT_TANH3
+from ._lib import ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, ACT_TANH3, round_up
 from .engine import Engine, Norm
-
-
-def _rup(x, m):
-    return (x + m - 1) // m * m
 
 
 def _heads(cfg, i):
@@ -160,7 +156,7 @@ def emit_cross_kv(E: Engine, W, ctx: torch.Tensor, tag: str) -> Dict[str, Tuple[
             o, c = offs[q]
             kv[q] = (allkv[:, :, o:o + c], allkv[:, :, o + c:o + 2 * c], True)
         return kv
-    pad = _rup(L, 64)
+    pad = round_up(L, 64)
     with E.zero_pool(sum(B * W[p + ".to_v.weight"].shape[0] * pad + 64 for p in sites) if pad != L else 0):  # (eager engines: one fill for all V^T)
         for p in sites:
             with E.scope(tag + "/" + p):
@@ -225,7 +221,7 @@ def emit_transformer(E: Engine, W, p: str, x, kv, heads: int, groups: int):
                 if fold and vrow:
                     qkv = E.linear(h, fold[0], fold[2], ln_c1=fold[1], name="qkv")
                 elif fold:
-                    qk, vt = E.linear(h, fold[0], fold[2], ln_c1=fold[1], split_n=2 * Cc, rows_per_batch=N, pad_cols=_rup(N, 64), name="qk")
+                    qk, vt = E.linear(h, fold[0], fold[2], ln_c1=fold[1], split_n=2 * Cc, rows_per_batch=N, pad_cols=round_up(N, 64), name="qk")
                 else:
                     n = E.layernorm(h, W[b + ".norm1.weight"], W[b + ".norm1.bias"], name="ln1")
                     if vrow:
@@ -233,10 +229,10 @@ def emit_transformer(E: Engine, W, p: str, x, kv, heads: int, groups: int):
                     elif b + ".attn1.to_qkv.weight" in W and not (E._fp8_weights and b + ".attn1.to_qk.weight" in W):
                         # q | k | v in one two-destination launch (q, k row-major + V^T); with Linears routed to the fp8 MFMA the
                         # registered copies are to_qk / to_v (the two-destination epilogue has no fp8 form)
-                        qk, vt = E.linear(n, W[b + ".attn1.to_qkv.weight"], split_n=2 * Cc, rows_per_batch=N, pad_cols=_rup(N, 64), name="qk")
+                        qk, vt = E.linear(n, W[b + ".attn1.to_qkv.weight"], split_n=2 * Cc, rows_per_batch=N, pad_cols=round_up(N, 64), name="qk")
                     else:
                         qk = E.linear(n, W[b + ".attn1.to_qk.weight"], name="qk")
-                        vt = E.linear(n, W[b + ".attn1.to_v.weight"], transposed_out=True, rows_per_batch=N, pad_cols=_rup(N, 64), name="vt")
+                        vt = E.linear(n, W[b + ".attn1.to_v.weight"], transposed_out=True, rows_per_batch=N, pad_cols=round_up(N, 64), name="vt")
                 if vrow:
                     a = E.attention(qkv[:, :, :Cc], qkv[:, :, Cc:2 * Cc], qkv[:, :, 2 * Cc:], heads, v_rowmajor=True, name="sa")
                 else:
@@ -419,7 +415,7 @@ def _emit_vae_attention(E: Engine, W, p: str, x, groups: int):
         h = E.groupnorm(x, W[p + ".group_norm.weight"], W[p + ".group_norm.bias"], groups, _vae_eps(W), name="gn").view(B, N, Cc)
         q = E.linear(h, W[p + ".to_q.weight"], W[p + ".to_q.bias"], name="q")
         k = E.linear(h, W[p + ".to_k.weight"], W[p + ".to_k.bias"], name="k")
-        Np = _rup(N, 64)
+        Np = round_up(N, 64)
         vt = E.linear(h, W[p + ".to_v.weight"], W[p + ".to_v.bias"], transposed_out=True, rows_per_batch=N, pad_cols=Np, name="vt")
         a = E.buf("a", (B, N, Cc))
         s = E.buf("s", (N, Np), zero=True)
@@ -562,7 +558,7 @@ def emit_clip_text(E: Engine, W, cfg, ids: torch.Tensor, hidden: Optional[List[t
     eps = cfg.get("layer_norm_eps", 1e-5)
     D = cfg["hidden_size"]
     act = ACT_QUICK_GELU if cfg["hidden_act"] == "quick_gelu" else ACT_GELU
-    nz = cfg["num_hidden_layers"] * (B * D * _rup(L, 64) + 64) if _rup(L, 64) != L else 0  # every layer's zero-padded V^T (eager engines: one fill)
+    nz = cfg["num_hidden_layers"] * (B * D * round_up(L, 64) + 64) if round_up(L, 64) != L else 0  # every layer's zero-padded V^T (eager engines: one fill)
     with E.scope("clip"), E.zero_pool(nz):
         x = E.embedding(ids, W["text_model.embeddings.token_embedding.weight"],
                         W["text_model.embeddings.position_embedding.weight"], name="emb")
@@ -571,16 +567,16 @@ def emit_clip_text(E: Engine, W, cfg, ids: torch.Tensor, hidden: Optional[List[t
             with E.scope(f"l{i}"):
                 fold = _ln_fold(E, W, p + ".self_attn.qkv_proj")
                 if fold:  # LayerNorm folded into the q | k | v launch (packing.fold_layernorms)
-                    qk, vt = E.linear(x, fold[0], fold[2], ln_c1=fold[1], ln_eps=eps, split_n=2 * D, rows_per_batch=L, pad_cols=_rup(L, 64), name="qk")
+                    qk, vt = E.linear(x, fold[0], fold[2], ln_c1=fold[1], ln_eps=eps, split_n=2 * D, rows_per_batch=L, pad_cols=round_up(L, 64), name="qk")
                 else:
                     n = E.layernorm(x, W[p + ".layer_norm1.weight"], W[p + ".layer_norm1.bias"], eps, name="ln1")
                     if p + ".self_attn.qkv_proj.weight" in W:  # q | k | v in one two-destination launch
                         qk, vt = E.linear(n, W[p + ".self_attn.qkv_proj.weight"], W[p + ".self_attn.qkv_proj.bias"], split_n=2 * D,
-                                          rows_per_batch=L, pad_cols=_rup(L, 64), name="qk")
+                                          rows_per_batch=L, pad_cols=round_up(L, 64), name="qk")
                     else:
                         qk = E.linear(n, W[p + ".self_attn.qk_proj.weight"], W[p + ".self_attn.qk_proj.bias"], name="qk")
                         vt = E.linear(n, W[p + ".self_attn.v_proj.weight"], W[p + ".self_attn.v_proj.bias"], transposed_out=True,
-                                      rows_per_batch=L, pad_cols=_rup(L, 64), name="vt")
+                                      rows_per_batch=L, pad_cols=round_up(L, 64), name="vt")
                 a = E.attention(qk[:, :, :D], qk[:, :, D:], vt, heads, causal=True, name="sa")
                 x = E.linear(a, W[p + ".self_attn.out_proj.weight"], W[p + ".self_attn.out_proj.bias"], residual=x, name="o")
                 fold = _ln_fold(E, W, p + ".mlp.fc1")

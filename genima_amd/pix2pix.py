@@ -157,12 +157,11 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionControlNetPipeline):
         save_tune_table()
         if self.use_graph:
             side = torch.cuda.Stream(device=dev)
-            E.use_stream(side)
-            with torch.cuda.stream(side):
+            with E.on_stream(side):
                 E.run()
                 side.synchronize()
                 E.capture()
-            io.stream = side
+            io.stream = side  # __call__ launches the captured program on it
         return io
 
     def __call__(self, prompt=None, image=None, negative_prompt=None, num_inference_steps: int = 100, guidance_scale: float = 7.5,
@@ -200,7 +199,8 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionControlNetPipeline):
         io.noise.copy_(latents.permute(0, 2, 3, 1))
         if stream is not None:
             stream.wait_stream(cur)
-            E.launch()
+            with E.on_stream(stream):
+                E.launch()
             cur.wait_stream(stream)
         else:
             E.use_stream(cur)
@@ -250,7 +250,6 @@ class InstructPix2PixTrainer(ControlNetTrainer):
         self.ema = self.cn.master.clone() if use_ema else None  # EMAModel(unet.parameters()): the shadow starts as a copy (:821-824)
         self.cdp = conditioning_dropout_prob
         self.null_ids, self._null_ctx = None, None  # tokenize_captions([""]) of the reference (:1213-1215): set_null_prompt(ids)
-        self.vae_W = None
 
     def set_null_prompt(self, input_ids: torch.Tensor):
         """Token ids [1, 77] of the empty prompt, as the run's tokenizer produces them (conditioning dropout's ``null_conditioning``)."""
@@ -270,15 +269,7 @@ class InstructPix2PixTrainer(ControlNetTrainer):
         ctx_pad, L = pad_context(ctx), ctx.shape[1]
         pred = t_unet_full(g, self.cn, self.cn_cfg, x8, t_dev, ctx_pad, L, added)
         loss, dpred = T.mse_loss(E, pred.t, noise8, c_valid, grad_scale=self.loss_scale / self.grad_accum)
-        pred.cell[0] = dpred
-        buckets = self.allreduce if hasattr(self.allreduce, "begin") else None
-        if buckets is not None and self._will_sync():
-            buckets.begin(self.cn.grad, self.cn.layout, g.first_use, len(g.tape))
-            g.on_entry_done = buckets.entry_done
-            g.fire_indices = getattr(buckets, "fire_indices", None)
-        self._side_wgrad(g)
-        g.backward()
-        self.last["pred"] = pred.t
+        self._backward(g, pred, dpred)
         return loss
 
     def step(self, *args, **kw):

@@ -11,14 +11,10 @@ from typing import Optional
 
 import torch
 
-from ._lib import OUT_F32, OUT_ROWMAJOR, AttnBwdDesc, GemmDesc, GroupNormDesc, WgradDesc, attn_dropout_desc, check
+from ._lib import OUT_F32, OUT_ROWMAJOR, AttnBwdDesc, GemmDesc, GroupNormDesc, WgradDesc, attn_dropout_desc, check, round_up
 from .engine import Engine, _ptr
 
 F16, F32 = torch.float16, torch.float32
-
-
-def _rup(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 def gemm(E: Engine, a, w, out, M: int, N: int, K: int, lda: int, ldw: int, ldo: int, *, bias=None, residual=None, ldr: int = 0,
@@ -72,10 +68,10 @@ def transpose2d(E: Engine, x: torch.Tensor, rows: int, cols: int, *, ld_in: Opti
     """x viewed as [batch][rows, cols] (row stride ld_in, element offset in_off) -> [batch][cols, rup(rows, pad_to)], zero padded
     (the pad keeps the transposed matrix usable as a GEMM operand whose reduction length must be a multiple of 8)."""
     ld_in = cols if ld_in is None else ld_in
-    ld_out = _rup(rows, pad_to)
+    ld_out = round_up(rows, pad_to)
     if out is None:
         shape = (batch, cols, ld_out) if batch > 1 else (cols, ld_out)
-        if ld_out != rows and ld_out <= _rup(rows, 64):  # the kernel writes the padding itself (no torch fill launch in front of it)
+        if ld_out != rows and ld_out <= round_up(rows, 64):  # the kernel writes the padding itself (no torch fill launch in front of it)
             out = torch.empty(shape, dtype=F16, device=E.device)
             check(E.lib.gn_transpose2d_zpad(E._ctx, x.data_ptr() + 2 * in_off, _ptr(out), rows, cols, ld_in, ld_out, batch, in_bs, cols * ld_out),
                   "gn_transpose2d_zpad")

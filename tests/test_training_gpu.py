@@ -159,6 +159,32 @@ def test_overlapped_step_equals_the_serial_step(monkeypatch):
     assert torch.equal(m0, m1)
 
 
+def test_sphere_fraction_is_recorded_without_waiting_for_the_scale_update(monkeypatch):
+    """train_step leaves the scaler's read-back in flight (the next step's front is issued under this step's optimizer) and still records
+    this step's ``sphere_fraction``: the update is pending when train_step returns, settles on the first read of ``loss_scale``, and
+    ``last["sphere_fraction"]`` is the marked share of the batch just stepped on."""
+    for k in ("GN_DEFER_SCALE", "GN_FRONT_SIDE", "GN_FRONT_UNET"):
+        monkeypatch.delenv(k, raising=False)
+    ucfg, ccfg, usd, csd, *_ = _setup()
+    synth = lambda sch, s: weights.round_to(weights.synth_state_dict(sch, s), torch.float16)  # noqa: E731
+    tr = ControlNetTrainer(Engine("cuda:0"), ucfg, ccfg, pack_state_dict(usd, "cuda"), csd, lr=1e-4, loss_scale=4096.0)
+    tr.attach_frozen(FAM["vae"], pack_state_dict(synth(schema.vae_schema(FAM["vae"]), 3), "cuda"), FAM["text"],
+                     pack_state_dict(synth(schema.clip_text_schema(FAM["text"]), 4), "cuda"), DDPMScheduler(), seed=5, sphere_loss_weight=4.0)
+    g = torch.Generator().manual_seed(3)
+    B, R = 2, 256
+    for rows in (64, 128):  # a [rows, 64] patch of every sample differs by the full byte range; everywhere else the images agree
+        cond = q16(torch.rand(B, 3, R, R, generator=g))
+        cond[:, :, :rows, :64] = 0.0
+        target = 2.0 * cond - 1.0
+        target[:, :, :rows, :64] = 1.0
+        batch = dict(pixel_values=target, conditioning_pixel_values=cond, input_ids=torch.randint(0, 1000, (B, 77), generator=g))
+        loss = tr.train_step(batch)
+        assert tr.scaler.pending, "train_step returned with the scale update applied: something in it waited for the optimizer"
+        assert tr.loss_scale > 0.0 and not tr.scaler.pending, "the first look at the scale settles it"
+        assert abs(float(tr.last["sphere_fraction"]) - rows * 64 / (R * R)) <= 1e-6
+        assert torch.isfinite(loss).all() and tr.last["grad_norm"] > 0.0
+
+
 def test_v_prediction_target():
     """prediction_type = "v_prediction" (diffusion/train_controlnet_genima.py:1393-1394: target = noise_scheduler.get_velocity(latents, noise, t)):
     the step's loss and flat gradient against the oracle's autograd with the velocity target; an unknown type is refused as the reference does."""

@@ -19,7 +19,7 @@ def fb(self, *a, **k):
 
 
 def opt(self):
-    streams = [self.E.stream] + [s for s in (getattr(self, n, None) for n in ("_fwd_stream", "_wgrad_stream", "_front_stream")) if s is not None]
+    streams = [self.E.stream] + [self._streams[n] for n in ("fwd", "wgrad", "front") if n in self._streams]
     idle = [bool(s.query()) for s in streams]
     t0 = time.perf_counter()
     r = orig_opt(self)
