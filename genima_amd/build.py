@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libgenima_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm_pp.hip", "gemm_ppp.hip", "gemm_s3.hip", "gemm_tn.hip", "attention.hip", "attention_stream.hip", "attention_pwg.hip", "attention_bwd.hip", "attention_fp8.hip", "norm.hip", "elementwise.hip", "backward.hip", "optim8.hip", "augment.hip", "fp8.hip", "comm.hip", "act_train.hip", "pack.hip", "tblock.hip", "conv_gn.hip", "conv_patch.hip", "taesd.hip", "render.hip", "ensemble.hip", "replay.hip", "replay_render.hip", "openloop.hip", "openloop_orient.hip", "openloop_seeds.hip", "loss_weight.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_pp.hip", "gemm_ppp.hip", "gemm_s3.hip", "gemm_tn.hip", "attention.hip", "attention_stream.hip", "attention_pwg.hip", "attention_bwd.hip", "attention_fp8.hip", "norm.hip", "elementwise.hip", "backward.hip", "optim8.hip", "augment.hip", "fp8.hip", "comm.hip", "act_train.hip", "pack.hip", "tblock.hip", "conv_gn.hip", "conv_patch.hip", "taesd.hip", "render.hip", "ensemble.hip", "replay.hip", "replay_render.hip", "openloop.hip", "openloop_orient.hip", "openloop_seeds.hip", "loss_weight.hip", "view_perturb.hip"]
 # -amdgpu-mfma-vgpr-form: gfx950's register file is unified, so keep MFMA accumulators in VGPRs -- the softmax / epilogue VALU
 # then works on them in place instead of through v_accvgpr_read/write copies (400 of them per attention tile otherwise).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
@@ -29,7 +29,8 @@ _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]  # measured: helps attention
 # openloop_seeds.hip: likewise -- its column 3 is openloop.hip's joint sum per seed, compared bit for bit, and its f64 sums are stated one rounded operation at a time
 # (gn_openloop_exec_actions replays ensemble.hip's rule bit for bit, so it is compiled IN ensemble.hip, under that file's flags, not here)
 # loss_weight.hip: likewise -- the mask's byte rule and the pooled weight are stated one rounded f32 operation at a time
-EXTRA_FLAGS = {"optim8.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"], "replay_render.hip": ["-ffp-contract=off"], "openloop.hip": ["-ffp-contract=off"], "openloop_orient.hip": ["-ffp-contract=off"], "openloop_seeds.hip": ["-ffp-contract=off"], "loss_weight.hip": ["-ffp-contract=off"],"attention.hip": _VGPR_FORM, "attention_stream.hip": _VGPR_FORM, "attention_pwg.hip": _VGPR_FORM, "attention_bwd.hip": _VGPR_FORM, "attention_fp8.hip": _VGPR_FORM}
+# view_perturb.hip: likewise -- its homography, bilinear weights and colour rule are stated one rounded f64 operation at a time, compared bit for bit
+EXTRA_FLAGS = {"optim8.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"], "replay_render.hip": ["-ffp-contract=off"], "openloop.hip": ["-ffp-contract=off"], "openloop_orient.hip": ["-ffp-contract=off"], "openloop_seeds.hip": ["-ffp-contract=off"], "loss_weight.hip": ["-ffp-contract=off"], "view_perturb.hip": ["-ffp-contract=off"], "attention.hip": _VGPR_FORM, "attention_stream.hip": _VGPR_FORM, "attention_pwg.hip": _VGPR_FORM, "attention_bwd.hip": _VGPR_FORM, "attention_fp8.hip": _VGPR_FORM}
 
 
 def _hipcc() -> str:

@@ -1695,6 +1695,25 @@ class Engine:
               "gn_openloop_seed_actions")
         return out
 
+    def view_perturb(self, src, M, colour, *, out=None, valid=None, n_revealed=None):
+        """``gn_view_perturb``: ``src`` uint8 [B, H, W, 3] (B = samples x views), ``M`` f64 [B, 9] (per view the homography that takes an
+        output pixel to the source pixel, ``perturb.homography``), ``colour`` f64 [B, 6] (gain r g b | offset r g b), all on the device ->
+        ``out`` uint8 [B, H, W, 3] (allocated where None; it must not overlap ``src``): every view warped, resampled bilinearly and
+        re-coloured by the rule of include/genima_hip.h.  ``valid``: uint8 [B, H, W] or None, 1 where the sample point lies inside the source;
+        ``n_revealed``: int32 [B] or None, the number of pixels of each view with ``valid == 0``, zeroed and summed by the call.  Eager
+        engines only."""
+        who = "view_perturb"
+        _eager_only(self, who, "the matrices change from batch to batch")
+        if not isinstance(src, torch.Tensor) or src.dim() != 4:
+            raise GenimaHipError("view_perturb: src must be uint8 [B, H, W, 3]")
+        B, H, W = (int(s) for s in src.shape[:3])
+        if out is None:
+            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=src.device)
+        _expect_each(who, ((src, torch.uint8, (B, H, W, 3)), (out, torch.uint8, (B, H, W, 3)), (M, torch.float64, (B, 9)), (colour, torch.float64, (B, 6))))
+        _expect_each(who, ((valid, torch.uint8, (B, H, W)), (n_revealed, torch.int32, (B,))), optional=True)
+        check(self.lib.gn_view_perturb(self._ctx, _ptr(src), _ptr(out), _ptr(valid), _ptr(n_revealed), _ptr(M), _ptr(colour), B, H, W), "gn_view_perturb")
+        return out
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

@@ -38,6 +38,14 @@ here.  What a demo tree does give is, for every transition, t
   can give every score's seed-to-seed standard deviation, the noise floor a checkpoint difference has to beat, and say whether a sphere that
   lands off is wrong on average or wrong at random.
 
+* optionally, all of that under a PERTURBED view: ``perturb=`` (a ``perturb.Perturbation``, a preset name or a spec) turns every camera about
+  its own optical centre, zooms or shifts it and tints the scene's light, per episode -- ``gn_view_perturb`` warps and re-colours the gathered
+  frames once per batch and the camera table changes with them, so the ground-truth render, the windows, the triangulation, the orientation
+  read-out and the seed tables all describe the perturbed view.  ``robustness_sweep`` runs the clean evaluator and each setting in turn and
+  reports every score's change, beside the seed-to-seed noise floor where there is one.  The rotation and the intrinsics are exact (no
+  parallax); the light is a per-channel gain, a stand-in; a camera TRANSLATION and the other four Colosseum factors are left out; and the
+  border a turned camera reveals is mirrored scene, not what it would have seen there (``OpenLoopResult.revealed`` counts it).
+
 ``OpenLoopEval(agent, None, ...)`` is the diffusion-only mode (no controller exists while the ControlNet is being fine-tuned):
 ``diffusion_validator`` makes a ``train_loop.TrainLoop`` ``validate`` callable of it.
 
@@ -235,11 +243,19 @@ class OpenLoopResult:
     [R, N, T, A] and ``"demo"`` f32 [N, T, A] (the normalised demo chunks) -- slice 0 of each IS ``image`` / ``spheres`` /
     ``actions["generated"]``; ``seed_spheres`` f64 [N, V, S, 8] (``SEED_SPHERE_COLUMNS``, ``gn_openloop_seed_spheres``) and ``seed_actions``
     ``{"norm" | "rad": f32 [N, T, 4]}`` (``SEED_ACTION_COLUMNS``, ``gn_openloop_seed_actions``; None without a controller).  ``summary()`` and
-    the other read-outs describe the first seed and read none of these; ``seed_summary()`` does."""
+    the other read-outs describe the first seed and read none of these; ``seed_summary()`` does.
+
+    ``perturbation``: None, or what the run was perturbed with: ``{"setting": Perturbation.describe(), "seed", "draws": per parameter the
+    smallest and largest value drawn}``; with it ``revealed`` int32 [N, V], per view the number of pixels whose sample point fell outside
+    the source frame (``gn_view_perturb``'s ``n_revealed``).  ``summary()`` reads neither; ``to_json`` adds them under ``"perturbation"``."""
 
     def __init__(self, image, actions, episode, step, task, tasks: Sequence[str], cameras: Sequence[str], joints: int, H: int, W: int,
                  spheres=None, windows=None, executions=None, chunks=None, points=None, point_slots=None, point_centres=None, cams=None,
-                 orientation=None, orientation_angles=None, seeds=None, seed_tables=None, seed_spheres=None, seed_actions=None):
+                 orientation=None, orientation_angles=None, seeds=None, seed_tables=None, seed_spheres=None, seed_actions=None, perturbation=None,
+                 revealed=None):
+        if (perturbation is None) != (revealed is None):
+            raise ValueError("OpenLoopResult: perturbation and revealed come together")
+        self.perturbation, self.revealed = perturbation, revealed
         if seeds is not None and (seed_tables is None or seed_spheres is None or windows is None or len(seeds) != len(seed_tables["spheres"])):
             raise ValueError("OpenLoopResult: seeds come with seed_tables, seed_spheres and windows, one slice per seed")
         self.seeds = None if seeds is None else [int(s) for s in seeds]
@@ -586,10 +602,22 @@ class OpenLoopResult:
                                         "spread": _mean(t[..., 2] / J), "gripper_acc_seed_mean": _mean(t[..., 1])}
         return out
 
+    def revealed_share(self) -> Optional[float]:
+        """None without a perturbation; else the mean over every view of the share of its pixels that the perturbation revealed."""
+        return None if self.revealed is None else float(self.revealed.astype(np.float64).mean() / float(self.H * self.W))
+
+    def perturbation_summary(self) -> Optional[Dict]:
+        """None without a perturbation; else ``perturbation`` (the setting's ``describe()``, the seed, the draws' ranges) plus
+        ``revealed_share`` overall and per camera.  An open-loop score under a perturbation is still not a success rate."""
+        if self.perturbation is None:
+            return None
+        per = self.revealed.astype(np.float64).mean(axis=0) / float(self.H * self.W)
+        return dict(self.perturbation, revealed_share=self.revealed_share(), revealed_share_per_camera={c: float(per[v]) for v, c in enumerate(self.cameras)})
+
     def to_json(self, path: str) -> Dict:
         s = self.summary()
         for key, extra in (("executions", self.execution_summary()), ("spheres_3d", self.triangulation_summary()), ("orientation", self.orientation_summary()),
-                           ("seeds", self.seed_summary())):
+                           ("seeds", self.seed_summary()), ("perturbation", self.perturbation_summary())):
             if extra is not None:  # a key of its own, and only with its table: summary() itself is as it was
                 s[key] = extra
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -691,6 +719,19 @@ class OpenLoopEval:
     ``.seed_spheres`` / ``.seed_actions``, ``seed_summary()``).  It needs a diffusion agent and costs R generations per transition; with None
     nothing changes: the same launches, the same tables, the same bits.
 
+    ``perturb``: None, a ``perturb.Perturbation``, a preset name or a spec (``perturb.parse``), drawn with ``perturb_seed``; the same as
+    calling ``set_perturbation(perturb, perturb_seed)`` after the setup.  The clean host view tables are kept.  ``set_perturbation`` draws
+    the values per episode (``perturb.draw``), recomputes the camera table (``perturb.perturb_cams``) and from it the windows -- with
+    ``triangulate`` also the group tables and the host camera table -- and uploads them with a per-(transition, view) homography f64
+    [N, V, 9] and colour row f64 [N, V, 6]; ``set_perturbation(None)`` puts the clean tables back.  ``targets()`` then launches
+    ``gn_view_perturb`` once per batch on the gathered ``images_u8``, and the warped frames take their place in the batch: as
+    ``images_u8``, as the background of the ground-truth render (the spheres are drawn untinted over the tinted frame, as a renderer would
+    overlay them) and as ``tiled``.  The proprioception, the actions and the tokens are untouched.  The per-view revealed counts go into an
+    int32 [N, V] table that rides in the one device-to-host copy (``OpenLoopResult.revealed``).  ``seeds``, ``executions``, ``triangulate``
+    and ``orientation`` compose with it: they read the batch and the tables.  Both the diffusion-only and the controller-only mode take it;
+    the controller-only mode's oracle pass sees the target over the perturbed frame.  With None there is no launch, no table and no bit
+    changed.  A score under a perturbation is still open-loop and not a success rate.
+
     Per batch, on the device: ``DeviceReplay.sample`` (the frames, proprioception, normalised action chunk, task tokens) -> ``gn_render_spheres``
     over the frames (``full``, ``occupied``) -> the four views on the 2x2 canvas -> the pipeline (``harness.make_prompt`` ids, one generator
     seeded ``seed`` and advanced call by call) -> ``act_tiled`` -> the image, sphere and action scores -> the controller again on ``full`` -> its action
@@ -700,7 +741,8 @@ class OpenLoopEval:
     def __init__(self, diffusion_agent, controller, episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None,
                  batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
                  change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None, triangulate: bool = False,
-                 tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6, orientation=None, seeds: Optional[int] = None, seed_min_ratio: float = 0.5):
+                 tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6, orientation=None, seeds: Optional[int] = None, seed_min_ratio: float = 0.5,
+                 perturb=None, perturb_seed: int = 0):
         from .render import load_traj
 
         device, engine, T = self._check_options(diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions,
@@ -726,6 +768,9 @@ class OpenLoopEval:
             raise ValueError(f"OpenLoopEval: the replay's demo actions are {tuple(rp.action.shape)}, expected {(rp.N, rp.A)}")
         self.E, self.N, self.H, self.W, self.T, self.A = rp.E, rp.N, H, W, rp.T, rp.A
         self._upload(self._transition_tables(trajs, episodes), stats)
+        self.perturbation, self.perturb_seed, self.perturb_draws, self.perturb_M, self.perturb_colour = None, 0, None, None, None
+        if perturb is not None:
+            self.set_perturbation(perturb, perturb_seed)
 
     def _check_options(self, diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions, triangulate,
                        tri_min_ratio, tri_min_det, orientation, seeds=None, seed_min_ratio=0.5):
@@ -792,7 +837,6 @@ class OpenLoopEval:
     def _transition_tables(self, trajs, episodes) -> Dict[str, np.ndarray]:
         """Part two, on the host: transition n of episode e, step t, reads observation t of trajectory e -> the view tables [N, V, ...] to
         upload; the step, episode and task of every transition, the spheres' windows, the groups and the episodes' first transitions are kept."""
-        from .render import sphere_windows
         from .replay import view_tables
 
         rp = self.replay
@@ -806,12 +850,8 @@ class OpenLoopEval:
                 raise ValueError(f"OpenLoopEval: episode {e} has {int(counts[e]) + 1} observations in its demo and {len(t['gripper_open'])} steps in its trajectory")
         rows = ((starts[ep_of] + step)[:, None] * self.V + np.arange(self.V)[None]).reshape(-1)
         views = {k: np.ascontiguousarray(vt[k][rows].reshape((rp.N, self.V) + vt[k].shape[1:])) for k in vt}
-        self.windows_host = self.point_slots_host = self.point_centres_host = self.cams_host = None
-        if self.agent is not None:  # the spheres' windows of every transition, once: int32 [N, V, S, 4]
-            self.windows_host = np.ascontiguousarray(sphere_windows(views["cams"], views["spheres"], views["count"], self.H, self.W))
-            if self.triangulate:  # which slot of which view shows which sphere, and where it truly is: int32 [N, G, V], f64 [N, G, 3]
-                self.point_slots_host, self.point_centres_host = sphere_groups(views["spheres"], views["count"], self.windows_host)
-                self.cams_host = views["cams"]
+        self.views_host = views  # the CLEAN tables: set_perturbation derives the perturbed ones from them and puts them back
+        self._camera_tables(views["cams"])
         # with execution modes to replay: the first transition of each one's episode
         self.first_tr_host = np.ascontiguousarray((np.arange(rp.N) - step).astype(np.int32)) if self.executions is not None else None
         self.step_index, self.episode_index = step, ep_of.copy()
@@ -819,6 +859,42 @@ class OpenLoopEval:
         self.tasks = sorted(set(names))
         self.task_index = np.asarray([self.tasks.index(names[e]) for e in ep_of], np.int32)
         return views
+
+    def _camera_tables(self, cams: np.ndarray) -> None:
+        """The host tables that follow from a camera table f32 [N, V, 18] (the clean one, or a perturbed one): with a diffusion agent the
+        spheres' windows of every transition, int32 [N, V, S, 4], and with ``triangulate`` which slot of which view shows which sphere and
+        where it truly is, int32 [N, G, V] and f64 [N, G, 3], beside the camera table itself."""
+        from .render import sphere_windows
+
+        views = self.views_host
+        self.windows_host = self.point_slots_host = self.point_centres_host = self.cams_host = None
+        if self.agent is not None:
+            self.windows_host = np.ascontiguousarray(sphere_windows(cams, views["spheres"], views["count"], self.H, self.W))
+            if self.triangulate:
+                self.point_slots_host, self.point_centres_host = sphere_groups(views["spheres"], views["count"], self.windows_host)
+                self.cams_host = cams
+
+    def set_perturbation(self, p=None, seed: int = 0) -> None:
+        """``p``: None, a ``perturb.Perturbation``, a preset name or a spec.  Draws the values of every episode with ``seed``, recomputes the
+        camera table and what follows from it on the host and uploads them with the homographies and the colour rows; None puts the clean
+        tables back.  The next ``run()`` / ``targets()`` uses them; nothing is launched here."""
+        from . import perturb as PB
+
+        def up(a):
+            return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(self.E.device)
+
+        clean = self.views_host["cams"]
+        if p is None:
+            cams, M, colour = clean, None, None
+            self.perturbation, self.perturb_seed, self.perturb_draws = None, 0, None
+        else:
+            p = PB.parse(p)
+            cams, M, colour, draws = PB.transition_tables(p, clean, self.episode_index, self.replay.N_ep, self.cameras, int(seed))
+            self.perturbation, self.perturb_seed, self.perturb_draws = p, int(seed), draws
+        self._camera_tables(cams)
+        self.views["cams"] = up(cams)
+        self.windows, self.point_slots, self.point_centres = up(self.windows_host), up(self.point_slots_host), up(self.point_centres_host)
+        self.perturb_M, self.perturb_colour = up(M), up(colour)
 
     def _upload(self, views: Dict[str, np.ndarray], stats) -> None:
         """Part three: the view tables, the atlas, a device copy of every host table that part two kept, the scales and the prompt ids."""
@@ -848,6 +924,11 @@ class OpenLoopEval:
         batch = self.replay.sample(idx, want_u8=True)
         sel = torch.from_numpy(np.asarray(idx, np.int64)).to(E.device, non_blocking=True)
         v = {k: t.index_select(0, sel).reshape((B * V,) + tuple(t.shape[2:])).contiguous() for k, t in self.views.items()}
+        if self.perturb_M is not None:  # the gathered frames warped and re-coloured, one launch; they take the clean ones' place
+            counts = torch.empty((B * V,), dtype=torch.int32, device=E.device)
+            warped = E.view_perturb(batch["images_u8"].view(B * V, H, W, 3), self.perturb_M.index_select(0, sel).reshape(B * V, 9),
+                                    self.perturb_colour.index_select(0, sel).reshape(B * V, 6), n_revealed=counts)
+            batch["images_u8"], batch["revealed"] = warped.view(tuple(batch["images_u8"].shape)), counts.view(B, V)
         frames = batch["images_u8"].view(B * V, H, W, 3)
         full = torch.empty((B * V, H, W, 3), dtype=torch.uint8, device=E.device)
         occupied = torch.empty((B * V, H, W), dtype=torch.uint8, device=E.device)
@@ -899,6 +980,8 @@ class OpenLoopEval:
             tabs["spheres"] = torch.zeros((N, self.V, int(self.windows.shape[2]), 17), dtype=torch.int64, device=dev)
             if self.orientation_rot is not None:
                 tabs["orientation"] = torch.zeros((N, self.V, int(self.windows.shape[2]), int(self.orientation_rot.shape[0]), 4), dtype=torch.int64, device=dev)
+        if self.perturb_M is not None:  # per view, the pixels the perturbation revealed
+            tabs["revealed"] = torch.zeros((N, self.V), dtype=torch.int32, device=dev)
         if self.executions is not None:  # every scored chunk, as the controller's head wrote it
             tabs["chunks"] = {k: torch.zeros((N, T, self.A), dtype=torch.float16, device=dev) for k in ("generated", "oracle") if k in tabs}
         if self.seeds is not None:
@@ -1019,6 +1102,8 @@ class OpenLoopEval:
         with torch.inference_mode():  # as harness.control_step runs the same two programs
             batch = self.targets(idx)
             B = len(idx)
+            if "revealed" in tabs:
+                tabs["revealed"][start: start + n_valid].copy_(batch["revealed"][:n_valid])
             if self.agent is not None and self.seeds is None:
                 self._score_generated(batch, idx, generator, tabs, start, n_valid)
             elif self.agent is not None:
@@ -1042,6 +1127,8 @@ class OpenLoopEval:
         dev = {"actions": {k: tabs[k] for k in ("generated", "oracle") if k in tabs}, "image": tabs.get("image"), "spheres": tabs.get("spheres"),
                "points": self.triangulate_spheres(tabs), "orientation": tabs.get("orientation"), "executions": self.replay_executions(tabs),
                "chunks": tabs.get("chunks")}
+        if "revealed" in tabs:
+            dev["revealed"] = tabs["revealed"]
         if self.seeds is not None:  # the first seed's tables travel once, inside the seed tables, and are sliced out of them on the host
             dev["seed_spheres"], dev["seed_actions"] = self.seed_reductions(tabs)
             dev["seed_tables"] = tabs["seed"]
@@ -1055,6 +1142,11 @@ class OpenLoopEval:
         copies = read_back(named)
         host = _map_tensors(dev, lambda name, t: copies[name])
         extra = {}
+        if "revealed" in host:
+            from .perturb import draw_ranges
+
+            extra = dict(revealed=host["revealed"], perturbation={"setting": self.perturbation.describe(), "seed": self.perturb_seed,
+                                                                  "draws": draw_ranges(self.perturb_draws)})
         if self.seeds is not None:
             st = host["seed_tables"]
             host["image"], host["spheres"] = st["image"][0], st["spheres"][0]
@@ -1062,12 +1154,50 @@ class OpenLoopEval:
                 host["actions"] = dict({"generated": {unit: t[0] for unit, t in st["generated"].items()}}, **host["actions"])
                 if host["chunks"] is not None:
                     host["chunks"] = dict({"generated": st["chunks"][0]}, **host["chunks"])
-            extra = dict(seeds=[self.seed + r for r in range(self.seeds)], seed_tables=st, seed_spheres=host["seed_spheres"], seed_actions=host["seed_actions"])
+            extra = dict(extra, seeds=[self.seed + r for r in range(self.seeds)], seed_tables=st, seed_spheres=host["seed_spheres"], seed_actions=host["seed_actions"])
         return OpenLoopResult(host["image"], host["actions"], self.episode_index, self.step_index, self.task_index, self.tasks, self.cameras, self.A - 1,
                               self.H, self.W, spheres=host["spheres"], windows=self.windows_host if host["spheres"] is not None else None,
                               executions=host["executions"], chunks=host["chunks"], points=host["points"], point_slots=self.point_slots_host,
                               point_centres=self.point_centres_host, cams=self.cams_host, orientation=host["orientation"],
                               orientation_angles=self.orientation_angles if host["orientation"] is not None else None, **extra)
+
+
+def robustness_sweep(ev: OpenLoopEval, settings, found_mass: float = 0.5, seed: int = 0) -> Dict:
+    """The clean evaluator, then each of ``settings`` (``perturb.Perturbation``s, preset names or specs, each drawn with ``seed``) on the same
+    evaluator -- the same programs, the same generator seeds -- and the clean tables put back at the end, whatever happened.  ->
+
+    ``{"clean": validator_scalars(found_mass) of the clean run, "n", "settings": [...]}``, one entry per setting: ``setting`` (its
+    ``describe()``), ``seed``, ``draws`` (the ranges drawn), ``scores`` (``validator_scalars(found_mass)`` under it), ``delta`` (scores minus
+    clean, None where either is), ``revealed_share`` and ``lost_spheres``, the number of spheres the clean run drew whose window is empty
+    after the perturbation (they left the view, so their scores are about other spheres than the clean run's).  When the evaluator has
+    ``seeds``, each entry also holds ``delta_over_std``: the delta over the CLEAN run's seed-to-seed standard deviation of that score (None
+    where there is none or it is 0) -- a ratio to read, not a verdict.  Open-loop like every score here: a score under a perturbation is
+    still not a success rate, and revealed borders are mirrored scene, not what a rotated camera would have seen there."""
+    from . import perturb as PB
+
+    if ev.agent is None:
+        raise ValueError("robustness_sweep: the scores are the generated image's; it needs an evaluator with a diffusion agent")
+    settings = [PB.parse(s) for s in settings]
+    try:
+        ev.set_perturbation(None)
+        clean = ev.run()
+        base = clean.validator_scalars(found_mass)
+        std = {k: v["std"] for k, v in clean.seed_summary(found_mass)["scores"].items()} if clean.seeds is not None else None
+        drawn = clean.sphere_drawn()
+        out: Dict = {"clean": base, "n": len(clean), "settings": []}
+        for p in settings:
+            ev.set_perturbation(p, seed)
+            res = ev.run()
+            scores = res.validator_scalars(found_mass)
+            delta = {k: None if scores[k] is None or base[k] is None else scores[k] - base[k] for k in base}
+            entry = {"setting": p.describe(), "seed": int(seed), "draws": res.perturbation["draws"], "scores": scores, "delta": delta,
+                     "revealed_share": res.revealed_share(), "lost_spheres": PB.lost_windows(clean.windows, res.windows, drawn)}
+            if std is not None:
+                entry["delta_over_std"] = {k: None if delta[k] is None or not std.get(k) else delta[k] / std[k] for k in base}
+            out["settings"].append(entry)
+        return out
+    finally:
+        ev.set_perturbation(None)
 
 
 def controller_validator(episodes, cameras: Sequence[str] = DEFAULT_CAMERAS, *, render_cfg, stats, tokenizer=None, batch_size: int = 8, engine=None,

@@ -1051,6 +1051,36 @@ int32_t gn_openloop_seed_spheres(gn_ctx* ctx, const uint64_t* sph, double* out, 
 int32_t gn_openloop_seed_actions(gn_ctx* ctx, const void* chunks, int32_t ld, const float* demo, const float* joint_scale, float* out, float inv_R,
                                  int32_t R, int32_t N, int32_t T, int32_t A);
 
+/* Camera-pose and light perturbation of a batch of views (genima_amd/perturb.py, OpenLoopEval(perturb=...)): one launch warps every view by
+ * its own homography, resamples it bilinearly and applies a per-channel gain and offset.  All pointers are device memory.
+ *   src       uint8 [B][H][W][3], the views (B = samples x views);  dst uint8 [B][H][W][3], the result.  dst must not overlap src
+ *   valid     uint8 [B][H][W] or NULL: 1 where the output pixel's sample point lies inside the source image, else 0
+ *   n_revealed int32 [B] (4-byte aligned) or NULL: per view the number of pixels with valid == 0 -- border the source never showed.  Zeroed by
+ *             the call on the ctx stream, then summed per workgroup and added with one integer atomicAdd each: order-independent, same bits
+ *   M         f64 [B][9], 8-byte aligned: per view the row-major 3x3 matrix that takes an OUTPUT pixel to the SOURCE pixel (homogeneous)
+ *   colour    f64 [B][6], 8-byte aligned: per view gain r g b | offset r g b, the offsets in levels of 0 .. 255
+ * Per output pixel (x, y) of view b, in f64, every operation rounded once in the written order (no fused multiply-add):
+ *    1. X = x + 0.5, Y = y + 0.5
+ *    2. a = (M0 X + M1 Y) + M2
+ *    3. c = (M3 X + M4 Y) + M5
+ *    4. w = (M6 X + M7 Y) + M8
+ *    5. if !(w > 0), or a, c or w is not finite: the pixel is (0, 0, 0), valid = 0 (it counts as revealed), and nothing below applies
+ *    6. u = a / w, v = c / w
+ *    7. valid = (0 <= u <= W and 0 <= v <= H)
+ *    8. su = clamp(u - 0.5, -(W - 1), 2 (W - 1)), x0 = floor(su), tx = su - x0;  sv, y0, ty likewise from v and H;
+ *       clamp(t, lo, hi) = t < lo ? lo : (t > hi ? hi : t)
+ *    9. the column indices x0 and x0 + 1 are folded into the image by ONE reflection about the edge pixel's centre (torch's `reflect`):
+ *       i < 0 -> -i, else i > W - 1 -> 2 (W - 1) - i; then clamped to [0, W - 1].  Rows likewise with H.
+ *   10. per channel, p00 p01 (row y0) and p10 p11 (row y0 + 1) the four source bytes as f64, at the folded columns x0 and x0 + 1:
+ *       top = p00 (1 - tx) + p01 tx,  bot = p10 (1 - tx) + p11 tx,  cc = top (1 - ty) + bot ty    ((1 - tx) and (1 - ty) rounded once each)
+ *       t = cc gain[ch] + offset[ch];  out = rint(t > 0 ? (t > 255 ? 255 : t) : 0), half to even (a NaN t gives 0)
+ * With M the identity, gain 1 and offset 0 the result is a copy, bit for bit: tx = ty = 0 and every product is exact.
+ * Revealed border is MIRRORED scene, not what a moved camera would have seen there; `valid` and n_revealed say how much of it there is.
+ * Refused, launching nothing and leaving the outputs as they were: a NULL ctx, src, dst, M or colour; B, H or W <= 0; B > 65535;
+ * B * H * W * 3 >= 2^31; dst overlapping src (dst == src included); a misaligned M, colour or n_revealed.  Eager only. */
+int32_t gn_view_perturb(gn_ctx* ctx, const uint8_t* src, uint8_t* dst, uint8_t* valid, int32_t* n_revealed, const double* M, const double* colour,
+                        int32_t B, int32_t H, int32_t W);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */

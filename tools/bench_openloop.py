@@ -31,9 +31,14 @@ and the oracle pass), the bytes the seed tables add to the final copy, and the t
 device events (``gn_openloop_seed_spheres``, ``gn_openloop_seed_actions`` with the joint scale).  There is no target: the cost is R
 generations and is the user's to choose.
 
+With ``--perturb SPEC`` (a preset or a spec of ``genima_amd.perturb.parse``) it times one evaluator batch (``run_batch``) of two evaluators
+over the same agents that alternate inside every repetition -- one clean and one with ``perturb=SPEC`` -- and the ``gn_view_perturb`` launch
+alone over one batch's frames by device events (its zeroing of the revealed counts included), beside the bytes it reads and writes.  No time
+is promised: the perturbed batch is reported beside the clean batch of the same process.
+
 Prints one JSON line; needs an MI355X.
 
-    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid] [--triangulate] [--orientation] [--seeds R]
+    python tools/bench_openloop.py [--batch 8] [--reps 10] [--warmup 2] [--episodes 2] [--length 12] [--exec_grid] [--triangulate] [--orientation] [--seeds R] [--perturb SPEC]
         [--sphere_textures tests/golden/sphere_textures] [--out profiles/openloop_b8.json]
 """
 import argparse
@@ -65,6 +70,7 @@ def main():
     ap.add_argument("--triangulate", action="store_true", help="also time whole runs without and with triangulate=True, and the triangulation launch")
     ap.add_argument("--orientation", action="store_true", help="also time whole runs without and with orientation=37, and the orientation launch")
     ap.add_argument("--seeds", type=int, default=None, metavar="R", help="also time whole runs without and with seeds=R, and the two seed-axis launches")
+    ap.add_argument("--perturb", default=None, metavar="SPEC", help="also time one evaluator batch clean and under this perturbation, and the gn_view_perturb launch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -260,6 +266,34 @@ def main():
         res["seeds_extra_copy_bytes"] = int(seed_bytes - plain_bytes)
         launches["seed_spheres_us"] = lambda: E.openloop_seed_spheres(whole["spheres"], s_sph, min_ratio=ev_seeds.seed_min_ratio)
         launches["seed_actions_us"] = lambda: E.openloop_seed_actions(whole["chunks"], whole["demo"], s_act["rad"], joint_scale=ev_seeds.joint_std)
+    if args.perturb is not None:
+        from genima_amd import perturb as PB
+
+        setting = PB.parse(args.perturb)
+        ev_p = OpenLoopEval(dagent, controller, eps, cams, render_cfg=rcfg, stats=(P.action_stats(demos), P.proprio_stats(demos)), tokenizer=tokens,
+                            batch_size=B, engine=E, perturb=setting, perturb_seed=0)
+        ptabs = ev_p._tables()
+        runs = {"batch_clean": lambda: ev.run_batch(0, tabs, gen), "batch_perturbed": lambda: ev_p.run_batch(0, ptabs, gen)}
+        rms = {k: [] for k in runs}
+        for i in range(args.warmup + args.reps):
+            for k, fn in runs.items():
+                E.synchronize()
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    rms[k].append((time.perf_counter() - t) * 1e3)
+        for k in runs:
+            res[k] = stats(rms[k])
+        res["perturb"] = {"setting": setting.describe(), "seed": 0, "alternations": args.reps, "draws": PB.draw_ranges(ev_p.perturb_draws)}
+        res["perturbed_minus_clean_ms"] = round(res["batch_perturbed"]["median_ms"] - res["batch_clean"]["median_ms"], 4)
+        res["batch_clean_spread_ms"] = round(res["batch_clean"]["max_ms"] - res["batch_clean"]["min_ms"], 4)
+        p_M = ev_p.perturb_M.index_select(0, sel).reshape(B * ev.V, 9)
+        p_col = ev_p.perturb_colour.index_select(0, sel).reshape(B * ev.V, 6)
+        p_out, p_cnt = torch.empty_like(frames), torch.empty((B * ev.V,), dtype=torch.int32, device=E.device)
+        launches["view_perturb_us"] = lambda: E.view_perturb(frames, p_M, p_col, out=p_out, n_revealed=p_cnt)  # frames: the CLEAN evaluator's batch
+        res["view_perturb_bytes"] = {"views": B * ev.V, "read_source": int(frames.numel()), "written": int(p_out.numel() + 4 * p_cnt.numel()),
+                                     "tables": int(8 * (p_M.numel() + p_col.numel()))}
     for name, launch in launches.items():
         us = []
         for _ in range(5):
@@ -276,6 +310,9 @@ def main():
     wh = ev.windows_host[idx]
     res["sphere_windows"] = {"n": int(wh[..., 0].size), "non_empty": int(((wh[..., 2] > wh[..., 0]) & (wh[..., 3] > wh[..., 1])).sum()),
                              "pixels": int(((wh[..., 2] - wh[..., 0]) * (wh[..., 3] - wh[..., 1])).sum()), "change_threshold": ev.change_threshold}
+    if args.perturb is not None:
+        res["view_perturb_revealed_share"] = round(float(p_cnt.double().mean().item()) / (S * S), 5)
+        res["view_perturb_gb_per_s"] = round((res["view_perturb_bytes"]["read_source"] + res["view_perturb_bytes"]["written"]) / (res["view_perturb_us"]["median"] * 1e-6) / 1e9, 2)
     res["image_metrics_bytes"] = int(out_img.numel() + batch["full"].numel() + batch["occupied"].numel())
     line = json.dumps(res)
     print(line, flush=True)

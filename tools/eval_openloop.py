@@ -28,6 +28,13 @@ the bias of the seeds' mean centroid beside their spread about it (``variance_sh
 error of the seed-averaged chunk beside the mean of the seeds' errors (``gain``; ``OpenLoopResult.seed_summary``).  Everything outside that
 block stays the first seed's, as without the option; the run costs R generations per transition.  A seed spread is not a success rate either,
 and ``gain`` is teacher-forced: nothing executes an averaged chunk.
+``--perturb SPEC`` (repeatable; a preset ``camera_pose`` / ``light_color``, a spec such as ``camera:pitch=-0.05..0.05,zoom=0.95..1.05`` or
+``light:r=0.5..1,g=0.5..1,b=0.5..1``, two joined by ``+``; ``genima_amd.perturb.parse``) also runs ``openloop.robustness_sweep`` after the clean
+run -- the same evaluator under each setting, drawn per episode with ``--perturb_seed`` -- and writes it beside the result as
+``<out>.robustness.json``: per setting the scores, their change against clean (with ``--seeds`` also over the clean seed-to-seed standard
+deviation), the share of revealed border and the spheres that left the view.  The camera rotation and intrinsics are exact, the light is a
+per-channel gain (a stand-in), a camera translation is left out; revealed borders are mirrored scene, and a score under a perturbation is
+still not a success rate.  The result file itself stays the clean run's.
 Open-loop error is not a success rate: every chunk is predicted from a demo state, nothing is executed and no error compounds."""
 import argparse
 import json
@@ -72,6 +79,9 @@ def parse(argv=None):
     ap.add_argument("--seeds", type=int, default=None, metavar="R",
                     help="also repeat the generation with R (2 .. 64) generator seeds, --seed .. --seed + R - 1: per-score seed spread, per-sphere bias and spread")
     ap.add_argument("--seed_min_ratio", type=float, default=0.5, help="with --seeds: a seed found a sphere when its mass is at least this share of the ground truth's")
+    ap.add_argument("--perturb", action="append", default=None, metavar="SPEC",
+                    help="also score under this camera-pose / light perturbation (a preset, a spec, or two joined by '+'); repeatable; written to <out>.robustness.json")
+    ap.add_argument("--perturb_seed", type=int, default=0, help="with --perturb: the seed of the per-episode draws")
     ap.add_argument("--out", default="openloop.json")
     a = ap.parse_args(argv)
     if not a.no_controller and not (a.controller_snapshot and a.stats_dir):
@@ -87,6 +97,13 @@ def parse(argv=None):
             ap.error(str(err))
     if a.seeds is not None and not 2 <= a.seeds <= 64:
         ap.error(f"--seeds {a.seeds}: the number of generator seeds must lie in [2, 64]")
+    if a.perturb is not None:
+        from genima_amd import perturb as PB
+
+        try:
+            a.perturb = [PB.parse(t) for t in a.perturb]
+        except ValueError as err:
+            ap.error(str(err))
     if a.orientation is not None:
         from genima_amd.openloop import orientation_candidates, parse_orientation
 
@@ -104,7 +121,7 @@ def main(argv=None):
     from genima_amd import configs, harness
     from genima_amd import render as R
     from genima_amd.act import GenimaACT
-    from genima_amd.openloop import OpenLoopEval
+    from genima_amd.openloop import OpenLoopEval, robustness_sweep
 
     episodes = P.list_episodes(a.dataset_root, a.tasks, a.demos)
     if not episodes:
@@ -139,6 +156,13 @@ def main(argv=None):
     print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
     summary = ev.run().to_json(a.out)
     print(json.dumps(summary, indent=1))
+    if a.perturb is not None:
+        sweep = robustness_sweep(ev, a.perturb, seed=a.perturb_seed)
+        path = os.path.splitext(a.out)[0] + ".robustness.json"
+        with open(path, "w") as f:
+            json.dump(sweep, f, indent=1)
+        print(json.dumps(sweep, indent=1))
+        print(f"eval_openloop: robustness sweep written to {path}", flush=True)
 
 
 if __name__ == "__main__":
