@@ -258,6 +258,7 @@ SIGNATURES = {
     "gn_openloop_action_metrics": (_I32, [_P, _P, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32]),
     "gn_openloop_exec_actions": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_openloop_exec_metrics": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32]),
+    "gn_openloop_exec_actions_samples": (_I32, [_P, _P, _I64, _I64, _I32, _F, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_openloop_triangulate": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _I32, _I32, _I32, _I32]),
     "gn_openloop_seed_spheres": (_I32, [_P, _P, _P, _D, _I32, _I32, _I32, _I32]),
     "gn_openloop_seed_actions": (_I32, [_P, _P, _I32, _P, _P, _P, _F, _I32, _I32, _I32, _I32]),
@@ -285,6 +286,7 @@ SIGNATURES = {
     "gn_action_ensemble_state_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "gn_action_ensemble": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_action_ensemble_f16": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
+    "gn_action_ensemble_samples_f16": (_I32, [_P, _P, _I64, _I64, _I32, _F, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_transpose2d": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I64, _I32, _I64, _I64]),
     "gn_transpose2d_zpad": (_I32, [_P, _P, _P, _I32, _I32, _I64, _I64, _I32, _I64, _I64]),
     "gn_transpose2d_multi": (_I32, [_P, _P, _I32, _I32]),
@@ -363,6 +365,7 @@ SIGNATURES = {
     "gn_program_add_softmax_rows": (_I32, [_P, _P, _I64, _I32, _I32, _F]),
     "gn_program_add_maxpool3x3s2": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32]),
     "gn_program_add_action_ensemble": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
+    "gn_program_record_action_ensemble_samples": (_I32, [_P, _P, _I64, _I64, _I32, _F, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F]),
     "gn_program_num_ops": (_I64, [_P]),
     "gn_program_get_gemm": (_I32, [_P, _I64, _P]),
     "gn_program_set_gemm_plan": (_I32, [_P, _I64, _I32, _I32, _P]),

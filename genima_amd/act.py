@@ -368,6 +368,19 @@ def execution_slots(T: int, execution_horizon: Optional[int], temporal_agg: bool
     return h, (-(-T // h) if temporal_agg else 1)
 
 
+def check_samples(samples, combine):
+    """-> ``(R, combine)`` or None: the sample mode of ``GenimaACT.set_execution`` / ``harness.control_step``, checked."""
+    if combine not in Engine.COMBINE_RULES:
+        raise GenimaHipError(f"combine must be one of {Engine.COMBINE_RULES}, got {combine!r}")
+    if samples is None:
+        if combine != "mean":
+            raise GenimaHipError(f"combine={combine!r} needs samples=R")
+        return None
+    if isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= 64:
+        raise GenimaHipError(f"samples must be an integer in 1 .. 64, got {samples!r}")
+    return samples, combine
+
+
 def check_ensemble_m(m) -> float:
     m = float(m)
     if not (m >= 0.0 and math.isfinite(m)):
@@ -400,6 +413,8 @@ class GenimaACT:
         self._exec = None          # (h, K, m) once set_execution() asked for an execution mode; None: act() returns the whole chunk
         self._exec_epoch = 0       # bumped by set_execution() / reset_execution(): a program whose epoch is older empties every row's ring
         self._exec_pending = set() # rows reset_execution(rows) marked for the next call
+        self._exec_samples = None  # (R, combine) once set_execution(samples=R) asked for sample-combined chunks
+        self.last_samples = None   # {"pick": int32 [B], "spread": f32 [B]} on the device: the last call under a sample mode
         if self.device.type == "cuda" and torch.cuda.is_available():
             self.to(self.device)
 
@@ -495,19 +510,29 @@ class GenimaACT:
         return missing, unexpected
 
     # ---- execution mode: the eval configurations' ``execution_horizon`` / ``temporal_agg`` ------------------------------------
-    def set_execution(self, execution_horizon: Optional[int] = None, temporal_agg: bool = False, m: float = 0.01):
+    def set_execution(self, execution_horizon: Optional[int] = None, temporal_agg: bool = False, m: float = 0.01, samples: Optional[int] = None,
+                      combine: str = "mean"):
         """Honour ``execution_horizon`` / ``temporal_agg`` (controller/cfgs/eval_genima.yaml:29,33; the reference never reads them): from now
         on ``act`` / ``act_tiled`` return f32 ``[B, h, A]`` -- the actions of the environment steps ``step .. step + h - 1`` with
         ``h = execution_horizon`` (None: the whole chunk), so the loop executes h actions and calls again.  With ``temporal_agg`` every
         chunk that still covers a step takes part in its action: the ACT paper's temporal ensembling with weights ``exp(-m i)``, i = 0 for
         the oldest prediction, over all action dimensions alike (the gripper's included); without it the result is the first h rows of the
         new chunk.  The history lives on the device (Engine.action_ensemble, one launch at the end of the recorded program) and starts
-        empty.  ``set_execution()`` with nothing set returns to the default: the whole chunk, no extra op."""
+        empty.  ``set_execution()`` with nothing set returns to the default: the whole chunk, no extra op.
+
+        ``samples=R``: the diffusion stage draws noise, so one observation generated R times gives R chunks.  ``act`` / ``act_tiled`` then take
+        ``B * R`` rows (row ``b * R + r`` is sample r of b) and return ``[B, h, A]``: the R chunks of a row are combined on the device -- ``combine``
+        ``"mean"`` (added in sample order, the arithmetic of ``OpenLoopEval(seeds=R)``'s ``seed_mean``) or ``"medoid"`` (the sample closest to all
+        the others in summed absolute distance over every action dimension alike; two samples in different modes average to an action of
+        neither, a medoid stays on one) -- and the combined chunk enters the history above, which is kept per b.  With ``samples`` alone the
+        whole combined chunk is returned (h = T, one slot).  ``last_samples`` holds the picks and spreads of the last call on the device."""
         T = int(self.config["num_queries"])
-        if execution_horizon is None and not temporal_agg:
+        self._exec_samples = check_samples(samples, combine)
+        if execution_horizon is None and not temporal_agg and self._exec_samples is None:
             self._exec = None
         else:
             self._exec = (*execution_slots(T, execution_horizon, temporal_agg), check_ensemble_m(m))
+        self.last_samples = None
         self._exec_epoch += 1
         self._exec_pending = set()
         return self
@@ -516,6 +541,11 @@ class GenimaACT:
     def execution(self):
         """The execution mode in force: ``(h, K, m)`` -- actions per call, ring slots, weight decay -- or None (the whole chunk)."""
         return self._exec
+
+    @property
+    def execution_samples(self):
+        """The sample mode in force: ``(R, combine)`` -- sampled chunks per row, ``"mean"`` or ``"medoid"`` -- or None (one chunk per row)."""
+        return self._exec_samples
 
     def reset_execution(self, rows=None):
         """Forget the chunk history at the next call (a new episode): of every batch row, or of the rows listed."""
@@ -575,6 +605,10 @@ class GenimaACT:
         if self.W is None:
             raise GenimaHipError("GenimaACT is not on a ROCm device (no CPU fallback)")
         key = (B, V, H, Wd, lang) if self._exec is None and not self.use_graph else (B, V, H, Wd, lang, self._exec, self.use_graph)
+        if self._exec_samples is not None:
+            if B % self._exec_samples[0]:
+                raise GenimaHipError(f"act: {B} rows are no multiple of samples = {self._exec_samples[0]} (row b * R + r is sample r of b)")
+            key += (self._exec_samples,)
         io = self._progs.get(key)
         if io is None:
             from types import SimpleNamespace
@@ -588,15 +622,22 @@ class GenimaACT:
             io.qpos = E.buf("in_qpos", (B, sdim), zero=True)
             io.tokens = E.buf("in_tokens", (B, 77), dtype=torch.int32, zero=True) if lang else None
             io.a_hat, io.is_pad, io.task = emit_act_forward(E, self.W, self.Wclip, self.config, self.clip_config, io.img, io.qpos, io.tokens)
-            io.exec = self._exec
+            io.exec, io.samples = self._exec, self._exec_samples
             if io.exec is not None:
                 # the last op, outside every guarded segment: ensembles a_hat (f16, 8-padded rows) with the ring it keeps on the device
                 h, K, m = io.exec
                 T, A = int(self.config["num_queries"]), int(self.config["action_dim"])
-                io.ens_ctl = torch.zeros(5 * B, dtype=torch.uint8, device=self.device)  # int32 steps [B] | uint8 reset [B]
-                io.ens_steps, io.ens_reset = io.ens_ctl[: 4 * B].view(torch.int32), io.ens_ctl[4 * B:]
-                io.ens_state = E.action_ensemble_state(B, T, A, K)
-                io.ens_out = E.action_ensemble(io.a_hat, io.ens_state, io.ens_steps, io.ens_reset, h, K, m, A=A, name="actions")
+                Bx = io.ens_rows = B if io.samples is None else B // io.samples[0]  # one ring per b, not per sampled row
+                io.ens_ctl = torch.zeros(5 * Bx, dtype=torch.uint8, device=self.device)  # int32 steps [Bx] | uint8 reset [Bx]
+                io.ens_steps, io.ens_reset = io.ens_ctl[: 4 * Bx].view(torch.int32), io.ens_ctl[4 * Bx:]
+                io.ens_state = E.action_ensemble_state(Bx, T, A, K)
+                if io.samples is None:
+                    io.ens_out = E.action_ensemble(io.a_hat, io.ens_state, io.ens_steps, io.ens_reset, h, K, m, A=A, name="actions")
+                else:
+                    io.ens_pick = torch.zeros(Bx, dtype=torch.int32, device=self.device)
+                    io.ens_spread = torch.zeros(Bx, dtype=torch.float32, device=self.device)
+                    io.ens_out = E.action_ensemble(io.a_hat, io.ens_state, io.ens_steps, io.ens_reset, h, K, m, A=A, name="actions",
+                                                   samples=io.samples[0], combine=io.samples[1], pick=io.ens_pick, spread=io.ens_spread)
                 io.ens_epoch = None
             save_tune_table()
             io.text_valid = False  # do the task_text segment's outputs belong to the tokens of the last replay?
@@ -628,7 +669,7 @@ class GenimaACT:
         if io.stream is None:
             E.use_stream(cur)
         if io.exec is not None:
-            self._fill_execution(io, step, B)
+            self._fill_execution(io, step, io.ens_rows)
         guard = lang and E.hoist and "task_text" in E.segments
         run_text = True
         if lang:
@@ -658,6 +699,8 @@ class GenimaACT:
             if guard:
                 E.set_segment("task_text", True)  # a direct replay of io.engine always runs the whole program
         io.text_valid = True
+        if io.samples is not None:
+            self.last_samples = {"pick": io.ens_pick, "spread": io.ens_spread}
         return io
 
     def encode_clip_text(self, tokens: torch.Tensor):

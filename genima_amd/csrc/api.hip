@@ -292,6 +292,19 @@ int32_t gn_program_add_action_ensemble(gn_program* p, const void* chunk, int32_t
   if (chunk_f16) return RECORD(gn_action_ensemble_f16, chunk, state, steps, reset, out, B, T, A, ld, K, h, m);
   return RECORD(gn_action_ensemble, (const float*)chunk, state, steps, reset, out, B, T, A, ld, K, h, m);
 }
+int32_t gn_program_record_action_ensemble_samples(gn_program* p, const void* chunk, int64_t bs, int64_t ss, int32_t R, float inv_R, int32_t combine, void* state,
+                                               const int32_t* steps, const uint8_t* reset, float* out, int32_t* pick_out, float* spread_out, int32_t B,
+                                               int32_t T, int32_t A, int32_t ld, int32_t K, int32_t h, float m) {
+  GN_REQUIRE(p, "%s: null program", __func__);
+  // its state advances on every call: a replay that skipped it would execute a stale ring
+  GN_REQUIRE(p->open_seg < 0, "%s: recorded inside a guarded segment", __func__);
+  // as above: what makes the launch refuse is refused here
+  if (int32_t e = gn_check_action_ensemble_samples(p->ctx, __func__, chunk, bs, ss, R, inv_R, combine, state, steps, reset, out, pick_out, spread_out, B, T, A,
+                                                   ld, K, h, m))
+    return e;
+  GN_REQUIRE(gn_action_ensemble_state_bytes(B, T, A, K) > 0, "%s: bad shape (B %d, T %d, A %d, K %d)", __func__, B, T, A, K);
+  return RECORD(gn_action_ensemble_samples_f16, chunk, bs, ss, R, inv_R, combine, state, steps, reset, out, pick_out, spread_out, B, T, A, ld, K, h, m);
+}
 int32_t gn_program_add_fork(gn_program* p) { return push(p, __func__, make_op(Kind::Fork, "fork")); }
 int32_t gn_program_add_main(gn_program* p) { return push(p, __func__, make_op(Kind::Main, "main")); }
 int32_t gn_program_add_join(gn_program* p) { return push(p, __func__, make_op(Kind::Join, "join")); }

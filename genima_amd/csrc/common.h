@@ -130,3 +130,7 @@ int32_t gn_ppp_pool_init(int device);  // gemm_ppp.hip: the zero-initialised han
 int32_t gn_launch_attention(gn_ctx* ctx, const gn_attn_desc* d);
 int32_t gn_launch_groupnorm(gn_ctx* ctx, const gn_groupnorm_desc* d);
 int32_t gn_launch_tblock(gn_ctx* ctx, const gn_tblock_desc* d);
+// ensemble.hip: gn_action_ensemble_samples_f16's refusals without its launch (asked at record time)
+int32_t gn_check_action_ensemble_samples(gn_ctx* ctx, const char* who, const void* chunk, int64_t bs, int64_t ss, int32_t R, float inv_R, int32_t combine,
+                                         const void* state, const int32_t* steps, const uint8_t* reset, const float* out, const int32_t* pick_out,
+                                         const float* spread_out, int32_t B, int32_t T, int32_t A, int32_t ld, int32_t K, int32_t h, float m);

@@ -1614,6 +1614,36 @@ class Engine:
                                                 int(bool(temporal_agg)), float(m)), "gn_openloop_exec_actions")
         return out
 
+    def openloop_exec_actions_samples(self, chunks, first_tr, h: int, temporal_agg: bool = False, m: float = 0.01, *, combine: str = "mean",
+                                      A: Optional[int] = None, out=None, n_calls=None, pick=None, first_tr_host=None):
+        """``gn_openloop_exec_actions_samples``: ``openloop_exec_actions`` over the combination of R sampled chunks per transition.  ``chunks``
+        f16 [R, N, T, ld] (a seed run's table; any two leading strides, so a permuted [N, R, T, ld] is taken as it is), ``combine`` ``"mean"``
+        or ``"medoid"`` -> ``out`` f32 [N, A], bit for bit what ``action_ensemble(samples=R, combine=...)`` returns when it is called every
+        ``h`` steps of each episode.  ``pick``: int32 [N], the medoid's sample per transition (-1 under mean); under medoid one is allocated
+        where None is given -- the two launches hand the picks over through it.  Returns ``out``, or ``(out, pick)`` where a pick table
+        exists.  Eager engines only."""
+        who = "openloop_exec_actions_samples"
+        _eager_only(self, who, _SCORES_TABLES)
+        if not isinstance(chunks, torch.Tensor) or chunks.dim() != 4 or chunks.dtype != F16 or not chunks.is_cuda or chunks.stride(3) != 1:
+            raise GenimaHipError(f"{who}: chunks must be f16 [R, N, T, ld] on the device with contiguous rows")
+        R, N, T = (int(s) for s in chunks.shape[:3])
+        R, inv_R, rule = self._sample_args(who, R, combine)
+        A = int(chunks.shape[3]) if A is None else int(A)
+        if not 0 < A <= chunks.shape[3]:
+            raise GenimaHipError(f"{who}: A = {A} columns asked of chunks that hold {int(chunks.shape[3])}")
+        if out is None:
+            out = torch.empty((N, A), dtype=torch.float32, device=chunks.device)
+        if pick is None and rule == 1:
+            pick = torch.empty(N, dtype=torch.int32, device=chunks.device)
+        _expect_each(who, ((first_tr, torch.int32, (N,)), (out, torch.float32, (N, A))))
+        _expect_each(who, ((n_calls, torch.int32, (N,)), (pick, torch.int32, (N,))), optional=True)
+        self._first_tr_host(who, first_tr_host, N)
+        ss, ns, ld = (int(s) for s in chunks.stride()[:3])
+        check(self.lib.gn_openloop_exec_actions_samples(self._ctx, _ptr(chunks), ns, ss, R, inv_R, rule, _ptr(first_tr), _ptr(out), _ptr(n_calls),
+                                                        _ptr(pick), N, T, A, ld, int(h), int(bool(temporal_agg)), float(m)),
+              "gn_openloop_exec_actions_samples")
+        return out if pick is None else (out, pick)
+
     def openloop_exec_metrics(self, exec_actions, demo, first_tr, out=None, *, joint_scale=None, first_tr_host=None):
         """``gn_openloop_exec_metrics``: ``exec_actions`` f32 [N, A] (``openloop_exec_actions``) against ``demo`` f32 [N, A], the normalised
         demo action of each transition -> ``out`` f32 [N, 4] = (joint L1 sum over the A - 1 joints, gripper flag, executed jump from the step
@@ -1867,12 +1897,22 @@ class Engine:
         return torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
 
     def action_ensemble(self, chunk: torch.Tensor, state: torch.Tensor, steps: torch.Tensor, reset: torch.Tensor, h: int, K: int, m: float = 0.01, *,
-                        A: Optional[int] = None, out=None, name=None) -> torch.Tensor:
+                        A: Optional[int] = None, out=None, name=None, samples: Optional[int] = None, combine: str = "mean", pick=None,
+                        spread=None) -> torch.Tensor:
         """Temporal ensembling of overlapping action chunks (csrc/ensemble.hip; include/genima_hip.h states the rule): chunk f32 or f16
         [B, T, ld] of which the first ``A`` columns count, state from ``action_ensemble_state(B, T, A, K)``, steps int32 [B] and reset uint8 [B]
         on the device -> f32 [B, h, A], the actions of the environment steps ``steps[b] .. steps[b] + h - 1``.  The launch updates ``state``:
         recorded, it belongs outside every guarded segment (it has to run on every replay), and between replays only the contents of
-        ``steps`` / ``reset`` change."""
+        ``steps`` / ``reset`` change.
+
+        ``samples=R``: ``chunk`` holds R sampled f16 chunks per row -- [B * R, T, ld] (row ``b * R + r``) or [B, R, T, ld] with any two
+        leading strides (a permuted [R, B, T, ld] table is taken as it is) -- and their combination (``combine``: ``"mean"`` or ``"medoid"``)
+        enters the ring (``gn_action_ensemble_samples_f16``).  ``pick``: int32 [B] or None, the medoid's sample (-1 under mean); ``spread``:
+        f32 [B] or None, the samples' mean absolute distance from the executed chunk.  With ``samples=None`` the call is the one above."""
+        if samples is not None:
+            return self._action_ensemble_samples(chunk, state, steps, reset, h, K, m, A, out, name, samples, combine, pick, spread)
+        if combine != "mean" or pick is not None or spread is not None:
+            raise GenimaHipError("action_ensemble: combine / pick / spread belong to samples=R")
         B, T, ld = chunk.shape
         A = ld if A is None else int(A)
         if chunk.dtype not in (torch.float32, F16) or chunk.stride(2) != 1 or chunk.stride(0) != T * chunk.stride(1):
@@ -1895,4 +1935,47 @@ class Engine:
                    (chunk, state, steps, reset, out),
                    lambda: dict(kind="action_ensemble", flops=0.0, bytes=float(4 * B * A * (T + K * h + h) + chunk.element_size() * B * T * A), shape=()),
                    rec_args=(_ptr(chunk), int(f16), *args))
+        return out
+
+    COMBINE_RULES = ("mean", "medoid")  # gn_action_ensemble_samples_f16's ``combine`` argument is the index
+
+    @staticmethod
+    def _sample_args(who: str, samples, combine):
+        """-> (R, inv_R, combine index): R checked as an integer >= 1 (the library bounds it), inv_R = (float)(1.0 / R) rounded once, here."""
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+            raise GenimaHipError(f"{who}: samples must be an integer >= 1, got {samples!r}")
+        if combine not in Engine.COMBINE_RULES:
+            raise GenimaHipError(f"{who}: combine must be one of {Engine.COMBINE_RULES}, got {combine!r}")
+        return samples, float(torch.tensor(1.0 / samples, dtype=torch.float64).to(torch.float32)), Engine.COMBINE_RULES.index(combine)
+
+    def _action_ensemble_samples(self, chunk, state, steps, reset, h, K, m, A, out, name, samples, combine, pick, spread):
+        who = "action_ensemble"
+        R, inv_R, rule = self._sample_args(who, samples, combine)
+        if chunk.dim() == 3 and chunk.shape[0] % R == 0 and chunk.stride(0) == chunk.shape[1] * chunk.stride(1):
+            chunk4 = chunk.unflatten(0, (chunk.shape[0] // R, R))
+        else:
+            chunk4 = chunk
+        if chunk4.dim() != 4 or chunk4.shape[1] != R or chunk4.dtype != F16 or not chunk4.is_cuda or chunk4.stride(3) != 1:
+            raise GenimaHipError(f"{who}: with samples={R} chunk must be f16 [B * {R}, T, ld] or [B, {R}, T, ld] on the device with contiguous rows")
+        B, _, T, ld = (int(s) for s in chunk4.shape)
+        A = ld if A is None else int(A)
+        bs, ss, ld = (int(s) for s in chunk4.stride()[:3])
+        if self._seg_open is not None:
+            raise GenimaHipError(f"{who}: recorded inside segment {self._seg_open!r}; its state advances on every call, so it cannot be skipped")
+        need = int(self.lib.gn_action_ensemble_state_bytes(B, T, A, int(K)))
+        if (steps.dtype != torch.int32 or reset.dtype != torch.uint8 or steps.numel() != B or reset.numel() != B or state.dtype != torch.uint8
+                or not (steps.is_contiguous() and reset.is_contiguous() and state.is_contiguous()) or need <= 0 or state.numel() < need):
+            raise GenimaHipError(f"{who}: steps int32 [{B}], reset uint8 [{B}], state uint8 [>= {need}] expected (K {K})")
+        _expect(who, pick, torch.int32, (B,), optional=True)
+        _expect(who, spread, torch.float32, (B,), optional=True)
+        if out is None:
+            out = self.buf(name, (B, max(int(h), 1), A), dtype=torch.float32)
+        else:
+            _expect(who, out, torch.float32, (B, int(h), A))
+            self._wrote(out)
+        self._wrote(state, pick, spread)
+        args = (_ptr(chunk4), bs, ss, R, inv_R, rule, _ptr(state), _ptr(steps), _ptr(reset), _ptr(out), _ptr(pick), _ptr(spread), B, T, A, ld, int(K),
+                int(h), float(m))
+        self._emit("gn_action_ensemble_samples_f16", "gn_program_record_action_ensemble_samples", args, (chunk, state, steps, reset, out, pick, spread),
+                   lambda: dict(kind="action_ensemble_samples", flops=0.0, bytes=float(4 * B * A * (T + K * h + h) + 2 * B * R * T * A), shape=()))
         return out

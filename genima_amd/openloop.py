@@ -82,6 +82,7 @@ def _ratio(a, b, fill=np.nan) -> np.ndarray:
 
 
 EXEC_COLUMNS = ("joint_l1", "gripper", "jump", "demo_jump")  # gn_openloop_exec_metrics' four values per transition
+COMBINE_RULES = ("mean", "medoid")  # gn_openloop_exec_actions_samples' rules: execution row kinds ``seed_mean`` / ``seed_medoid``
 POINT_COLUMNS = ("n_views", "x", "y", "z", "err_m", "ray_rms_m", "reproj_rms_px", "det")  # gn_openloop_triangulate's eight values per (transition, group, kind)
 POINT_KINDS = ("generated", "ground_truth")
 MAX_GROUPS = 8  # gn_openloop_triangulate's bound on G
@@ -397,6 +398,10 @@ class OpenLoopResult:
             for where, sel in (("boundary", boundary), ("inside", inside)):
                 out[f"jump_{where}_{unit}"] = _mean(t[sel, 2] / J)
                 out[f"demo_jump_{where}_{unit}"] = _mean(t[sel, 3] / J)
+        p = tabs["picks"][rows].astype(np.int64) if "picks" in tabs else np.zeros(0, dtype=np.int64)
+        if p.size and int(p.min()) >= 0:  # the medoid's: which seed's chunk was executed (the mean's picks are -1)
+            out["pick_histogram"] = np.bincount(p, minlength=len(self.seeds)).tolist()
+            out["pick_is_seed0_rate"] = _mean(p == 0)
         return out
 
     def execution_summary(self) -> Optional[list]:
@@ -406,14 +411,21 @@ class OpenLoopResult:
         position ``s % h`` inside the call (how the error grows with the age of the prediction; None where no step has that position),
         ``jump_boundary_*`` / ``jump_inside_*``: the mean per-joint jump between consecutive executed actions where a new call takes over
         (``s % h == 0, s > 0``) and inside a call, beside ``demo_jump_*``, the demo's own over the same steps.  ``per_task``: the same per task
-        when there is more than one.  Open-loop like every score here: each chunk was predicted from a demo state."""
+        when there is more than one.  Open-loop like every score here: each chunk was predicted from a demo state.
+
+        With ``OpenLoopEval(combine=...)`` the row kinds ``seed_mean`` / ``seed_medoid`` stand beside ``generated`` (which is seed 0 alone): the
+        same scores of what the mode executes when the R seeds' chunks of every call are combined first (``GenimaACT.set_execution(samples=R,
+        combine=...)``).  ``seed_medoid`` also holds ``pick_histogram`` (how often each seed's chunk was the medoid, over the transitions)
+        and ``pick_is_seed0_rate``.  Still teacher-forced, still no success rate; a mean over seeds whose targets lie in different modes is an
+        action of neither mode -- the case the medoid exists for."""
         if self.executions is None:
             return None
         out = []
+        kinds = ("generated", "oracle") + tuple("seed_" + r for r in COMBINE_RULES)
         for ex in self.executions:
             h = int(ex["h"])
             d = {"h": h, "temporal_agg": bool(ex["temporal_agg"]), "m": float(ex["m"]), "K": int(ex["K"]), "calls_per_step": 1.0 / h}
-            d.update(self._over_tasks(lambda rows: {k: self._execution_block(ex[k], h, rows) for k in ("generated", "oracle") if k in ex}))
+            d.update(self._over_tasks(lambda rows: {k: self._execution_block(ex[k], h, rows) for k in kinds if k in ex}))
             out.append(d)
         return out
 
@@ -719,6 +731,13 @@ class OpenLoopEval:
     ``.seed_spheres`` / ``.seed_actions``, ``seed_summary()``).  It needs a diffusion agent and costs R generations per transition; with None
     nothing changes: the same launches, the same tables, the same bits.
 
+    ``combine``: None, ``"mean"``, ``"medoid"`` or a sequence of the two; it needs ``seeds`` and ``executions``.  After the last batch, per
+    execution setting and rule, ``gn_openloop_exec_actions_samples`` replays the setting over the COMBINATION of the R seeds' chunks of every
+    transition -- their mean in seed order, or their medoid -- bit for bit what ``GenimaACT.set_execution(..., samples=R, combine=)`` executes,
+    and ``gn_openloop_exec_metrics`` scores it twice; the tables ride in the same copy (``executions[i]["seed_mean" | "seed_medoid"]``:
+    ``actions``, ``n_calls``, ``picks``, ``scores``) and ``execution_summary()`` gets those row kinds beside ``generated``, which stays seed
+    0.  Still teacher-forced; a mean across two modes is an action of neither, which is what the medoid is for.  With None nothing changes.
+
     ``perturb``: None, a ``perturb.Perturbation``, a preset name or a spec (``perturb.parse``), drawn with ``perturb_seed``; the same as
     calling ``set_perturbation(perturb, perturb_seed)`` after the setup.  The clean host view tables are kept.  ``set_perturbation`` draws
     the values per episode (``perturb.draw``), recomputes the camera table (``perturb.perturb_cams``) and from it the windows -- with
@@ -742,11 +761,11 @@ class OpenLoopEval:
                  batch_size: int = 8, num_inference_steps: int = 5, guidance_scale: float = 0.0, seed: int = 0, engine=None,
                  change_threshold: int = 30, action_sequence: Optional[int] = None, executions=None, triangulate: bool = False,
                  tri_min_ratio: float = 0.5, tri_min_det: float = 1e-6, orientation=None, seeds: Optional[int] = None, seed_min_ratio: float = 0.5,
-                 perturb=None, perturb_seed: int = 0):
+                 perturb=None, perturb_seed: int = 0, combine=None):
         from .render import load_traj
 
         device, engine, T = self._check_options(diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions,
-                                                triangulate, tri_min_ratio, tri_min_det, orientation, seeds, seed_min_ratio)
+                                                triangulate, tri_min_ratio, tri_min_det, orientation, seeds, seed_min_ratio, combine)
         self.cfg, self.batch_size = render_cfg, int(batch_size)
         self.num_inference_steps, self.guidance_scale, self.seed = int(num_inference_steps), float(guidance_scale), int(seed)
         H, W = int(render_cfg.image_height), int(render_cfg.image_width)
@@ -773,7 +792,7 @@ class OpenLoopEval:
             self.set_perturbation(perturb, perturb_seed)
 
     def _check_options(self, diffusion_agent, controller, cameras, stats, engine, change_threshold, action_sequence, executions, triangulate,
-                       tri_min_ratio, tri_min_det, orientation, seeds=None, seed_min_ratio=0.5):
+                       tri_min_ratio, tri_min_det, orientation, seeds=None, seed_min_ratio=0.5, combine=None):
         """Part one of the setup, before any device work: every option checked and kept -> ``(device, engine, T)`` for the replay."""
         if controller is None:
             if diffusion_agent is None:
@@ -829,6 +848,14 @@ class OpenLoopEval:
             if not self.seed_min_ratio >= 0.0:
                 raise ValueError(f"OpenLoopEval: seed_min_ratio = {seed_min_ratio} must be >= 0")
             self.seeds = int(seeds)
+        self.combine = None
+        if combine is not None:  # the rules that turn the R seeds' chunks into the executed one, scored per execution setting
+            rules = (combine,) if isinstance(combine, str) else tuple(combine)
+            if not rules or len(set(rules)) != len(rules) or any(r not in COMBINE_RULES for r in rules):
+                raise ValueError(f"OpenLoopEval: combine is None or distinct rules out of {COMBINE_RULES}, got {combine!r}")
+            if self.seeds is None or self.executions is None:
+                raise ValueError("OpenLoopEval: combine scores the combination of the seeds' chunks under an execution mode: it needs seeds=R and executions=[...]")
+            self.combine = rules
         self.agent, self.controller, self.cameras, self.V, self.change_threshold = diffusion_agent, controller, tuple(cameras), len(cameras), int(change_threshold)
         if diffusion_agent is not None and self.V != 4:
             raise ValueError(f"OpenLoopEval: the 2x2 canvas takes exactly four cameras, got {self.V}")
@@ -1046,6 +1073,14 @@ class OpenLoopEval:
                 d[kind] = {"actions": acts, "n_calls": n_calls,
                            "scores": {"norm": E.openloop_exec_metrics(acts, self.replay.action, self.first_tr),
                                       "rad": E.openloop_exec_metrics(acts, self.replay.action, self.first_tr, joint_scale=self.joint_std)}}
+            for rule in self.combine or ():  # what the mode executes when the R seeds' chunks are combined first: the same two score launches
+                n_calls = torch.empty((N,), dtype=torch.int32, device=dev)
+                picks = torch.empty((N,), dtype=torch.int32, device=dev)
+                acts, _ = E.openloop_exec_actions_samples(tabs["seed"]["chunks"], self.first_tr, ex["h"], ex["temporal_agg"], ex["m"], combine=rule,
+                                                          n_calls=n_calls, pick=picks, first_tr_host=self.first_tr_host)
+                d["seed_" + rule] = {"actions": acts, "n_calls": n_calls, "picks": picks,
+                                     "scores": {"norm": E.openloop_exec_metrics(acts, self.replay.action, self.first_tr),
+                                                "rad": E.openloop_exec_metrics(acts, self.replay.action, self.first_tr, joint_scale=self.joint_std)}}
             out.append(d)
         return out
 

@@ -584,6 +584,38 @@ int32_t gn_action_ensemble(gn_ctx* ctx, const float* chunk, void* state, const i
 int32_t gn_action_ensemble_f16(gn_ctx* ctx, const void* chunk, void* state, const int32_t* steps, const uint8_t* reset, float* out, int32_t B, int32_t T,
                                int32_t A, int32_t ld, int32_t K, int32_t h, float m);
 
+/* ---- R sampled chunks combined into the one that is executed.  The diffusion stage draws noise, so R draws for one observation give R chunks;
+ * the combined chunk enters the ring above as the new chunk, and from there on the rule, the state blob and gn_action_ensemble_state_bytes are
+ * gn_action_ensemble's.  The combination, element e = t * A + a of a chunk (t < T, a < A), x_r the f16 sample r widened to f32:
+ *   mean    mean[e] = (x_0[e] + x_1[e] + .. + x_{R-1}[e]) * inv_R: f32 additions in sample order starting from x_0[e], then one multiplication by
+ *           inv_R, which must be (float)(1.0 / R) rounded once by the caller (any other value is refused) -- gn_openloop_seed_actions' mean_j, so
+ *           its seed_mean columns describe the chunk executed here
+ *   medoid  d(r, q) = sum_e |x_r[e] - x_q[e]|, D_r = sum_q d(r, q), pick = the lowest r with the smallest D_r; the combined chunk is sample
+ *           `pick` widened.  All A dimensions count alike, the gripper's included.  D_r is summed in f32 in ONE fixed order by the row's workgroup
+ *           of 256 threads: thread i adds its terms for q = 0 .. R - 1 (outer) and e = i, i + 256, .. < T * A (inner) to one f32 starting from 0;
+ *           within each wave of 64 lanes the 64 sums are added by the xor butterfly over lane distances 32, 16, 8, 4, 2, 1; then
+ *           D_r = ((w0 + w1) + w2) + w3 over the four waves.  Picks compare with <, from r = 0 up.  No atomics: equal inputs give equal picks in
+ *           both entry points below and on every run
+ *   spread  = (sum_r sum_e |x_r[e] - chosen[e]|) * inv_R / (float)(T * A): the samples' mean absolute disagreement with what is executed, in
+ *           normalised action units.  Three operations in this order: the sum (thread i adds e = i, i + 256, .. (outer), r = 0 .. R - 1 (inner);
+ *           butterfly and waves as for D_r), one multiplication by inv_R, one division by (float)(T * A)
+ * R = 1 under either rule is the sample itself: outputs and state bytes are gn_action_ensemble_f16's bit for bit (pick 0 under medoid, spread 0).
+ *
+ * gn_action_ensemble_samples_f16: one launch, one workgroup per row b, which stages the row's R * T * A values as f32 in LDS.
+ *   chunk    f16: sample r of row b is [T][ld] from chunk + b * bs + r * ss (elements).  [B][R]: bs = R * T * ld, ss = T * ld; [R][B]: bs = T * ld,
+ *            ss = B * T * ld
+ *   combine  0 = mean, 1 = medoid;  state, steps, reset, out, K, h, m as gn_action_ensemble takes them
+ *   pick_out int32 [B] or NULL: the pick, -1 under mean;  spread_out f32 [B] or NULL
+ *   The output pass takes the new slot's values from LDS, not from the ring: no thread reads a word of device memory another thread of the
+ *   launch writes.  Refused, launching nothing and leaving outputs and state as they were: whatever gn_action_ensemble_f16 refuses, R outside
+ *   [1, GN_ENSEMBLE_MAX_SAMPLES], R * T * A > GN_ENSEMBLE_MAX_STAGED, a wrong inv_R, combine outside {0, 1}, a misaligned pointer, negative
+ *   strides and strides under which two samples of (T - 1) * ld + A elements overlap. */
+#define GN_ENSEMBLE_MAX_SAMPLES 64
+#define GN_ENSEMBLE_MAX_STAGED 12288
+int32_t gn_action_ensemble_samples_f16(gn_ctx* ctx, const void* chunk, int64_t bs, int64_t ss, int32_t R, float inv_R, int32_t combine, void* state,
+                                       const int32_t* steps, const uint8_t* reset, float* out, int32_t* pick_out, float* spread_out, int32_t B, int32_t T,
+                                       int32_t A, int32_t ld, int32_t K, int32_t h, float m);
+
 /* ---- training-side kernels (ControlNet fine-tune step, diffusion/train_controlnet_genima.py:1317-1408) ----------
  * The backward matrix products reuse gn_gemm: dX = dY.W through a transposed weight copy, dW = dY^T.X through transposed
  * activations with GN_OUT_F32 + split-K, conv dgrad = conv with rotated weights, conv wgrad = GEMM over gn_im2col_t's image.
@@ -972,6 +1004,17 @@ int32_t gn_openloop_exec_actions(gn_ctx* ctx, const void* chunks, const int32_t*
                                  int32_t A, int32_t ld, int32_t h, int32_t temporal_agg, float m);
 int32_t gn_openloop_exec_metrics(gn_ctx* ctx, const float* exec, const float* demo, const int32_t* first_tr, const float* joint_scale, float* out, int32_t N,
                                  int32_t A);
+/* gn_openloop_exec_actions_samples: gn_openloop_exec_actions over the combined chunk of every transition (gn_action_ensemble_samples_f16 states
+ * the combination): bit for bit the rows that entry returns when it is called at t = 0, h, 2h, ... of each episode after a reset.
+ *   chunks   f16: sample r of transition n is [T][ld] from chunks + n * ns + r * ss (elements); an evaluation's [R][N] table has ns = T * ld,
+ *            ss = N * T * ld
+ *   pick_out int32 [N]: under medoid REQUIRED -- a first launch (one workgroup per transition, the shared pick) stores every transition's pick
+ *            there and the replay launch reads it; under mean optional, filled with -1
+ *   first_tr, exec, n_calls, h, temporal_agg, m as gn_openloop_exec_actions takes them.  Eager only.  Refused, launching nothing: what that entry
+ *   refuses, plus R, R * T * A, inv_R, combine, alignment and overlapping strides as gn_action_ensemble_samples_f16 refuses them. */
+int32_t gn_openloop_exec_actions_samples(gn_ctx* ctx, const void* chunks, int64_t ns, int64_t ss, int32_t R, float inv_R, int32_t combine,
+                                         const int32_t* first_tr, float* exec, int32_t* n_calls, int32_t* pick_out, int32_t N, int32_t T, int32_t A,
+                                         int32_t ld, int32_t h, int32_t temporal_agg, float m);
 
 /* gn_openloop_triangulate: where the drawn spheres are in the WORLD.  Each sphere is triangulated from the centroids of the views that found
  * it and compared with its true centre; one launch over the finished tables of a run.  All pointers but the two host copies are device memory.
@@ -1128,6 +1171,12 @@ int32_t gn_program_add_softmax_rows(gn_program* p, void* x, int64_t rows, int32_
 int32_t gn_program_add_maxpool3x3s2(gn_program* p, const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C);
 int32_t gn_program_add_action_ensemble(gn_program* p, const void* chunk, int32_t chunk_f16, void* state, const int32_t* steps, const uint8_t* reset,
                                        float* out, int32_t B, int32_t T, int32_t A, int32_t ld, int32_t K, int32_t h, float m);
+/* gn_action_ensemble_samples_f16 as a recorded op: exactly one op appended, none when refused.  Refused at record time, by this name: a NULL
+ * program, whatever the launch refuses, and a guarded segment that is open (the op's state advances on every call, so no replay may skip it)
+ * -- which no gn_program_add_* entry checks itself, hence the other name: those entries record inside a segment as they are told. */
+int32_t gn_program_record_action_ensemble_samples(gn_program* p, const void* chunk, int64_t bs, int64_t ss, int32_t R, float inv_R, int32_t combine, void* state,
+                                               const int32_t* steps, const uint8_t* reset, float* out, int32_t* pick_out, float* spread_out, int32_t B,
+                                               int32_t T, int32_t A, int32_t ld, int32_t K, int32_t h, float m);
 int32_t gn_program_add_image_normalize_u8(gn_program* p, const uint8_t* in, void* out, int64_t pixels, int32_t Cpad, float m0,
                                           float m1, float m2, float a0, float a1, float a2);
 int32_t gn_program_add_gather_rows(gn_program* p, const void* x, const int32_t* idx, void* out, int32_t B, int32_t L, int32_t D);

@@ -70,6 +70,8 @@ def main():
     ap.add_argument("--triangulate", action="store_true", help="also time whole runs without and with triangulate=True, and the triangulation launch")
     ap.add_argument("--orientation", action="store_true", help="also time whole runs without and with orientation=37, and the orientation launch")
     ap.add_argument("--seeds", type=int, default=None, metavar="R", help="also time whole runs without and with seeds=R, and the two seed-axis launches")
+    ap.add_argument("--combine", default=None, metavar="RULE[,RULE]",
+                    help="with --seeds: also time the sample-combined replay launches (mean, medoid) over the seed run's chunk table, at execution (5, agg)")
     ap.add_argument("--perturb", default=None, metavar="SPEC", help="also time one evaluator batch clean and under this perturbation, and the gn_view_perturb launch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -266,6 +268,14 @@ def main():
         res["seeds_extra_copy_bytes"] = int(seed_bytes - plain_bytes)
         launches["seed_spheres_us"] = lambda: E.openloop_seed_spheres(whole["spheres"], s_sph, min_ratio=ev_seeds.seed_min_ratio)
         launches["seed_actions_us"] = lambda: E.openloop_seed_actions(whole["chunks"], whole["demo"], s_act["rad"], joint_scale=ev_seeds.joint_std)
+        if args.combine is not None:  # the launches OpenLoopEval(combine=...) adds per execution setting and rule (two score launches follow each)
+            c_out = torch.empty((ev_seeds.N, ev_seeds.A), dtype=torch.float32, device=E.device)
+            c_pick = torch.empty((ev_seeds.N,), dtype=torch.int32, device=E.device)
+            c_first = torch.zeros((ev_seeds.N,), dtype=torch.int32, device=E.device)  # one long episode: the most calls per step
+            res["combine"] = [r.strip() for r in args.combine.split(",")]
+            for rule in res["combine"]:
+                launches[f"exec_actions_samples_{rule}_us"] = lambda rule=rule: E.openloop_exec_actions_samples(whole["chunks"], c_first, 5, True, combine=rule,
+                                                                                                                out=c_out, pick=c_pick)
     if args.perturb is not None:
         from genima_amd import perturb as PB
 

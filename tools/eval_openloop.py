@@ -27,7 +27,11 @@ per seed with its mean and seed-to-seed standard deviation -- the noise floor a 
 the bias of the seeds' mean centroid beside their spread about it (``variance_share``: 0 all bias, 1 all noise) and, with a controller, the
 error of the seed-averaged chunk beside the mean of the seeds' errors (``gain``; ``OpenLoopResult.seed_summary``).  Everything outside that
 block stays the first seed's, as without the option; the run costs R generations per transition.  A seed spread is not a success rate either,
-and ``gain`` is teacher-forced: nothing executes an averaged chunk.
+and ``gain`` is teacher-forced: it measures an averaged chunk that only ``--combine`` below replays.
+``--combine mean,medoid`` (with ``--seeds`` and ``--execution``) adds, per execution setting, the row kinds ``seed_mean`` / ``seed_medoid`` beside
+``generated`` (seed 0): the same scores of what the mode executes when the R seeds' chunks of every call are combined first, as
+``GenimaACT.set_execution(samples=R, combine=...)`` does in the control loop; the medoid's rows also carry ``pick_histogram`` and
+``pick_is_seed0_rate``.  Still teacher-forced and no success rate; averaging across modes is the known failure the medoid exists for.
 ``--perturb SPEC`` (repeatable; a preset ``camera_pose`` / ``light_color``, a spec such as ``camera:pitch=-0.05..0.05,zoom=0.95..1.05`` or
 ``light:r=0.5..1,g=0.5..1,b=0.5..1``, two joined by ``+``; ``genima_amd.perturb.parse``) also runs ``openloop.robustness_sweep`` after the clean
 run -- the same evaluator under each setting, drawn per episode with ``--perturb_seed`` -- and writes it beside the result as
@@ -78,6 +82,8 @@ def parse(argv=None):
                     help="also read the orientation the generated spheres show: K (odd, at most 64) candidate rotations over span degrees (default 180)")
     ap.add_argument("--seeds", type=int, default=None, metavar="R",
                     help="also repeat the generation with R (2 .. 64) generator seeds, --seed .. --seed + R - 1: per-score seed spread, per-sphere bias and spread")
+    ap.add_argument("--combine", default=None, metavar="RULE[,RULE]",
+                    help="with --seeds and --execution: also score what each mode executes when the seeds' chunks are combined first, by 'mean', 'medoid' or both")
     ap.add_argument("--seed_min_ratio", type=float, default=0.5, help="with --seeds: a seed found a sphere when its mass is at least this share of the ground truth's")
     ap.add_argument("--perturb", action="append", default=None, metavar="SPEC",
                     help="also score under this camera-pose / light perturbation (a preset, a spec, or two joined by '+'); repeatable; written to <out>.robustness.json")
@@ -97,6 +103,12 @@ def parse(argv=None):
             ap.error(str(err))
     if a.seeds is not None and not 2 <= a.seeds <= 64:
         ap.error(f"--seeds {a.seeds}: the number of generator seeds must lie in [2, 64]")
+    if a.combine is not None:
+        a.combine = tuple(r.strip() for r in a.combine.split(","))
+        if a.seeds is None or a.execution is None:
+            ap.error("--combine scores the combined chunk of the seeds under an execution mode: it needs --seeds and --execution")
+        if not a.combine or len(set(a.combine)) != len(a.combine) or any(r not in ("mean", "medoid") for r in a.combine):
+            ap.error(f"--combine {','.join(a.combine)}: distinct rules out of mean, medoid expected")
     if a.perturb is not None:
         from genima_amd import perturb as PB
 
@@ -152,7 +164,7 @@ def main(argv=None):
     ev = OpenLoopEval(dagent, controller, episodes, a.cameras, render_cfg=rcfg, stats=stats, tokenizer=tokenizer, batch_size=a.batch_size,
                       num_inference_steps=a.num_inference_steps, guidance_scale=a.guidance_scale, seed=a.seed, change_threshold=a.change_threshold,
                       action_sequence=a.action_sequence, executions=a.execution, triangulate=a.triangulate, tri_min_ratio=a.tri_min_ratio,
-                      tri_min_det=a.tri_min_det, orientation=a.orientation, seeds=a.seeds, seed_min_ratio=a.seed_min_ratio)
+                      tri_min_det=a.tri_min_det, orientation=a.orientation, seeds=a.seeds, seed_min_ratio=a.seed_min_ratio, combine=a.combine)
     print(f"eval_openloop: {len(episodes)} episodes, {ev.N} transitions, {ev.replay.device_bytes / 1e6:.0f} MB of frames on the device", flush=True)
     summary = ev.run().to_json(a.out)
     print(json.dumps(summary, indent=1))
