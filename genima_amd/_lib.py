@@ -263,6 +263,7 @@ SIGNATURES = {
     "gn_openloop_seed_spheres": (_I32, [_P, _P, _P, _D, _I32, _I32, _I32, _I32]),
     "gn_openloop_seed_actions": (_I32, [_P, _P, _I32, _P, _P, _P, _F, _I32, _I32, _I32, _I32]),
     "gn_view_perturb": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32]),
+    "gn_view_augment_tiled": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _F]),
     "gn_gather_rows": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32]),
     "gn_argmax_rows_i32": (_I32, [_P, _P, _P, _I32, _I32]),
     "gn_copy4d": (_I32, [_P, _P, _P, _P, _P, _P, _I32]),

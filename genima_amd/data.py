@@ -179,9 +179,14 @@ def _to_device_cached(E, batch) -> Dict[str, torch.Tensor]:
 def _to_device_rendered(E, batch) -> Dict[str, torch.Tensor]:
     """A ``DataLoader(render_targets=...)`` batch: the conditioning frames (uploaded, or where they lie in the device cache, through the
     same pointer table ``gn_gather_u8_to_f16`` reads) are the tiled backgrounds over which ``gn_render_spheres`` draws the targets,
-    straight into the f16 NHWC-8 ``pixel_values``.  The view arrays were packed and pinned by the producer thread."""
+    straight into the f16 NHWC-8 ``pixel_values``.  The view arrays were packed and pinned by the producer thread.
+
+    Where the views carry ``M`` (``DataLoader(view_augment=...)``): one ``gn_view_augment_tiled`` launch reads the same frames, writes the
+    warped and tinted tiled uint8 background, ``conditioning_pixel_values`` directly (scale (1, 0)) and the ``view_revealed`` table; the
+    spheres are then drawn over that background with the perturbed cameras.  Without ``M`` the launches are the ones above."""
     dev, src = E.device, batch["render_source"]
     views = [batch["render_views"][k].to(dev, non_blocking=True) for k in ("cams", "spheres", "tex_index", "count")]
+    aug = "M" in batch["render_views"]
     if "frame_slots" in batch:
         cache, R = batch["frame_cache"], int(batch["resolution"])
         cache.upload(dev, R, batch["frame_uploads"])
@@ -192,15 +197,23 @@ def _to_device_rendered(E, batch) -> Dict[str, torch.Tensor]:
         ptrs = torch.tensor([staging.data_ptr() + i * fb if c < 0 else cache.address(R, c, i) for c, i in batch["frame_slots"].tolist()],
                             dtype=torch.int64)
         ptrs = (ptrs.pin_memory() if torch.cuda.is_available() else ptrs).to(dev, non_blocking=True)
-        B, bg = ptrs.numel(), dict(bg_frames=ptrs)
-        cond = E.gather_u8_to_f16(ptrs, (R, R), 8, 1.0, 0.0)
+        B, bg, source = ptrs.numel(), dict(bg_frames=ptrs), dict(frames=ptrs)
+        cond = None if aug else E.gather_u8_to_f16(ptrs, (R, R), 8, 1.0, 0.0)
     else:
         cd = batch["conditioning_pixel_values_u8"].to(dev, non_blocking=True)
-        B, bg = cd.shape[0], dict(bg=cd)
-        cond = E.image_u8_to_f16(cd, 8, 1.0, 0.0)
+        B, bg, source = cd.shape[0], dict(bg=cd), dict(src=cd)
+        cond = None if aug else E.image_u8_to_f16(cd, 8, 1.0, 0.0)
+    out = {}
+    if aug:
+        M, colour = (batch["render_views"][k].to(dev, non_blocking=True) for k in ("M", "colour"))
+        warped = torch.empty((B, 2 * src.H, 2 * src.W, 3), dtype=torch.uint8, device=dev)
+        cond = torch.empty((B, 2 * src.H, 2 * src.W, 8), dtype=torch.float16, device=dev)
+        out["view_revealed"] = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        E.view_augment_tiled(M, colour, src.H, src.W, out_u8=warped, out_f16=cond, scale=(1.0, 0.0), n_revealed=out["view_revealed"], **source)
+        bg = dict(bg=warped)
     px = torch.empty((B, 2 * src.H, 2 * src.W, 8), dtype=torch.float16, device=dev)
     E.render_spheres(*views, src.atlas_on(dev), src.H, src.W, src.samples, bg_tiled=True, n_tiled=B, full_f16=px, full_scale=(2.0, -1.0), **bg)
-    return {"pixel_values": px, "conditioning_pixel_values": cond, "input_ids": batch["input_ids"].to(dev, non_blocking=True)}
+    return {"pixel_values": px, "conditioning_pixel_values": cond, "input_ids": batch["input_ids"].to(dev, non_blocking=True), **out}
 
 
 class FrameCache:
@@ -351,17 +364,48 @@ class DataLoader:
     ``render_targets`` (a ``render.TrajectorySource``; off by default): the target image of a sample is not read from its PNG but drawn on
     the device -- the trajectory's spheres over the sample's conditioning frame (``gn_render_spheres``, in ``to_device`` / ``train_step``) --
     so only the conditioning frames are decoded, and cached when ``cache`` is on.  For datasets whose targets are the rendering of their own
-    conditioning frame (the tiled ``tiled_rgb`` / ``tiled_rgb_rendered`` pair without ``predict_future``)."""
+    conditioning frame (the tiled ``tiled_rgb`` / ``tiled_rgb_rendered`` pair without ``predict_future``).
+
+    ``view_augment`` (a ``perturb.Perturbation``, a spec string or a preset name, read through ``perturb.parse``; off by default; needs
+    ``render_targets``): the camera-pose and light perturbation the open-loop evaluator measures with (``OpenLoopEval(perturb=...)``), as a
+    train-time augmentation with re-drawn targets.  With probability ``view_augment_prob`` a sample's four views are perturbed: the
+    OBSERVATION is warped by the homography of its turned camera and tinted by the light's gain and offset (``gn_view_augment_tiled``,
+    in ``to_device`` / ``train_step``), and the target's spheres are drawn UNTINTED over that frame from the turned camera's table -- the
+    spheres are the signal, not scene, as DESIGN 3.19 argues for the evaluator.  The border the turned camera reveals is MIRRORED scene, not
+    what it would have seen there; the batch's ``view_revealed`` (int32 [B, 4] on the device, read back by nothing here) counts it.  A
+    sphere that leaves a view is simply not in that view's target.  The rotation and a change of intrinsics are exact, the light is an
+    image-space stand-in, a camera translation is left out, and the ranges are the caller's choice (``perturb.py``).
+
+    A sample's draw is a pure function of ``(view_augment_seed, epoch, dataset index)`` (``perturb.sample_tables``), ``epoch`` the value
+    the epoch's shuffle used and ``view_augment_seed=None`` the loader's ``seed``: it does not depend on the batch size or composition, the
+    rank, the world size, ``prefetch``, ``decode_workers`` or the cache, and a sample the data-parallel tail repeats gets the same draw.
+    The producer thread computes the tables (``M``, ``colour`` and the perturbed ``cams`` in ``render_views``) and launches nothing.
+    ``--augmentations`` of the trainer run afterwards, as before; the change mask of ``sphere_loss_weight`` / ``loss_parts`` is taken
+    between the warped target and the warped frame.  A held-out loader (``eval_loss``) is unaffected as long as it sets no ``view_augment``."""
 
     MAX_DECODE_WORKERS = 16  # a fixed cap, never the machine's CPU count: a training host runs one loader per GPU
 
     def __init__(self, dataset, batch_size: int, tokenizer, resolution: int, shuffle: bool = True, seed: int = 0, prefetch: int = 2,
                  proportion_empty_prompts: float = 0.0, rank: int = 0, world: int = 1, cache=None, cache_bytes: int = 8 << 30,
-                 decode_workers: int = 1, render_targets=None):
+                 decode_workers: int = 1, render_targets=None, view_augment=None, view_augment_prob: float = 1.0,
+                 view_augment_seed: Optional[int] = None):
         self.ds, self.bs, self.tok, self.res = dataset, batch_size, tokenizer, resolution
         self.render_targets = render_targets
         if render_targets is not None and (resolution != 2 * render_targets.H or resolution != 2 * render_targets.W):
             raise ValueError(f"render_targets draws {2 * render_targets.H} x {2 * render_targets.W} tiled targets: resolution must be that, not {resolution}")
+        self.view_augment = None
+        if not 0.0 <= float(view_augment_prob) <= 1.0:  # (a NaN fails the comparison)
+            raise ValueError(f"view_augment_prob = {view_augment_prob} must lie in [0, 1]")
+        if view_augment is not None:
+            from . import perturb
+
+            if render_targets is None:
+                raise ValueError("view_augment needs render_targets: without the trajectory there is no camera to turn and no target to re-draw")
+            self.view_augment = perturb.parse(view_augment)
+        self.view_augment_prob = float(view_augment_prob)
+        self.view_augment_seed = int(seed if view_augment_seed is None else view_augment_seed)
+        if self.view_augment is not None and self.view_augment_seed < 0:
+            raise ValueError(f"view_augment_seed = {self.view_augment_seed} must not be negative (it is part of a numpy seed sequence)")
         self.shuffle, self.seed, self.prefetch, self.pep = shuffle, seed, max(0, prefetch), proportion_empty_prompts
         self.rank, self.world, self.epoch = rank, world, 0
         self.cache = FrameCache(cache, cache_bytes) if isinstance(cache, str) else cache
@@ -406,7 +450,7 @@ class DataLoader:
     def _decode_all(self, jobs) -> List[np.ndarray]:
         return list(self._pool.map(self._decode, jobs)) if self._pool is not None and len(jobs) > 1 else [self._decode(j) for j in jobs]
 
-    def _make(self, ix: List[int]) -> Dict[str, object]:
+    def _make(self, ix: List[int], epoch: int = 0) -> Dict[str, object]:
         R, cache = self.res, self.cache
         meta = [self._sources(i) for i in ix]
         uses = [m[1][role] for role in (0, 1) for m in meta]  # the order collate_u8 decodes in: every target, then every conditioning image
@@ -414,7 +458,17 @@ class DataLoader:
         if self.render_targets is not None:  # the targets are drawn on the device from the conditioning frames: those alone are decoded
             uses = uses[len(meta):]
             packed = [v for path, _ in uses for v in self.render_targets.views(path)]
-            rendered = {"cams": torch.from_numpy(np.stack([v[0] for v in packed])), "spheres": torch.from_numpy(np.stack([v[1] for v in packed])),
+            cams, tables = np.stack([v[0] for v in packed]), {}  # a stacked copy: TrajectorySource memoises its views and they stay clean
+            if self.view_augment is not None:
+                from . import perturb
+                from .render import tile_cameras
+
+                names = tile_cameras(self.render_targets.cfg.cameras)
+                drawn = [perturb.sample_tables(self.view_augment, cams[4 * k:4 * k + 4], names, (self.view_augment_seed, epoch, i),
+                                               self.view_augment_prob) for k, i in enumerate(ix)]
+                cams = np.concatenate([d[0] for d in drawn])
+                tables = {"M": torch.from_numpy(np.stack([d[1] for d in drawn])), "colour": torch.from_numpy(np.stack([d[2] for d in drawn]))}
+            rendered = {**tables, "cams": torch.from_numpy(cams), "spheres": torch.from_numpy(np.stack([v[1] for v in packed])),
                         "tex_index": torch.from_numpy(np.stack([v[2] for v in packed]).astype(np.int32)),
                         "count": torch.tensor([v[3] for v in packed], dtype=torch.int32)}
             if torch.cuda.is_available():
@@ -472,13 +526,14 @@ class DataLoader:
         return {"pixel_values_u8": out[:B], "conditioning_pixel_values_u8": out[B:], "input_ids": ids.pin_memory() if pin else ids}
 
     def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
+        epoch = self.epoch  # the value the shuffle below uses: part of a view_augment draw's key
         batches = self._batches()
         self.epoch += 1
 
         def make(ix):
             if self.cache is None and self._pool is None and self.render_targets is None:
                 return collate_u8([self.ds[i] for i in ix], self.tok, self.res, self.pep)
-            return self._make(ix)
+            return self._make(ix, epoch)
 
         if self.prefetch == 0:
             for ix in batches:

@@ -1744,6 +1744,30 @@ class Engine:
         check(self.lib.gn_view_perturb(self._ctx, _ptr(src), _ptr(out), _ptr(valid), _ptr(n_revealed), _ptr(M), _ptr(colour), B, H, W), "gn_view_perturb")
         return out
 
+    def view_augment_tiled(self, M, colour, H: int, W: int, *, src=None, frames=None, out_u8=None, out_f16=None, scale=(1.0, 0.0), valid=None,
+                           n_revealed=None):
+        """``gn_view_augment_tiled``: ``view_perturb``'s rule over n 2 x 2 tiled frames, every ``H`` x ``W`` tile an independent view.  The
+        source is ``src`` uint8 [n, 2H, 2W, 3] or ``frames``, a DEVICE int64 [n] tensor of the addresses of such frames (4-byte aligned,
+        repeats allowed, anywhere on the device: the frame cache's pointer table; no output may overlap a frame) -- exactly one of them.
+        ``M`` f64 [n, 4, 9] and ``colour`` f64 [n, 4, 6] are indexed by frame, then tile.  Outputs, written where given: ``out_u8`` uint8
+        [n, 2H, 2W, 3] (``render_spheres`` takes it as ``bg`` with ``bg_tiled``), ``out_f16`` f16 [n, 2H, 2W, 8] = ``image_u8_to_f16`` of those
+        bytes with ``scale`` = (mul, add), ``valid`` uint8 [n, 2H, 2W], ``n_revealed`` int32 [n, 4] (zeroed and summed by the call).  With
+        neither ``out_u8`` nor ``out_f16`` given, ``out_u8`` is allocated.  Returns ``(out_u8, out_f16)``.  Eager engines only."""
+        who = "view_augment_tiled"
+        _eager_only(self, who, "the matrices and the frame addresses change from batch to batch")
+        if not isinstance(M, torch.Tensor) or M.dim() != 3 or (src is None) == (frames is None):
+            raise GenimaHipError(f"{who}: M must be f64 [n, 4, 9] and exactly one of src and frames must be given")
+        n, H, W = int(M.shape[0]), int(H), int(W)
+        tiled = (n, 2 * H, 2 * W)
+        if out_u8 is None and out_f16 is None:
+            out_u8 = torch.empty(tiled + (3,), dtype=torch.uint8, device=M.device)
+        _expect_each(who, ((M, torch.float64, (n, 4, 9)), (colour, torch.float64, (n, 4, 6))))
+        _expect_each(who, ((src, torch.uint8, tiled + (3,)), (frames, torch.int64, (n,)), (out_u8, torch.uint8, tiled + (3,)), (out_f16, F16, tiled + (8,)),
+                           (valid, torch.uint8, tiled), (n_revealed, torch.int32, (n, 4))), optional=True)
+        check(self.lib.gn_view_augment_tiled(self._ctx, _ptr(src), _ptr(frames), _ptr(out_u8), _ptr(out_f16), _ptr(valid), _ptr(n_revealed), _ptr(M),
+                                             _ptr(colour), n, H, W, float(scale[0]), float(scale[1])), "gn_view_augment_tiled")
+        return out_u8, out_f16
+
     def render_spheres(self, cams, spheres, tex_index, count, atlas, H: int, W: int, samples: int = 4, *, bg=None, bg2=None, blend=None,
                        tile_index=None, bg_frames=None, bg_tiled: bool = False, n_tiled: int = 0, full=None, rnd=None, occupied=None, full_f16=None,
                        rnd_f16=None, full_scale=(2.0, -1.0), rnd_scale=(1.0, 0.0)):

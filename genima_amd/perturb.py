@@ -187,7 +187,7 @@ def parse(text) -> Perturbation:
     return p if len(parts) == 1 else dataclasses.replace(p, name=text)
 
 
-def draw(p: Perturbation, n_episodes: int, cameras: Sequence[str], seed: int = 0) -> Dict[str, np.ndarray]:
+def draw(p: Perturbation, n_episodes: int, cameras: Sequence[str], seed: int = 0, rng=None) -> Dict[str, np.ndarray]:
     """The values of one evaluation -> ``{"pitch" | "yaw" | "roll" | "zoom" | "shift_x" | "shift_y": f64 [E, V], "gain" | "offset": f64
     [E, 3]}``, E episodes and V cameras.
 
@@ -195,9 +195,13 @@ def draw(p: Perturbation, n_episodes: int, cameras: Sequence[str], seed: int = 0
     shift_y with size (E, V); then gain r, g, b and offset r, g, b with size (E,) each.  Every call is made whatever the ranges are, so a
     value does not depend on which other ranges are fixed (``uniform(v, v)`` returns v exactly).  The camera values are per (episode, camera); a camera outside ``p.cameras``
     is set to the identity after the draw.  The colour values are per EPISODE and shared by that episode's views: it is the scene's light.
-    Every transition of an episode uses its episode's draw, as Colosseum randomises per episode."""
+    Every transition of an episode uses its episode's draw, as Colosseum randomises per episode.
+
+    ``rng``: a ``numpy.random.Generator`` to ask instead, in the same order (``seed`` is then not used): ``sample_tables`` draws its coin
+    from the generator first."""
     E, V = int(n_episodes), len(cameras)
-    rng = np.random.default_rng(int(seed))
+    if rng is None:
+        rng = np.random.default_rng(int(seed))
     out = {k: rng.uniform(*getattr(p, k), size=(E, V)) for k in CAMERA_KEYS}
     if p.cameras is not None:
         off = np.asarray([c not in p.cameras for c in cameras], bool)
@@ -287,6 +291,35 @@ def transition_tables(p: Perturbation, cams, episode_of, n_episodes: int, camera
     colour = np.concatenate([d["gain"], d["offset"]], axis=1)[ep]  # [N, 6]
     colour = np.ascontiguousarray(np.broadcast_to(colour[:, None, :], cams.shape[:2] + (6,)))
     return np.ascontiguousarray(new), np.ascontiguousarray(homography(cams, new)), colour, d
+
+
+def sample_tables(p: Perturbation, cams, cameras: Sequence[str], key, prob: float = 1.0):
+    """The train-time augmentation's part on the host (``data.DataLoader(view_augment=...)``): one sample's clean f32 camera table [4, 18],
+    its rows in the order of ``cameras``, -> ``(cams_new f32 [4, 18], M f64 [4, 9], colour f64 [4, 6], applied)``.
+
+    ``key``: a tuple of non-negative ints; the draw is a pure function of it.  ``rng = numpy.random.default_rng(list(key))``; FIRST ``applied
+    = rng.random() < prob``, drawn whatever ``prob`` is, so the values below do not depend on ``prob``; then ``draw(p, 1, cameras,
+    rng=rng)``.  ``cams_new = perturb_cams(...)``, ``M = homography(cams, cams_new)``, and the colour row is shared by the four views: it is
+    the scene's light.  Not applied: the input camera bits and the identity of both parts.  A camera outside ``p.cameras`` keeps its bits and
+    the identity matrix (the ``camera_pose`` preset leaves the wrist alone); the light still reaches it."""
+    cams = np.ascontiguousarray(cams)
+    V = len(cameras)
+    if cams.dtype != np.float32 or cams.shape != (V, 18):
+        raise ValueError(f"sample_tables: cams must be f32 [{V}, 18], got {cams.dtype} {cams.shape}")
+    key = [int(k) for k in key]
+    if not key or min(key) < 0:
+        raise ValueError(f"sample_tables: key = {key} must be a non-empty tuple of non-negative ints")
+    if not 0.0 <= float(prob) <= 1.0:
+        raise ValueError(f"sample_tables: prob = {prob} must lie in [0, 1]")
+    rng = np.random.default_rng(key)
+    applied = bool(rng.random() < float(prob))
+    d = draw(p, 1, cameras, rng=rng)
+    if not applied:
+        return cams.copy(), np.tile(np.eye(3).reshape(1, 9), (V, 1)), np.tile(np.array([[1.0, 1.0, 1.0, 0.0, 0.0, 0.0]]), (V, 1)), False
+    new = np.ascontiguousarray(perturb_cams(cams, rotation(d["pitch"][0], d["yaw"][0], d["roll"][0]), d["zoom"][0],
+                                            np.stack([d["shift_x"][0], d["shift_y"][0]], axis=-1)))
+    colour = np.ascontiguousarray(np.broadcast_to(np.concatenate([d["gain"][0], d["offset"][0]])[None, :], (V, 6)))
+    return new, np.ascontiguousarray(homography(cams, new)), colour, True
 
 
 def draw_ranges(draws: Dict[str, np.ndarray]) -> Dict:

@@ -1124,6 +1124,32 @@ int32_t gn_openloop_seed_actions(gn_ctx* ctx, const void* chunks, int32_t ld, co
 int32_t gn_view_perturb(gn_ctx* ctx, const uint8_t* src, uint8_t* dst, uint8_t* valid, int32_t* n_revealed, const double* M, const double* colour,
                         int32_t B, int32_t H, int32_t W);
 
+/* gn_view_perturb's rule over the trainer's frames (genima_amd/data.py DataLoader(view_augment=...)): n frames of 2 x 2 tiled views
+ * (tiling.py order: tile t at tile row t / 2, tile column t % 2), every tile an independent H x W view with its own matrix and colour row.
+ * All pointers are device memory.  Exactly one source is given:
+ *   src       uint8 [n][2H][2W][3], stacked frames, or
+ *   frames    a DEVICE array (8-byte aligned) of n device pointers to such tiled frames: they may be 4-byte aligned, may repeat and may lie
+ *             anywhere (the table gn_gather_u8_to_f16 and gn_render_desc::bg_frames read).  THE CALLER GUARANTEES that no output overlaps a
+ *             frame; nothing here can check it.
+ *   M         f64 [n][4][9], 8-byte aligned;  colour f64 [n][4][6], 8-byte aligned: indexed by frame i, then tile t
+ * Output tile t of frame i is gn_view_perturb's rule, steps 1 to 10 above with the TILE's H and W, applied to source tile t of frame i with
+ * M[i][t] and colour[i][t]: pixel (x, y) of the tile is pixel ((t % 2) W + x, (t / 2) H + y) of the frame, source and output alike.  The fold
+ * of step 9 and the clamp of step 8 act INSIDE the tile: no sample ever reads a neighbouring tile.
+ * Outputs, each may be NULL, at least one of dst and dst_f16 is not:
+ *   dst       uint8 [n][2H][2W][3]: the warped and re-coloured tiled frames (gn_render_spheres takes them as bg with bg_tiled)
+ *   dst_f16   f16 [n][2H][2W][8], 16-byte aligned: each byte dst would hold, converted as gn_image_u8_to_f16 converts it,
+ *             (f16)((float)v / 255 * mul + add); channels 3 .. 7 are zero
+ *   valid     uint8 [n][2H][2W]: step 7's valid of every pixel
+ *   n_revealed int32 [n][4], 4-byte aligned: per (frame, tile) the number of pixels with valid == 0.  Zeroed by the call on the ctx stream,
+ *             then summed per workgroup and added with one integer atomicAdd each: order-independent, same bits
+ * With the identity matrix, gain 1 and offset 0 dst is a copy of the source and dst_f16 is gn_image_u8_to_f16 of it, bit for bit.  In
+ * general dst, valid and n_revealed equal gn_view_perturb on the untiled views, put back into the tiling, bit for bit.
+ * Refused, launching nothing and leaving the outputs as they were: a NULL ctx, M or colour; both of src and frames, or neither; dst and
+ * dst_f16 both NULL; n, H or W <= 0; 4 n > 65535; n * 2H * 2W * 3 >= 2^31; a misaligned M, colour, frames, n_revealed or dst_f16; with
+ * src, a dst that overlaps it (dst == src included); a mul or add that is not finite.  Eager only. */
+int32_t gn_view_augment_tiled(gn_ctx* ctx, const uint8_t* src, const uint8_t* const* frames, uint8_t* dst, void* dst_f16, uint8_t* valid,
+                              int32_t* n_revealed, const double* M, const double* colour, int32_t n, int32_t H, int32_t W, float mul, float add);
+
 /* ---- op programs: record once, replay on the stream (eagerly or as a captured hipGraph) ---------------------------
  * The host classes (UNet2DConditionModel / ControlNetModel / AutoencoderKL / pipeline) lower a forward pass to a flat list of
  * the ops above with all buffers pre-allocated, so the 5-step denoise loop runs without returning to Python. */

@@ -7,13 +7,16 @@
   * ms per loader-fed ``train_step`` of the SD-Turbo family for ``cache=None`` against ``cache="device"`` from epoch 2 on, and per step on one
     resident synthetic batch (what bench_train.py times), all three alternating in one process; with ``--render-textures DIR`` also, in the
     same alternation, ``cache="device"`` on a tree that ``render_episode`` wrote against the same loader with ``render_targets`` (targets
-    drawn on the device instead of read).
+    drawn on the device instead of read); with ``--view-augment SPEC`` on top of that, in the same alternation, that ``render_targets``
+    loader with ``view_augment=SPEC`` (the camera-pose and light augmentation with re-drawn targets), its difference to the loader without it
+    beside that loader's own spread, us of ``gn_view_augment_tiled`` alone on one of its batches beside the bytes it moves, and the share of
+    pixels the turned cameras reveal.
 
 The frames are generated (smooth structure + sensor noise, ~400 KB per 512^2 PNG); real renders compress better and decode faster.  Every
 setting is timed ``--rounds`` times, alternating, after a warm-up epoch; the spread over the rounds is printed beside the median.  Needs an
 MI355X.
 
-    python tools/bench_loader.py [--batch 8] [--resolution 512] [--examples 64] [--rounds 3] [--no-train] [--render-textures DIR] [--out bench_loader.json]
+    python tools/bench_loader.py [--batch 8] [--resolution 512] [--examples 64] [--rounds 3] [--no-train] [--render-textures DIR] [--view-augment SPEC] [--out bench_loader.json]
 """
 import argparse
 import json
@@ -96,8 +99,12 @@ def main():
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--render-textures", default=None, help="directory of the five sphere textures: also time a loader whose targets are drawn "
                     "on the device (DataLoader(render_targets=...)) against cache=\"device\" on a tree that render_episode wrote (resolution 512)")
+    ap.add_argument("--view-augment", default=None, help="a perturb.parse spec or preset (camera_pose+light_color): also time the render_targets "
+                    "loader with view_augment=SPEC, and gn_view_augment_tiled alone (needs --render-textures)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.view_augment and not args.render_textures:
+        ap.error("--view-augment needs --render-textures: the augmentation re-draws the targets a render_targets loader draws")
     from genima_amd import configs
     from genima_amd.engine import Engine
     from genima_amd.pipeline import HashTokenizer
@@ -197,6 +204,10 @@ def main():
                 drawn = {"rendered_tree_cache_device": D.DataLoader(ds2, B, tok, R, shuffle=True, seed=0, cache="device"),
                          "rendered_tree_cache_device_render_targets": D.DataLoader(ds2, B, tok, R, shuffle=True, seed=0, cache="device",
                                                                                    render_targets=Rn.TrajectorySource(cfg2))}
+                base_key, aug_key = "rendered_tree_cache_device_render_targets", "rendered_tree_cache_device_render_targets_view_augment"
+                if args.view_augment:
+                    drawn[aug_key] = D.DataLoader(ds2, B, tok, R, shuffle=True, seed=0, cache="device", render_targets=Rn.TrajectorySource(cfg2),
+                                                  view_augment=args.view_augment)
                 for ld in drawn.values():
                     epoch_seconds(ld, step)  # the caches fill
             times = {"cache_none": [], "cache_device": [], "resident_synthetic_batch": [], **{k: [] for k in drawn}}
@@ -207,6 +218,36 @@ def main():
                     times[k].append(epoch_seconds(ld, step))
                 times["resident_synthetic_batch"].append(resident_seconds())
             res["train_step_ms"] = {k: summary(v, 1e3) for k, v in times.items()}
+            if args.view_augment and drawn:
+                from genima_amd import perturb
+
+                base, aug = res["train_step_ms"][base_key], res["train_step_ms"][aug_key]
+                va = dict(spec=args.view_augment, setting=perturb.parse(args.view_augment).describe(), baseline=base_key,
+                          train_step_delta_ms=aug["median"] - base["median"], baseline_spread_ms=base["max"] - base["min"])
+                va["delta_exceeds_baseline_spread"] = abs(va["train_step_delta_ms"]) > va["baseline_spread_ms"]
+                # the kernel alone, on the tables of one of the loader's own batches and frames that lie apart on the device
+                host = next(iter(D.DataLoader(ds2, B, tok, R, shuffle=True, seed=0, prefetch=0, render_targets=Rn.TrajectorySource(cfg2),
+                                              view_augment=args.view_augment)))
+                M, colour = (host["render_views"][k].to(dev) for k in ("M", "colour"))
+                n = int(M.shape[0])
+                out_u8 = torch.empty((n, R, R, 3), dtype=torch.uint8, device=dev)
+                out_f16 = torch.empty((n, R, R, 8), dtype=torch.float16, device=dev)
+                rev = torch.empty((n, 4), dtype=torch.int32, device=dev)
+                fn = lambda: E.view_augment_tiled(M, colour, R // 2, R // 2, frames=ptrs[:n], out_u8=out_u8, out_f16=out_f16, n_revealed=rev)  # noqa: E731
+                va["kernel_us"] = summary([kernel_us(fn) for _ in range(args.rounds)])
+                va["kernel_mb"] = dict(read_u8=n * R * R * 3 / 1e6, write_u8=n * R * R * 3 / 1e6, write_f16=n * R * R * 16 / 1e6)
+                # the revealed share over one epoch of the loader's batches: per tile camera, and over the cameras the setting turns
+                counts = torch.zeros(4, dtype=torch.int64, device=dev)
+                seen = 0
+                for b in drawn[aug_key]:
+                    r = D.to_device(E, b)["view_revealed"]
+                    counts += r.sum(dim=0)
+                    seen += int(r.shape[0])
+                share = (counts.double() / (seen * (R // 2) ** 2)).tolist()
+                va["revealed_share_per_tile_camera"] = dict(zip(Rn.tile_cameras(cfg2.cameras), share))
+                turned = [s for s in share if s > 0]
+                va["revealed_share_of_turned_cameras"] = sum(turned) / len(turned) if turned else 0.0
+                res["view_augment"] = va
             res["train_family"], res["train_steps_per_epoch"] = args.family, n_batches
     print(json.dumps(res, indent=1), flush=True)
     if args.out:
