@@ -1067,7 +1067,7 @@ int32_t gn_clip_coef(gn_ctx* ctx, const float* sumsq, float* clip, float max_nor
 int32_t gn_adamw_flat(gn_ctx* ctx, float* param, float* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                       float weight_decay, int32_t step, const float* clip_dev, float grad_scale, void* half_out, int32_t zero_grad) {
   GN_REQUIRE(ctx && param && grad && m && v && n > 0 && step >= 1, "gn_adamw_flat: bad arguments");
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)(1.0 - pow((double)beta2, (double)step));  // f64, rounded once
   hipLaunchKernelGGL(adamw_kernel, dim3(nblk(n)), dim3(256), 0, ctx->stream, param, grad, m, v, (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
                      clip_dev, grad_scale, (f16*)half_out, zero_grad);
   GN_LAUNCH_CHECK();

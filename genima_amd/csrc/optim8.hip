@@ -157,8 +157,8 @@ int32_t gn_adamw8_flat(gn_ctx* ctx, float* param, float* grad, int64_t n, void* 
              "gn_adamw8_flat: param / grad must be 16-byte aligned, half_out 8-byte, the code buffers 4-byte, the block table 16-byte");
   Adam8Hyper h;
   h.lr = lr; h.b1 = beta1; h.b2 = beta2; h.eps = eps; h.wd = weight_decay; h.gscale = grad_scale;
-  h.bc1 = 1.0f - powf(beta1, (float)step);
-  h.bc2 = 1.0f - powf(beta2, (float)step);
+  h.bc1 = (float)(1.0 - pow((double)beta1, (double)step));  // f64, rounded once: the step size of gn_adamw_flat (backward.hip)
+  h.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
   const int want = (n_blocks + 3) / 4;
   const int grid = want < 2048 ? want : 2048;  // persistent: 8 workgroups of 4 waves per CU walk the table
   hipLaunchKernelGGL(adamw8_kernel, dim3(grid), dim3(256), 0, ctx->stream, param, grad, (uint8_t*)m_codes, (uint8_t*)v_codes, m_absmax, v_absmax,

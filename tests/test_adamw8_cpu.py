@@ -46,7 +46,7 @@ def restate_step(state: dict, grad: torch.Tensor, expand, step: int, clip_coef=N
     lr, b1, b2, eps, wd, gsc = (f(np.float32(v)) for v in (lr, beta1, beta2, eps, wd, grad_scale))
     one = f(1.0)
     gs = gsc * (f(np.float32(clip_coef)) if clip_coef is not None else one)
-    bc1, bc2 = one - np.power(b1, f(step)), one - np.power(b2, f(step))
+    bc1, bc2 = f(1.0 - np.power(np.float64(b1), step)), f(1.0 - np.power(np.float64(b2), step))  # an f64 power, rounded once (the host code)
     decay, omb1, omb2, rbc2, slr = one - lr * wd, one - b1, one - b2, np.sqrt(bc2), lr / bc1
     S, U = optim8.dynamic_map(True).to(dtype), optim8.dynamic_map(False).to(dtype)
     nb = state["m_absmax"].numel()
